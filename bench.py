@@ -11,9 +11,12 @@ call (forward + first-order backward to the positions) over one batch.  The path
 independent molecules: every rank owns its own 256-frame batch (weak scaling), no data-path
 collective.  edge-messages/s = E * n_interactions * steps / time, summed over ranks.
 
-Prints ONE JSON line on rank 0 with `roofline` (dominant kernel, HIP-event timed on the launch
-stream in a separate eager pass) and `cpu_baseline` (the CPU oracle = torch restatement of the
-reference, timed on the host cores, N=1 only).
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and prints the
+headline (`metric`, `value`, `unit`, `ms_per_step`, ...); `--dump-outputs DIR` writes the energies
+and forces of the last timed step as DIR/<name>.npy (seeded inputs: two builds compare file by file).
+`--full` adds everything else the line has carried: `roofline` (dominant kernel, HIP-event timed on
+the launch stream in a separate eager pass, in-run counter passes), `cpu_baseline` (the reference on
+the host cores, N=1 only) and the `painn` / `water` / `train` / `md` / `sweep` / ... sub-objects.
 """
 import argparse
 import json
@@ -71,7 +74,17 @@ def parse():
     ap.add_argument("--detail", default=os.path.join(ROOT, "bench_detail.json"),
                     help="where the FULL record of the run goes (every note, per-kernel table and counter detail); the stdout line is its compact, numbers-only face")
     ap.add_argument("--dry-run", action="store_true", help="rank wiring only (launcher, process group, barrier, max-over-ranks reduction), no device work: for the CPU test of --gpus N")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: per-kernel roofline and counter passes, CPU baseline, the "
+                         "value before the clock ramp, and the painn / water / train / md / sweep / scatter_add / neighbor_list / drop_in sub-objects")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last step (eval mode: energy, forces) as DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.mode != "eval":
+        ap.error("--dump-outputs: only the eval force call (--mode eval) writes its outputs")
+    return args
 
 
 def _free_port():
@@ -226,6 +239,25 @@ def emit(full, detail_path):
     assert len(s) < LINE_LIMIT, len(s)
     print(s, flush=True)
     return line
+
+
+DUMP_LIMIT = 64 << 20          # bytes over all files of --dump-outputs
+
+
+def dump_outputs(out_dir, arrays):
+    """Write each tensor of `arrays` as out_dir/<name>.npy (float32, float64 where the path computed in float64).  An array
+    beyond its share of DUMP_LIMIT is written as a fixed, seeded sample of its rows (sorted, the same for the same shape)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_LIMIT // max(len(arrays), 1)
+    for name, t in arrays.items():
+        t = t.detach().cpu()
+        a = (t.double() if t.dtype == torch.float64 else t.float()).numpy()
+        row_bytes = a.nbytes // max(a.shape[0], 1) if a.ndim else a.nbytes
+        if a.nbytes > share:
+            keep = max(share // max(row_bytes, 1), 1)
+            a = a[np.sort(np.random.RandomState(0).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
 
 
 def dry_run(args, rank, world):
@@ -701,16 +733,18 @@ def eval_leg(args, kind, workload, model, rep_p, head_p, rank, world, dev, dist,
             torch.cuda.synchronize()
 
     step = graph.replay if graph is not None else force_call
-    # the same K timed steps WITHOUT the clock ramp first (reported beside the headline as value_without_ramp: what a freshly
-    # started process measures over these few milliseconds)
-    for _ in range(warmup):
-        step()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(steps):
-        step()
-    torch.cuda.synchronize()
-    dt_cold = time.perf_counter() - t0
+    dt_cold = None
+    if args.full:
+        # the same K timed steps WITHOUT the clock ramp first (reported beside the headline as value_without_ramp: what a freshly
+        # started process measures over these few milliseconds)
+        for _ in range(warmup):
+            step()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(steps):
+            step()
+        torch.cuda.synchronize()
+        dt_cold = time.perf_counter() - t0
     # clock ramp, untimed and BEFORE the W warm-up steps: a freshly started process reaches its sustained clocks only after some
     # tens of milliseconds of work -- with the driver's --steps 20 --warmup 5 the whole measurement is 6 ms long and came out 8 %
     # below the same binary at --steps 200 (one box, alternating runs).  Bounded: RAMP_S seconds of replays, reported in `config`
@@ -729,13 +763,14 @@ def eval_leg(args, kind, workload, model, rep_p, head_p, rank, world, dev, dist,
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(steps):
-        step()
+        out = step()
     torch.cuda.synchronize()
     if dist is not None:
         dist.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     if graph is not None:   # the LAST timed replay must still reproduce the eager result (not only the first one)
+        out = (ge, gf)
         err = float((gf - f_ref).abs().max() / f_ref.abs().max())
         if not (err < 1e-5):
             raise RuntimeError("graph replay deviates from eager after the timed loop: %g" % err)
@@ -749,9 +784,10 @@ def eval_leg(args, kind, workload, model, rep_p, head_p, rank, world, dev, dist,
         dist.all_reduce(et, op=dist.ReduceOp.SUM)
         E_total = int(et.item())
     value = E_total * n_int * steps / dt / 1e6
-    res = {"value": value, "value_without_ramp": E * n_int * steps / dt_cold / 1e6, "dt": dt, "steps": steps, "E": E, "N": N, "frames": hi - lo, "graph": graph is not None, "batch": batch, "inp": inp, "n_ramp": n_ramp,
-           "e_ref": e_ref, "f_ref": f_ref, "n_int": n_int, "F": F, "n_rbf": n_rbf, "cutoff": cutoff}
-    if rank != 0:
+    res = {"value": value, "value_without_ramp": E * n_int * steps / dt_cold / 1e6 if dt_cold else None, "dt": dt, "steps": steps, "E": E, "N": N,
+           "frames": hi - lo, "graph": graph is not None, "batch": batch, "inp": inp, "n_ramp": n_ramp, "outputs": {"energy": out[0], "forces": out[1]},
+           "e_ref": e_ref, "f_ref": f_ref, "n_int": n_int, "F": F, "n_rbf": n_rbf, "cutoff": cutoff, "kernels": None, "roofline": None, "cpu": None}
+    if rank != 0 or not args.full:
         return res
 
     # ---------------- per-kernel timing (separate eager pass, HIP events on the launch stream)
@@ -1143,7 +1179,7 @@ def main():
     model, rep_p, head_p = make_model(args.kind)
 
     if args.mode == "train":
-        line = train_measure(args, args.kind, rank, world, dev, dist, model, rep_p, head_p, args.steps, args.warmup, with_pmc=True)
+        line = train_measure(args, args.kind, rank, world, dev, dist, model, rep_p, head_p, args.steps, args.warmup, with_pmc=args.full)
         if rank == 0 and line is not None:
             emit(line, args.detail)
         if dist is not None:
@@ -1159,117 +1195,122 @@ def main():
         if dist is not None:
             dist.destroy_process_group()
         return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, r["outputs"])
     value, dt, E, N, batch, inp = r["value"], r["dt"], r["E"], r["N"], r["batch"], r["inp"]
     kernels, roofline, cpu = r["kernels"], r["roofline"], r["cpu"]
-    default_line = world == 1 and args.kind == "schnet" and args.workload == "aspirin"
+    default_line = args.full and world == 1 and args.kind == "schnet" and args.workload == "aspirin"
 
-    # ---------------- scatter_add op alone (north_star: HBM roofline of the segmented sum) and the measured copy
-    # bandwidth of this box beside it (fraction of nominal AND of measured copy bandwidth).
-    # Both are timed as 50 launches inside ONE HIP graph (no host launch gaps), with events around the replay.
-    idx = inp["_idx_i"]
-    from schnetpack_amd import ops
-    src = torch.empty(64 * 1024 * 1024, device=dev)     # 256 MB: beyond the Infinity Cache together with dst
-    dst = torch.empty_like(src)
+    # everything below the headline (and its checks) runs with --full only: a plain run stops at the timed steps
+    scatter = nbl = None
+    if args.full:
+        # ---------------- scatter_add op alone (north_star: HBM roofline of the segmented sum) and the measured copy
+        # bandwidth of this box beside it (fraction of nominal AND of measured copy bandwidth).
+        # Both are timed as 50 launches inside ONE HIP graph (no host launch gaps), with events around the replay.
+        idx = inp["_idx_i"]
+        from schnetpack_amd import ops
+        src = torch.empty(64 * 1024 * 1024, device=dev)     # 256 MB: beyond the Infinity Cache together with dst
+        dst = torch.empty_like(src)
 
-    def graph_time_us(fn, reps=50):
-        fn(); torch.cuda.synchronize()
-        side = torch.cuda.Stream(); side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            fn()
-        torch.cuda.current_stream().wait_stream(side); torch.cuda.synchronize()
-        gg = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(gg):
-            for _ in range(reps):
+        def graph_time_us(fn, reps=50):
+            fn(); torch.cuda.synchronize()
+            side = torch.cuda.Stream(); side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
                 fn()
-        gg.replay(); torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(); gg.replay(); e1.record(); torch.cuda.synchronize()
-        return 1e3 * e0.elapsed_time(e1) / reps
+            torch.cuda.current_stream().wait_stream(side); torch.cuda.synchronize()
+            gg = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(gg):
+                for _ in range(reps):
+                    fn()
+            gg.replay(); torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(); gg.replay(); e1.record(); torch.cuda.synchronize()
+            return 1e3 * e0.elapsed_time(e1) / reps
 
-    def scatter_case(idx_, n_rows, chan, n_buf, reps, label):
-        """`reps` launches of spk_scatter_add_f32 inside one HIP graph, cycling through `n_buf` input / output buffer pairs: with n_buf = 1 the
-        operand stays in the 256 MB Infinity Cache between launches, with a working set far beyond it every launch streams from DRAM."""
-        e_ = int(idx_.shape[0])
-        rp_ = ops.segment_rowptr(idx_, n_rows)
-        xb = [torch.randn(e_, chan, device=dev) for _ in range(n_buf)]
-        yb = [torch.empty(n_rows, chan, device=dev) for _ in range(n_buf)]
-        it = [0]
+        def scatter_case(idx_, n_rows, chan, n_buf, reps, label):
+            """`reps` launches of spk_scatter_add_f32 inside one HIP graph, cycling through `n_buf` input / output buffer pairs: with n_buf = 1 the
+            operand stays in the 256 MB Infinity Cache between launches, with a working set far beyond it every launch streams from DRAM."""
+            e_ = int(idx_.shape[0])
+            rp_ = ops.segment_rowptr(idx_, n_rows)
+            xb = [torch.randn(e_, chan, device=dev) for _ in range(n_buf)]
+            yb = [torch.empty(n_rows, chan, device=dev) for _ in range(n_buf)]
+            it = [0]
 
-        def once():
-            k = it[0] % n_buf
-            it[0] += 1
-            _lib.check(_lib.lib().spk_scatter_add_f32(_lib.fptr(xb[k]), _lib.iptr(idx_), _lib.iptr(rp_, torch.int32), 1, e_, chan, n_rows, _lib.fptr(yb[k]), _lib.stream()))
-        us = graph_time_us(once, reps=reps)
-        nbytes = 4.0 * e_ * chan + 8.0 * e_ + 4.0 * n_rows * chan
-        gbs = nbytes / (us * 1e-6) / 1e9
-        ws = n_buf * (4.0 * e_ * chan + 4.0 * n_rows * chan) / 1e6
-        del xb, yb
-        return {"what": label, "shape": [e_, chan, n_rows], "buffers": n_buf, "working_set_MB": round(ws, 1), "us": round(us, 2), "achieved": round(gbs, 1),
-                "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(gbs / HBM_PEAK_GBS, 4)}
+            def once():
+                k = it[0] % n_buf
+                it[0] += 1
+                _lib.check(_lib.lib().spk_scatter_add_f32(_lib.fptr(xb[k]), _lib.iptr(idx_), _lib.iptr(rp_, torch.int32), 1, e_, chan, n_rows, _lib.fptr(yb[k]), _lib.stream()))
+            us = graph_time_us(once, reps=reps)
+            nbytes = 4.0 * e_ * chan + 8.0 * e_ + 4.0 * n_rows * chan
+            gbs = nbytes / (us * 1e-6) / 1e9
+            ws = n_buf * (4.0 * e_ * chan + 4.0 * n_rows * chan) / 1e6
+            del xb, yb
+            return {"what": label, "shape": [e_, chan, n_rows], "buffers": n_buf, "working_set_MB": round(ws, 1), "us": round(us, 2), "achieved": round(gbs, 1),
+                    "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(gbs / HBM_PEAK_GBS, 4)}
 
-    cp_us = graph_time_us(lambda: dst.copy_(src), reps=10)
-    copy_gbs = 2.0 * src.numel() * 4 / (cp_us * 1e-6) / 1e9
-    del src, dst
-    scatter = {"measured_copy_GBs": round(copy_gbs, 1)}
-    cases = [("cache_resident", idx, N, F, 1, 50, "configs[1] x_ij shape, ONE buffer replayed: the 43 MB operand stays in the Infinity Cache (an upper bound, not a DRAM figure)"),
-             ("dram_rotating", idx, N, F, 16, 48, "configs[1] x_ij shape, 16 rotating buffer pairs (working set >> 256 MB MALL): every launch streams from DRAM")]
-    if default_line and not args.no_md:
-        wb_ = cached_water_box(args.water_side, 0)
-        cases.append(("dram_water_dmu", wb_["idx_i"].to(dev), int(wb_["Z"].shape[0]), 3 * F, 2, 6,
-                      "configs[4] per-bead PaiNN dmu shape (E x 3F floats = 2.6 GB per launch, far beyond the MALL)"))
-    for name, idx_, n_rows, chan, n_buf, reps, label in cases:
+        cp_us = graph_time_us(lambda: dst.copy_(src), reps=10)
+        copy_gbs = 2.0 * src.numel() * 4 / (cp_us * 1e-6) / 1e9
+        del src, dst
+        scatter = {"measured_copy_GBs": round(copy_gbs, 1)}
+        cases = [("cache_resident", idx, N, F, 1, 50, "configs[1] x_ij shape, ONE buffer replayed: the 43 MB operand stays in the Infinity Cache (an upper bound, not a DRAM figure)"),
+                 ("dram_rotating", idx, N, F, 16, 48, "configs[1] x_ij shape, 16 rotating buffer pairs (working set >> 256 MB MALL): every launch streams from DRAM")]
+        if default_line and not args.no_md:
+            wb_ = cached_water_box(args.water_side, 0)
+            cases.append(("dram_water_dmu", wb_["idx_i"].to(dev), int(wb_["Z"].shape[0]), 3 * F, 2, 6,
+                          "configs[4] per-bead PaiNN dmu shape (E x 3F floats = 2.6 GB per launch, far beyond the MALL)"))
+        for name, idx_, n_rows, chan, n_buf, reps, label in cases:
+            try:
+                scatter[name] = scatter_case(idx_, n_rows, chan, n_buf, reps, label)
+                scatter[name]["frac_of_measured_copy"] = round(scatter[name]["achieved"] / copy_gbs, 4)
+            except Exception as exc:  # pragma: no cover
+                scatter[name] = {"error": str(exc)[:200]}
+            torch.cuda.empty_cache()
+        dram = [v["frac"] for k, v in scatter.items() if k.startswith("dram_") and isinstance(v, dict) and "frac" in v]
+        scatter["frac_dram"] = min(dram) if dram else None        # north_star's ">= 40 % of the HBM roofline on the scatter_add": the WORST of the DRAM-resident cases
+        scatter["note"] = ("algorithmic bytes 4EC + 8E + 4NC per launch over the HIP-graph time of the launches (events around one replay); copy = 256 MB device-to-device "
+                           "torch copy (read + write bytes) timed the same way; frac = achieved / 8 TB/s; frac_dram = the smaller of the DRAM-resident cases")
+
+        # ---------------- neighbour-list rebuild on the device for this workload (SURVEY.md section 8 row f1)
+        from schnetpack_amd import neighborlist as NL
+        nl_cell = batch["cell"].reshape(1, 3, 3).to(dev) if args.workload == "water" else None
+        nl_pbc = torch.tensor([True, True, True], device=dev) if args.workload == "water" else None
+        nl_kw = dict(idx_m=inp["_idx_m"], cell=nl_cell, pbc=nl_pbc, n_systems=int(batch["n_mol"]))
+        nl = NL.neighbor_list(inp["_positions"].detach(), cutoff, **nl_kw)
+        t_nl = []
+        for _ in range(5):
+            torch.cuda.synchronize()
+            c0 = time.perf_counter()
+            NL.neighbor_list(inp["_positions"].detach(), cutoff, **nl_kw)
+            torch.cuda.synchronize()
+            t_nl.append(time.perf_counter() - c0)
+        t_nl.sort()
+        # bit-exact comparison with the list the workload was built with (north_star: "neighbour indices bit-exact"): both lists in the
+        # canonical order (idx_i, idx_j, image shift), indices and integer image shifts compared with torch.equal -- not a pair count
+        def _canonical(ii, jj, off):
+            if nl_cell is not None:
+                sh = torch.round(off.double() @ torch.linalg.inv(nl_cell[0].double())).to(torch.int64)
+            else:
+                sh = torch.zeros(ii.shape[0], 3, dtype=torch.int64, device=ii.device)
+            key = ((ii.to(torch.int64) * int(inp["_positions"].shape[0]) + jj.to(torch.int64)) * 27 + (sh[:, 0] + 1) * 9 + (sh[:, 1] + 1) * 3 + (sh[:, 2] + 1))
+            order = torch.argsort(key, stable=True)
+            return ii[order].to(torch.int64), jj[order].to(torch.int64), sh[order]
         try:
-            scatter[name] = scatter_case(idx_, n_rows, chan, n_buf, reps, label)
-            scatter[name]["frac_of_measured_copy"] = round(scatter[name]["achieved"] / copy_gbs, 4)
+            nl_full = NL.neighbor_list(inp["_positions"].detach(), cutoff, **nl_kw)
+            ca = _canonical(nl_full["_idx_i"], nl_full["_idx_j"], nl_full["_offsets"])
+            cb = _canonical(inp["_idx_i"], inp["_idx_j"], inp["_offsets"])
+            nl_exact = bool(ca[0].shape == cb[0].shape and all(torch.equal(x, y) for x, y in zip(ca, cb)))
         except Exception as exc:  # pragma: no cover
-            scatter[name] = {"error": str(exc)[:200]}
-        torch.cuda.empty_cache()
-    dram = [v["frac"] for k, v in scatter.items() if k.startswith("dram_") and isinstance(v, dict) and "frac" in v]
-    scatter["frac_dram"] = min(dram) if dram else None        # north_star's ">= 40 % of the HBM roofline on the scatter_add": the WORST of the DRAM-resident cases
-    scatter["note"] = ("algorithmic bytes 4EC + 8E + 4NC per launch over the HIP-graph time of the launches (events around one replay); copy = 256 MB device-to-device "
-                       "torch copy (read + write bytes) timed the same way; frac = achieved / 8 TB/s; frac_dram = the smaller of the DRAM-resident cases")
-
-    # ---------------- neighbour-list rebuild on the device for this workload (SURVEY.md section 8 row f1)
-    from schnetpack_amd import neighborlist as NL
-    nl_cell = batch["cell"].reshape(1, 3, 3).to(dev) if args.workload == "water" else None
-    nl_pbc = torch.tensor([True, True, True], device=dev) if args.workload == "water" else None
-    nl_kw = dict(idx_m=inp["_idx_m"], cell=nl_cell, pbc=nl_pbc, n_systems=int(batch["n_mol"]))
-    nl = NL.neighbor_list(inp["_positions"].detach(), cutoff, **nl_kw)
-    t_nl = []
-    for _ in range(5):
-        torch.cuda.synchronize()
-        c0 = time.perf_counter()
-        NL.neighbor_list(inp["_positions"].detach(), cutoff, **nl_kw)
-        torch.cuda.synchronize()
-        t_nl.append(time.perf_counter() - c0)
-    t_nl.sort()
-    # bit-exact comparison with the list the workload was built with (north_star: "neighbour indices bit-exact"): both lists in the
-    # canonical order (idx_i, idx_j, image shift), indices and integer image shifts compared with torch.equal -- not a pair count
-    def _canonical(ii, jj, off):
-        if nl_cell is not None:
-            sh = torch.round(off.double() @ torch.linalg.inv(nl_cell[0].double())).to(torch.int64)
-        else:
-            sh = torch.zeros(ii.shape[0], 3, dtype=torch.int64, device=ii.device)
-        key = ((ii.to(torch.int64) * int(inp["_positions"].shape[0]) + jj.to(torch.int64)) * 27 + (sh[:, 0] + 1) * 9 + (sh[:, 1] + 1) * 3 + (sh[:, 2] + 1))
-        order = torch.argsort(key, stable=True)
-        return ii[order].to(torch.int64), jj[order].to(torch.int64), sh[order]
-    try:
-        nl_full = NL.neighbor_list(inp["_positions"].detach(), cutoff, **nl_kw)
-        ca = _canonical(nl_full["_idx_i"], nl_full["_idx_j"], nl_full["_offsets"])
-        cb = _canonical(inp["_idx_i"], inp["_idx_j"], inp["_offsets"])
-        nl_exact = bool(ca[0].shape == cb[0].shape and all(torch.equal(x, y) for x, y in zip(ca, cb)))
-    except Exception as exc:  # pragma: no cover
-        nl_exact = "error: %s" % str(exc)[:120]
-    nbl = {"pairs": int(nl["_idx_i"].shape[0]), "matches_input_list": nl_exact, "pair_count_matches": int(nl["_idx_i"].shape[0]) == E,
-           "build_ms": round(1e3 * t_nl[len(t_nl) // 2], 4), "M_pairs_per_s": round(E / t_nl[len(t_nl) // 2] / 1e6, 1),
-           "note": "count + fill incl. allocation and the one D2H of the pair count (wall clock, median of 5)"}
-    if cpu is not None and args.workload == "aspirin":
-        # the reference's per-molecule TorchNeighborList loop, restated (oracle/nbl_oracle.py), same batch
-        from oracle import nbl_oracle as NB
-        c0 = time.perf_counter()
-        oi, _, _, _ = NB.batch_neighbor_list(batch["R"], batch["idx_m"], None, None, cutoff)
-        nbl["cpu_oracle_ms"] = round(1e3 * (time.perf_counter() - c0), 2)
-        nbl["cpu_oracle_pairs"] = int(oi.shape[0])
+            nl_exact = "error: %s" % str(exc)[:120]
+        nbl = {"pairs": int(nl["_idx_i"].shape[0]), "matches_input_list": nl_exact, "pair_count_matches": int(nl["_idx_i"].shape[0]) == E,
+               "build_ms": round(1e3 * t_nl[len(t_nl) // 2], 4), "M_pairs_per_s": round(E / t_nl[len(t_nl) // 2] / 1e6, 1),
+               "note": "count + fill incl. allocation and the one D2H of the pair count (wall clock, median of 5)"}
+        if cpu is not None and args.workload == "aspirin":
+            # the reference's per-molecule TorchNeighborList loop, restated (oracle/nbl_oracle.py), same batch
+            from oracle import nbl_oracle as NB
+            c0 = time.perf_counter()
+            oi, _, _, _ = NB.batch_neighbor_list(batch["R"], batch["idx_m"], None, None, cutoff)
+            nbl["cpu_oracle_ms"] = round(1e3 * (time.perf_counter() - c0), 2)
+            nbl["cpu_oracle_pairs"] = int(oi.shape[0])
 
     # ---------------- configs[2]: the same 256-frame batch through PaiNN (default line only)
     painn = None
@@ -1326,7 +1367,7 @@ def main():
     # ---------------- the other half of BASELINE's metric: MD ns/day (on-device NVE loop, rows f1-f3), aspirin x 256 and the
     # 32k-atom water box, same model kind; configs[4] as stated: PaiNN, 8 beads, RPMD 0.2 fs + PILE-L NVT on the full box
     md = None
-    if world == 1 and not args.no_md:
+    if args.full and world == 1 and not args.no_md:
         md = {}
         keys = ("ns_per_day", "ms_per_step", "n_atoms", "pairs_in_list", "trajectories", "rebuilds", "fraction_in_rebuilds", "dt_fs", "steps", "hip_graph")
         for wl in ("aspirin", "water"):
@@ -1351,7 +1392,7 @@ def main():
             except Exception as exc:  # pragma: no cover
                 md["water_pimd"] = {"error": str(exc)[:300]}
     sweep = None
-    if world == 1 and not args.no_sweep:
+    if args.full and world == 1 and not args.no_sweep:
         try:
             sweep = sweep_measure(model, dev, args.kind)
             if default_line:        # PaiNN rows beside the SchNet ones (symmetric k = 16 / 32 / 64, asymmetric k = 32)
@@ -1416,7 +1457,7 @@ def main():
     hi_lo = r["frames"]
     line = {
         "metric": "M edge-messages/s (eval force call, %s, %s)" % ("MD17-aspirin 256-frame batch" if args.workload == "aspirin" else "32k-atom bulk-water PBC box", "SchNet" if args.kind == "schnet" else "PaiNN"),
-        "value": round(value, 2), "value_without_ramp": round(r["value_without_ramp"], 2) if world == 1 else None,
+        "value": round(value, 2), "value_without_ramp": round(r["value_without_ramp"], 2) if world == 1 and r["value_without_ramp"] is not None else None,
         "unit": "M edge-messages/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": round(1e3 * dt / args.steps, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
         "dtype": "f32", "data": "synthetic",
@@ -1429,8 +1470,9 @@ def main():
                    "parallelism": "frames sharded over %d rank(s), no data-path collective" % world,
                    "world_size": world, "backend": (dist.get_backend() + (" (RCCL)" if dist.get_backend() == "nccl" else "")) if dist is not None else None,
                    "hip_graph": r["graph"], "variant": args.variant, "compute_units": info["compute_units"],
-                   "preconditioning": "%d untimed replays (%.2f s clock ramp) before the %d warm-up steps; the timed region is exactly %d steps; "
-                                      "value_without_ramp = the same %d steps timed once before the ramp (this rank)" % (r["n_ramp"], RAMP_S, args.warmup, r["steps"], r["steps"])},
+                   "preconditioning": "%d untimed replays (%.2f s clock ramp) before the %d warm-up steps; the timed region is exactly %d steps%s" % (
+                       r["n_ramp"], RAMP_S, args.warmup, r["steps"],
+                       "; value_without_ramp = the same %d steps timed once before the ramp (this rank)" % r["steps"] if r["value_without_ramp"] is not None else "")},
         "roofline": roofline, "cpu_baseline": cpu, "painn": painn, "water": water, "train": train, "md": md, "sweep": sweep, "drop_in": drop_in, "experiments": experiments,
         "kernels": kernels, "scatter_add": scatter, "neighbor_list": nbl, "molecule_cliff": cliff,
     }
@@ -1441,7 +1483,7 @@ def main():
             if isinstance(water.get(k_), dict) and "n_atoms" in water[k_]:
                 line["config"]["water_atoms"], line["config"]["water_pairs"] = water[k_]["n_atoms"], water[k_]["n_edges"]      # 22^3 x 3 = 31 944 atoms (the survey's 32 001 is another lattice)
                 break
-    line["parity_ledger_worst"] = parity_ledger_worst()
+    line["parity_ledger_worst"] = parity_ledger_worst() if args.full else None
     line["config"]["multi_gpu_measured"] = world > 1      # N > 1 has never run on hardware from this repo: the driver's SCALE run is the measurement
     emit(line, args.detail)
     if dist is not None:
@@ -1646,19 +1688,20 @@ def train_measure(args, kind, rank, world, dev, dist, model, rep_p, head_p, step
         return None
     # launch count of one step (library + framework kernels): torch's kineto profile of one eager step
     launches = None
-    try:
-        from torch.profiler import profile, ProfilerActivity
-        tstep_use_graph = tstep.use_graph
-        tstep.use_graph = False
-        step(0)
-        torch.cuda.synchronize()
-        with profile(activities=[ProfilerActivity.CUDA]) as pr:
-            step(1)
+    if args.full:
+        try:
+            from torch.profiler import profile, ProfilerActivity
+            tstep_use_graph = tstep.use_graph
+            tstep.use_graph = False
+            step(0)
             torch.cuda.synchronize()
-        launches = sum(1 for ev in pr.events() if str(getattr(ev, "device_type", "")).endswith("CUDA") and not ev.name.lower().startswith(("memcpy", "memset")))
-        tstep.use_graph = tstep_use_graph
-    except Exception as exc:  # pragma: no cover
-        sys.stderr.write("[bench] launch count unavailable (%s)\n" % exc)
+            with profile(activities=[ProfilerActivity.CUDA]) as pr:
+                step(1)
+                torch.cuda.synchronize()
+            launches = sum(1 for ev in pr.events() if str(getattr(ev, "device_type", "")).endswith("CUDA") and not ev.name.lower().startswith(("memcpy", "memset")))
+            tstep.use_graph = tstep_use_graph
+        except Exception as exc:  # pragma: no cover
+            sys.stderr.write("[bench] launch count unavailable (%s)\n" % exc)
     ms_step = 1e3 * dt / steps
     # training = forward + recorded first-order backward (B_force) + the backward of that pass (about 2x the force call):
     # booked as 3 x B_force of the per-GPU batch; the step is launch-latency bound at this size, which the fraction shows
@@ -1684,7 +1727,7 @@ def train_measure(args, kind, rank, world, dev, dist, model, rep_p, head_p, step
                                               "parameters of the optimizer, the saved activations of all four passes and the framework's copies" % (PMC_TRAIN_STEPS, PMC_TRAIN_STEPS))
             roofline["traffic_frac_of_hbm_peak"] = round(roofline["traffic"] / (ms_step * 1e-3) / (HBM_PEAK_GBS * 1e9), 4)
     cpu = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         ncores = min(os.cpu_count() or 1, 16)
         torch.set_num_threads(ncores)
         b, _, Et, Ft = pool[0]

@@ -391,8 +391,31 @@ def deep_bessel_goldens(ns):
         save(name + ".npz", b, res, weights_checksum=checksum(p), kind=kind, cutoff=5.0, radial="bessel", n_interactions=6)
 
 
+def collate_goldens(ns):
+    """The reference's ``_atoms_collate_fn`` (data/loader.py:13-58) on five seeded systems (tests/test_data_wire.py): the stored
+    inputs ``in<s>_<key>`` and the collated batch ``ref_<key>``, so that the collate mirror is checked without the reference."""
+    rng = np.random.RandomState(0)
+    systems = []
+    for kind in ("aspirin", "ethanol", "aspirin", "ethanol", "ethanol"):
+        Z, R0 = (S.ASPIRIN_Z, np.asarray(S.ASPIRIN_R)) if kind == "aspirin" else (S.ETHANOL_Z, np.asarray(S.ETHANOL_R))
+        R = R0 + 0.05 * rng.randn(*R0.shape)
+        ii, jj = S.neighbor_pairs_open(R, 5.0)
+        t = torch.arange(min(4, len(ii)))
+        systems.append({"_atomic_numbers": torch.tensor(Z), "_positions": torch.from_numpy(R).float(), "_n_atoms": torch.tensor([len(Z)]),
+                        "_idx_i": torch.from_numpy(ii), "_idx_j": torch.from_numpy(jj), "_offsets": torch.zeros(len(ii), 3),
+                        "_cell": torch.zeros(1, 3, 3), "_pbc": torch.zeros(3, dtype=torch.bool), "energy": torch.from_numpy(rng.randn(1)).float(),
+                        "_idx_i_triples": t.clone(), "_idx_j_triples": t.clone(), "_idx_k_triples": t.clone()})
+    ref = ns.loader._atoms_collate_fn(systems)
+    arrs = {"in%d_%s" % (s, k): v.numpy() for s, d in enumerate(systems) for k, v in d.items()}
+    arrs.update({"ref_" + k: v.numpy() for k, v in ref.items()})
+    np.savez_compressed(os.path.join(OUT, "collate_reference.npz"), **arrs)
+    print("wrote collate_reference.npz", len(arrs), "arrays")
+
+
 if __name__ == "__main__":
-    if len(sys.argv) > 1 and sys.argv[1] == "deep":
+    if len(sys.argv) > 1 and sys.argv[1] == "collate":
+        collate_goldens(refshim.load())
+    elif len(sys.argv) > 1 and sys.argv[1] == "deep":
         deep_model_goldens(refshim.load())
     elif len(sys.argv) > 1 and sys.argv[1] == "deep_bessel":
         deep_bessel_goldens(refshim.load())
@@ -412,3 +435,4 @@ if __name__ == "__main__":
         deep_model_goldens(refshim.load())
         deep_bessel_goldens(refshim.load())
         trained_model_goldens(refshim.load())
+        collate_goldens(refshim.load())

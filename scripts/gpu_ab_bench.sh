@@ -5,7 +5,7 @@ OUT=$ROOT/gpurun_out/${1:-abb}; mkdir -p $OUT; shift
 KIND=${KIND:-painn}
 for rep in 1 2; do
 for V in "$@"; do
-  env $V timeout 300 python bench.py --kind $KIND --steps 100 --warmup 10 --no-cpu-baseline --no-md --no-sweep --no-pmc --no-train --no-drop-in --no-painn 2>/dev/null > $OUT/b.json
+  env $V timeout 300 python bench.py --full --kind $KIND --steps 100 --warmup 10 --no-cpu-baseline --no-md --no-sweep --no-pmc --no-train --no-drop-in --no-painn 2>/dev/null > $OUT/b.json
   python - <<PY
 import json
 d=json.load(open("$OUT/b.json"))

@@ -7,7 +7,7 @@ OUT=gpurun_out/${1:-r04dual}; mkdir -p $OUT
 (SPK_FM_NO_DUAL=1 timeout 900 python -m pytest tests/test_gpu_fm.py -q 2>&1 | tail -3) | tee $OUT/pytest_nodual.log
 for k in schnet painn; do for ND in 0 1 0 1; do
   if [ $ND = 0 ]; then unset SPK_FM_NO_DUAL; else export SPK_FM_NO_DUAL=1; fi
-  timeout 200 python bench.py --mode train --kind $k --no-cpu-baseline > $OUT/train_${k}_nd$ND.json 2> $OUT/train_${k}_nd$ND.err
+  timeout 200 python bench.py --full --mode train --kind $k --no-cpu-baseline > $OUT/train_${k}_nd$ND.json 2> $OUT/train_${k}_nd$ND.err
   python - <<PY
 import json
 d = json.loads(open("$OUT/train_${k}_nd$ND.json").read().strip().splitlines()[-1])

@@ -4,7 +4,7 @@ OUT=gpurun_out/${1:-r04z}; mkdir -p $OUT
 (timeout 900 python -m pytest tests/test_gpu_fm.py tests/test_gpu_train.py -q 2>&1 | tail -5) | tee $OUT/pytest.log
 for k in schnet painn; do for NS in 1 0 1 0; do
   if [ $NS = 1 ]; then unset SPK_FM_STREAMS; else export SPK_FM_STREAMS=1; fi
-  timeout 200 python bench.py --mode train --kind $k --no-cpu-baseline > $OUT/train_${k}_ns$NS.json 2> $OUT/train_${k}_ns$NS.err
+  timeout 200 python bench.py --full --mode train --kind $k --no-cpu-baseline > $OUT/train_${k}_ns$NS.json 2> $OUT/train_${k}_ns$NS.err
   python - <<PY
 import json
 d = json.loads(open("$OUT/train_${k}_ns$NS.json").read().strip().splitlines()[-1])

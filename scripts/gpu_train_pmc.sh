@@ -2,7 +2,7 @@
 # round 4: the `--mode train` lines with the HBM traffic of one step from this run's counters
 OUT=gpurun_out/${1:-r04trainpmc}; mkdir -p $OUT
 for k in schnet painn; do
-  timeout 400 python bench.py --mode train --kind $k > $OUT/bench_train_$k.json 2> $OUT/bench_train_$k.err
+  timeout 400 python bench.py --full --mode train --kind $k > $OUT/bench_train_$k.json 2> $OUT/bench_train_$k.err
   python - <<PY
 import json
 d = json.loads(open("$OUT/bench_train_$k.json").read().strip().splitlines()[-1])

@@ -24,15 +24,23 @@ def _systems(seed=0, kinds=("aspirin", "ethanol", "aspirin", "ethanol", "ethanol
     return out
 
 
-@pytest.mark.skipif(not refshim.available(), reason="reference not present")
 def test_collate_mirror_equals_reference_collate():
-    ns = refshim.load()
-    batch = _systems()
-    ref = ns.loader._atoms_collate_fn(batch)
-    got = D.atoms_collate_fn(batch)
-    assert set(ref) == set(got)
-    for k in ref:
-        assert ref[k].dtype == got[k].dtype and torch.equal(ref[k], got[k]), k
+    """Against the reference's own collate of the stored systems (tests/golden/collate_reference.npz, oracle/make_golden.py), and
+    against the live reference on fresh ones where it is present."""
+    from conftest import load_npz
+    z = load_npz("collate_reference.npz")
+    n_sys = 1 + max(int(k[2:k.index("_")]) for k in z if k.startswith("in"))
+    batch = [{k[k.index("_") + 1:]: torch.from_numpy(np.asarray(v)) for k, v in z.items() if k.startswith("in%d_" % s)} for s in range(n_sys)]
+    ref = {k[4:]: torch.from_numpy(np.asarray(v)) for k, v in z.items() if k.startswith("ref_")}
+    checks = [(batch, ref)]
+    if refshim.available():
+        fresh = _systems()
+        checks.append((fresh, refshim.load().loader._atoms_collate_fn(fresh)))
+    for systems, want in checks:
+        got = D.atoms_collate_fn(systems)
+        assert set(want) == set(got)
+        for k in want:
+            assert want[k].dtype == got[k].dtype and torch.equal(want[k], got[k]), k
 
 
 def _brute_plan(ii, jj, off, n):

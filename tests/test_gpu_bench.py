@@ -1,5 +1,6 @@
-"""bench.py's contract on a real device: `--gpus N` starts N ranks by itself, and the default N=1 line carries
-`roofline`, `cpu_baseline`, the `md` (ns/day) half of BASELINE's metric and the padded-neighbour `sweep`."""
+"""bench.py's contract on a real device: `--gpus N` starts N ranks by itself; a plain run prints the headline only and
+`--dump-outputs` writes what its last timed step computed; the `--full` N=1 line carries `roofline`, `cpu_baseline`, the `md`
+(ns/day) half of BASELINE's metric and the padded-neighbour `sweep`."""
 import json
 import os
 import subprocess
@@ -42,7 +43,7 @@ def test_gpus_2_runs_two_ranks():
 
 
 def test_default_line_has_both_halves_of_the_metric():
-    line, detail = _run(["--steps", "10", "--warmup", "3", "--md-steps", "40", "--water-side", "10", "--no-pmc", "--cpu-reps", "2"], with_detail=True)
+    line, detail = _run(["--full", "--steps", "10", "--warmup", "3", "--md-steps", "40", "--water-side", "10", "--no-pmc", "--cpu-reps", "2"], with_detail=True)
     assert line["n_gpus"] == 1 and line["dtype"] == "f32" and line["value"] > 0
     rf = line["roofline"]
     assert rf["bound"] in ("mfma", "hbm") and 0 < rf["frac"] <= 1.0 and rf["peak"] > 0
@@ -64,3 +65,29 @@ def test_default_line_has_both_halves_of_the_metric():
     assert sc["dram_rotating"]["frac_of_measured_copy"] <= 1.05
     # the edge of the molecule regime is a row of the line
     assert {r[1] for r in line["molecule_cliff"]["rows"]} == {21, 29, 42, 60}
+
+
+def test_plain_run_is_the_headline_and_dumps_the_last_step():
+    """Without --full the line is the headline alone (no roofline / CPU baseline / sub-objects), and --dump-outputs writes the
+    energies and forces of the last timed step: those of the oracle for the same seeded weights and batch."""
+    import tempfile
+    import numpy as np
+    from oracle import spk_oracle as O
+    from schnetpack_amd import model as M, synthetic as S
+    out = tempfile.mkdtemp(prefix="spk_dump_")
+    line = _run(["--steps", "4", "--warmup", "2", "--frames", "16", "--dump-outputs", out])
+    assert line["steps"] == 4 and line["warmup"] == 2 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert line["unit"] == "M edge-messages/s" and line["higher_is_better"] is True and line["dtype"] == "f32"
+    for k in ("roofline", "cpu_baseline", "painn", "water", "train", "md", "sweep", "scatter_add", "neighbor_list", "drop_in"):
+        assert line.get(k) is None, k
+    assert sorted(os.listdir(out)) == ["energy.npy", "forces.npy"]
+    energy, forces = np.load(os.path.join(out, "energy.npy")), np.load(os.path.join(out, "forces.npy"))
+    assert energy.dtype == np.float32 and forces.dtype == np.float32
+    torch.manual_seed(0)                        # bench.py's make_model: seeded package initialisation, host copies of the weights
+    m = M.build_model("schnet", 128, 3, 20, 5.0)
+    rep = {k: v.detach().clone() for k, v in m.representation.state_dict().items()}
+    head = {k: v.detach().clone() for k, v in m.output_modules[0].state_dict().items()}
+    ref = O.energy_and_forces("schnet", rep, head, S.molecule_batch("aspirin", 16, seed=0), 3)
+    assert energy.shape == tuple(ref["energy"].shape) and forces.shape == tuple(ref["forces"].shape) == (line["config"]["n_atoms"], 3)
+    assert np.abs(forces - ref["forces"].numpy()).max() / np.abs(ref["forces"].numpy()).max() < 1e-5
+    assert np.abs(energy - ref["energy"].numpy()).max() / np.abs(ref["energy"].numpy()).max() < 1e-5

@@ -62,6 +62,33 @@ def test_bench_books_every_modelled_kernel_with_a_lower_bound():
     assert 0.05 <= B.RAMP_S <= 0.5          # the untimed clock ramp stays a bounded fraction of a second
 
 
+def test_bench_plain_by_default_and_dump_outputs_within_its_limit(tmp_path, monkeypatch):
+    """A plain `bench.py --gpus 1 --steps N --warmup W` measures the headline only (--full is opt-in); --dump-outputs writes one
+    .npy per array in float32 (float64 kept), and an array beyond its share of the 64 MB limit as the same seeded sample of rows."""
+    import numpy as np
+    B = _bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = B.parse()
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        B.parse()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--mode", "md", "--dump-outputs", str(tmp_path)])
+    with pytest.raises(SystemExit):
+        B.parse()
+    monkeypatch.setattr(B, "DUMP_LIMIT", 3 * 4096)
+    big = torch.arange(3000 * 3, dtype=torch.float32).reshape(3000, 3)
+    arrays = {"energy": torch.arange(5, dtype=torch.float64), "forces": big}
+    for d in ("a", "b"):
+        B.dump_outputs(str(tmp_path / d), arrays)
+    e, f = np.load(tmp_path / "a" / "energy.npy"), np.load(tmp_path / "a" / "forces.npy")
+    assert e.dtype == np.float64 and np.array_equal(e, np.arange(5.0))
+    assert f.dtype == np.float32 and f.nbytes <= B.DUMP_LIMIT // 2 and f.shape[1] == 3 and f.shape[0] == (B.DUMP_LIMIT // 2) // 12
+    rows = f[:, 0].astype(np.int64) // 3
+    assert np.all(np.diff(rows) > 0) and np.array_equal(f, big.numpy()[rows])          # whole rows, sorted, unchanged
+    assert np.array_equal(f, np.load(tmp_path / "b" / "forces.npy"))                     # the same sample every time
+
+
 def test_documented_second_order_of_the_filter_node():
     """HISTORY.md 4.12 writes down the first and second derivative of the SchNet filter node (schnet.py:60-62) for the fused training
     node that is not built yet: the formulas, restated in float64, against torch autograd."""
