@@ -222,6 +222,16 @@ int spk_pairwise_bwd_f32(const float* gr, const int64_t* idx_i, const int64_t* i
  * row sum gR[a] = sum_{e in row(a)} (gr[rev[e]] - gr[e]) -- no atomics, deterministic; other lists
  * take the atomic kernel above. */
 int spk_pairwise_bwd_graph_f32(const float* gr, const spk_graph_t* g, float* gR, void* stream);
+/* The virial of the pair vectors (atomistic/response.py:434-464: Strain strains R, offsets and cell by S^T):
+ *   W[m] = dE/dS[m] = sum over the edges e of molecule m of  gr[e] r_e^T    (3 x 3 row-major, gr as the row index; energy units)
+ * with r_e = (R[idx_j[e]] - R[idx_i[e]]) + offsets[e] recomputed in fp32 as spk_pairwise_f32 does; stress = W / V is left to the caller.
+ * W_atom [N, 3, 3] (may be NULL): the same sum over the edges of each centre atom (idx_i); its sum over a molecule's atoms is W[m].
+ * idx_m [N] ascending (as the reference's batches); W [n_mol, 3, 3] is overwritten (molecules without atoms: zero).  offsets may be NULL.
+ * Lists sorted by idx_i use g->rowptr; other lists are put in a stable by-centre order on the device.  No float atomics (the same list
+ * gives the same bits on every call), no host synchronisation.  workspace: spk_edge_virial_workspace_bytes(g, n_mol, W_atom != NULL). */
+int64_t spk_edge_virial_workspace_bytes(const spk_graph_t* g, int64_t n_mol, int32_t with_atom_virial);
+int spk_edge_virial_f32(const float* gr, const float* R, const float* offsets, const spk_graph_t* g, const int64_t* idx_m, int64_t n_mol,
+                        float* W, float* W_atom, void* workspace, void* stream);
 
 /* ------------------------------------------------------------------ transform/neighborlist.py:438-507
  * (TorchNeighborList) and md/neighborlist_md.py:100-159 -- cell-list neighbour list on the device for
@@ -503,6 +513,12 @@ int spk_schnet_potential_forces_f32(const spk_schnet_t* m, const spk_head_t* hea
                                     const float* x0, const float* emb, const int64_t* Z, int32_t n_types, const float* R,
                                     const float* offsets, const int64_t* idx_m, int64_t n_mol, int32_t all_inside, float* x_out,
                                     float* E, float* F, float* pre_h, float* saved, void* stream);
+/* The same, and the backward launch also writes gr = dE/dr [E, 3] of every edge (pairs beyond the cutoff: zero), the input of
+ * spk_edge_virial_f32; E and F are those of spk_schnet_potential_forces_f32 bit for bit. */
+int spk_schnet_potential_forces_gr_f32(const spk_schnet_t* m, const spk_head_t* head, const spk_graph_t* g, const spk_radial_t* rb,
+                                       const float* x0, const float* emb, const int64_t* Z, int32_t n_types, const float* R,
+                                       const float* offsets, const int64_t* idx_m, int64_t n_mol, int32_t all_inside, float* x_out,
+                                       float* E, float* F, float* gr, float* pre_h, float* saved, void* stream);
 
 /* EXPERIMENT (eval only, not on any default path; scripts/tab_filter_experiment.py): continuous-filter convolution
  * (representation/schnet.py:60-67) with the filter W_l(d) f_c(d) read from a cubic-Hermite table instead of the filter network:
@@ -644,6 +660,12 @@ int spk_painn_potential_forces_f32(const spk_painn_t* m, const spk_head_t* head,
                                    const float* q0, const float* emb, const int64_t* Z, int32_t n_types, const float* R,
                                    const float* offsets, const int64_t* idx_m, int64_t n_mol, int32_t all_inside, float* q_out,
                                    float* mu_out, float* E, float* F, float* pre_h, float* saved, float* scratch, void* stream);
+/* The same two launches with the backward writing gr = dE/dr [E, 3] of every edge INSTEAD of the forces (the molecule-resident
+ * backward writes one or the other): forces = -spk_pairwise_bwd_graph_f32(gr), virial = spk_edge_virial_f32(gr, ...). */
+int spk_painn_potential_gr_f32(const spk_painn_t* m, const spk_head_t* head, const spk_graph_t* g, const spk_radial_t* rb,
+                               const float* q0, const float* emb, const int64_t* Z, int32_t n_types, const float* R,
+                               const float* offsets, const int64_t* idx_m, int64_t n_mol, int32_t all_inside, float* q_out,
+                               float* mu_out, float* E, float* gr, float* pre_h, float* saved, float* scratch, void* stream);
 
 
 /* ------------------------------------------------------------------ deployment runtime
@@ -684,6 +706,18 @@ int spk_potential_compute_cell(spk_potential_t* p, int64_t n_atoms, const int64_
                                int64_t n_mol, const int64_t* host_idx_m, const float* host_cell,
                                const uint8_t* host_pbc, float skin, float* host_energy, float* host_forces,
                                int64_t* host_stats);
+/* The same calls with the virial W = dE/dstrain (atomistic/response.py:434-464; energy units, stress = W / V) from the same
+ * per-edge gradient: host_virial [n_mol,3,3] (gradient as the row index, as spk_edge_virial_f32), host_atom_virial [n_atoms,3,3] or
+ * NULL (by centre atom, in the caller's atom order; it sums to host_virial over each molecule's atoms).  Pairs of a skin list beyond
+ * the cutoff contribute zero.  A LAMMPS pair style wants -W as virial[6] = (xx, yy, zz, xy, xz, yz). */
+int spk_potential_compute_virial(spk_potential_t* p, int64_t n_atoms, const int64_t* host_z, const float* host_R,
+                                 int64_t n_edges, const int64_t* host_idx_i, const int64_t* host_idx_j,
+                                 const float* host_offsets, int64_t n_mol, const int64_t* host_idx_m,
+                                 float* host_energy, float* host_forces, float* host_virial, float* host_atom_virial);
+int spk_potential_compute_cell_virial(spk_potential_t* p, int64_t n_atoms, const int64_t* host_z, const float* host_R,
+                                      int64_t n_mol, const int64_t* host_idx_m, const float* host_cell,
+                                      const uint8_t* host_pbc, float skin, float* host_energy, float* host_forces,
+                                      float* host_virial, float* host_atom_virial, int64_t* host_stats);
 
 /* ------------------------------------------------------------------ small helpers
  * out[n, :] = table[z[n], :]  (nn.Embedding lookup, schnet.py:161 / painn.py:239) */

@@ -139,6 +139,8 @@ _PROTOS = {
     "spk_segment_rowptr_i32": (ctypes.c_int, [c_f, c_i64, c_i64, c_f, c_f, c_f]),
     "spk_index_range_check": (ctypes.c_int, [c_f, c_i64, c_i64, c_f, c_f]),
     "spk_pairwise_bwd_graph_f32": (ctypes.c_int, [c_f, P(GraphT), c_f, c_f]),
+    "spk_edge_virial_workspace_bytes": (c_i64, [P(GraphT), c_i64, c_i32]),
+    "spk_edge_virial_f32": (ctypes.c_int, [c_f, c_f, c_f, P(GraphT), c_f, c_i64, c_f, c_f, c_f, c_f]),
     "spk_radial_cutoff_f32": (ctypes.c_int, [c_f, c_i64, P(RadialT), c_f, c_f, c_f]),
     "spk_radial_cutoff_bwd_f32": (ctypes.c_int, [c_f, c_i64, P(RadialT), c_f, c_f, c_f, c_f]),
     "spk_edge_norm_f32": (ctypes.c_int, [c_f, c_i64, c_f, c_f, c_f]),
@@ -189,9 +191,11 @@ _PROTOS = {
     "spk_schnet_potential_supported": (ctypes.c_int, [P(SchnetT), P(HeadT), P(GraphT), P(RadialT)]),
     "spk_schnet_potential_forward_f32": (ctypes.c_int, [P(SchnetT), P(HeadT), P(GraphT), P(RadialT), c_f, c_f, c_f, c_f, c_i64, c_f, c_f, c_f, c_f, c_f]),
     "spk_schnet_potential_forces_f32": (ctypes.c_int, [P(SchnetT), P(HeadT), P(GraphT), P(RadialT), c_f, c_f, c_f, c_i32, c_f, c_f, c_f, c_i64, c_i32, c_f, c_f, c_f, c_f, c_f, c_f]),
+    "spk_schnet_potential_forces_gr_f32": (ctypes.c_int, [P(SchnetT), P(HeadT), P(GraphT), P(RadialT), c_f, c_f, c_f, c_i32, c_f, c_f, c_f, c_i64, c_i32, c_f, c_f, c_f, c_f, c_f, c_f, c_f]),
     "spk_schnet_potential_backward_f32": (ctypes.c_int, [P(SchnetT), P(HeadT), P(GraphT), P(RadialT), c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f]),
     "spk_painn_potential_supported": (ctypes.c_int, [P(PainnT), P(HeadT), P(GraphT), P(RadialT)]),
     "spk_painn_potential_forces_f32": (ctypes.c_int, [P(PainnT), P(HeadT), P(GraphT), P(RadialT), c_f, c_f, c_f, c_i32, c_f, c_f, c_f, c_i64, c_i32, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f]),
+    "spk_painn_potential_gr_f32": (ctypes.c_int, [P(PainnT), P(HeadT), P(GraphT), P(RadialT), c_f, c_f, c_f, c_i32, c_f, c_f, c_f, c_i64, c_i32, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f]),
     "spk_painn_message_fwd_f32": (ctypes.c_int, [P(GraphT), P(RadialT), c_f, c_f, c_f, c_f, c_f, c_f, c_i32, c_f, c_f, c_f]),
     "spk_painn_message_bwd_f32": (ctypes.c_int, [P(GraphT), P(RadialT), c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i32, c_f, c_f, c_f, c_f]),
     "spk_painn_set_tile": (None, [c_i32]),
@@ -228,6 +232,12 @@ _PROTOS = {
     "spk_potential_compute_cell": (ctypes.c_int, [ctypes.c_void_p, c_i64, P(ctypes.c_int64), P(ctypes.c_float), c_i64, P(ctypes.c_int64),
                                                   P(ctypes.c_float), P(ctypes.c_uint8), ctypes.c_float, P(ctypes.c_float),
                                                   P(ctypes.c_float), P(ctypes.c_int64)]),
+    "spk_potential_compute_virial": (ctypes.c_int, [ctypes.c_void_p, c_i64, P(ctypes.c_int64), P(ctypes.c_float), c_i64, P(ctypes.c_int64),
+                                                    P(ctypes.c_int64), P(ctypes.c_float), c_i64, P(ctypes.c_int64), P(ctypes.c_float),
+                                                    P(ctypes.c_float), P(ctypes.c_float), P(ctypes.c_float)]),
+    "spk_potential_compute_cell_virial": (ctypes.c_int, [ctypes.c_void_p, c_i64, P(ctypes.c_int64), P(ctypes.c_float), c_i64, P(ctypes.c_int64),
+                                                         P(ctypes.c_float), P(ctypes.c_uint8), ctypes.c_float, P(ctypes.c_float),
+                                                         P(ctypes.c_float), P(ctypes.c_float), P(ctypes.c_float), P(ctypes.c_int64)]),
 }
 
 _lib = None

@@ -1,6 +1,6 @@
 """Mirrors of the reference *callers* either side of the hot path, so that a complete force call can be
-assembled (and scripted) without the reference package: ``PairwiseDistances`` (atomistic/distances.py:9-26),
-``Atomwise`` (atomistic/atomwise.py:14-88) and ``Forces`` (atomistic/response.py:18-92).  In an integration the
+assembled (and scripted) without the reference package: ``Strain`` (atomistic/response.py:434-464), ``PairwiseDistances``
+(atomistic/distances.py:9-26), ``Atomwise`` (atomistic/atomwise.py:14-88) and ``Forces`` (atomistic/response.py:18-92).  In an integration the
 reference's own modules run unchanged on top of the HIP classes (tests/test_gpu_reference_callers.py) -- they only see
 ``schnetpack.nn.scatter_add`` / ``Dense`` / the representation classes; ``install(fused_head=True)`` swaps in this
 ``Atomwise`` for its one-kernel energy head.
@@ -17,7 +17,27 @@ from .nn import Dense, build_mlp, scatter_add
 from .nn.base import activation_id
 from .nn.fallback import note_fallback, use_aten
 
-__all__ = ["PairwiseDistances", "Atomwise", "Forces"]
+__all__ = ["Strain", "PairwiseDistances", "Atomwise", "Forces"]
+
+
+class Strain(nn.Module):
+    """Zero strain S [n_mol, 3, 3] (requires grad) applied to positions, offsets and cell as x (1 + S^T), so that ``Forces(calc_stress=True)``
+    can differentiate the energy w.r.t. it.  Module by module this is the reference's formula on any device and dtype; the standard
+    potential with stress (``model.classify_potential`` == 3) does not run it: its operator returns dE/dS directly."""
+
+    def forward(self, inputs: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+        strain = torch.zeros_like(inputs[properties.cell])
+        strain.requires_grad_()
+        inputs[properties.strain] = strain
+        strain = strain.transpose(1, 2)
+        inputs[properties.cell] = inputs[properties.cell] + torch.matmul(inputs[properties.cell], strain)
+        idx_m = inputs[properties.idx_m]
+        strain_i = strain[idx_m]
+        inputs[properties.R] = inputs[properties.R] + torch.matmul(inputs[properties.R][:, None, :], strain_i).squeeze(1)
+        idx_i = inputs[properties.idx_i]
+        strain_ij = strain_i[idx_i]
+        inputs[properties.offsets] = inputs[properties.offsets] + torch.matmul(inputs[properties.offsets][:, None, :], strain_ij).squeeze(1)
+        return inputs
 
 
 class PairwiseDistances(nn.Module):

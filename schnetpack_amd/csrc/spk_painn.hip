@@ -1791,18 +1791,17 @@ extern "C" int spk_painn_potential_supported(const spk_painn_t* m, const spk_hea
 // embedding table `emb` [n_types, F] are looked up by Z inside the forward launch).  all_inside != 0: the caller guarantees that every
 // molecule's atoms lie inside ONE group of the plan and that every molecule has an atom -- the energies are then stored, not
 // accumulated, and E needs no clearing launch.  scratch: spk_painn_scratch_floats() floats.
-extern "C" int spk_painn_potential_forces_f32(const spk_painn_t* m, const spk_head_t* head, const spk_graph_t* g, const spk_radial_t* rb,
+static int painn_potential_forces(const spk_painn_t* m, const spk_head_t* head, const spk_graph_t* g, const spk_radial_t* rb,
                                               const float* q0, const float* emb, const int64_t* Z, int32_t n_types, const float* R,
                                               const float* offsets, const int64_t* idx_m, int64_t n_mol, int32_t all_inside, float* q_out,
-                                              float* mu_out, float* E, float* F, float* pre_h, float* saved, float* scratch, void* stream_) {
+                                              float* mu_out, float* E, float* F, float* gr, float* pre_h, float* saved, float* scratch, const char* who, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  const char* who = "spk_painn_potential_forces_f32";
   SPK_CHECK_ARG(painn_potential_ok(m, head, g, rb), "%s: model / list not covered by the fused potential (see spk_painn_potential_supported)", who);
   SPK_CHECK_ARG(n_mol >= 0 && (n_mol == 0 || E), "%s: null energy buffer", who);
   SPK_CHECK_ARG(q0 || (emb && Z && n_types > 0), "%s: neither features nor an embedding table", who);
   if (n_mol > 0 && !all_inside) { int zr = spk_zero_async(E, (size_t)n_mol * sizeof(float), stream); if (zr) return zr; }
   if (g->n_atoms == 0) return SPK_OK;
-  SPK_CHECK_ARG(R && idx_m && q_out && mu_out && F && pre_h && saved && scratch, "%s: null buffer", who);
+  SPK_CHECK_ARG(R && idx_m && q_out && mu_out && (F || gr) && pre_h && saved && scratch, "%s: null buffer", who);
   PmHeadDev h;
   h.w1 = head->w1; h.w1t = head->w1t; h.b1 = head->b1; h.w2 = head->w2; h.b2 = head->b2; h.H = head->n_hidden; h.act = head->act;
   h.idx_m = idx_m; h.E = E; h.pre_h = pre_h; h.direct_store = all_inside ? 1 : 0;
@@ -1814,5 +1813,26 @@ extern "C" int spk_painn_potential_forces_f32(const spk_painn_t* m, const spk_he
   float* rij = scratch + 6 * nf;
   float* gq = scratch + 7 * nf;
   SPK_TRY(spk_painn_mol_forward_ex(m, g, rb, ptab, q0, nullptr, R, offsets, q0 ? nullptr : emb, Z, n_types, &h, rij, gq, q_out, mu_out, saved, stream));
-  return spk_painn_mol_backward_ex(m, g, rb, ptab, gq, nullptr, rij, saved, scratch, nullptr, nullptr, F, stream);
+  return spk_painn_mol_backward_ex(m, g, rb, ptab, gq, nullptr, rij, saved, scratch, gr, nullptr, F, stream);
+}
+
+extern "C" int spk_painn_potential_forces_f32(const spk_painn_t* m, const spk_head_t* head, const spk_graph_t* g, const spk_radial_t* rb,
+                                              const float* q0, const float* emb, const int64_t* Z, int32_t n_types, const float* R,
+                                              const float* offsets, const int64_t* idx_m, int64_t n_mol, int32_t all_inside, float* q_out,
+                                              float* mu_out, float* E, float* F, float* pre_h, float* saved, float* scratch, void* stream_) {
+  SPK_CHECK_ARG(F, "spk_painn_potential_forces_f32: null forces");
+  return painn_potential_forces(m, head, g, rb, q0, emb, Z, n_types, R, offsets, idx_m, n_mol, all_inside, q_out, mu_out, E, F, nullptr, pre_h, saved,
+                                scratch, "spk_painn_potential_forces_f32", stream_);
+}
+
+// The same two launches with the backward writing dE/dr [E, 3] of every edge instead of the forces (the molecule-resident backward writes
+// one or the other): the caller forms the forces with spk_pairwise_bwd_graph_f32 and the virial with spk_edge_virial_f32.
+extern "C" int spk_painn_potential_gr_f32(const spk_painn_t* m, const spk_head_t* head, const spk_graph_t* g, const spk_radial_t* rb,
+                                          const float* q0, const float* emb, const int64_t* Z, int32_t n_types, const float* R,
+                                          const float* offsets, const int64_t* idx_m, int64_t n_mol, int32_t all_inside, float* q_out,
+                                          float* mu_out, float* E, float* gr, float* pre_h, float* saved, float* scratch, void* stream_) {
+  const char* who = "spk_painn_potential_gr_f32";
+  SPK_CHECK_ARG(g && (g->n_edges == 0 || gr), "%s: null edge gradient", who);
+  return painn_potential_forces(m, head, g, rb, q0, emb, Z, n_types, R, offsets, idx_m, n_mol, all_inside, q_out, mu_out, E, nullptr, gr, pre_h, saved,
+                                scratch, who, stream_);
 }

@@ -60,7 +60,7 @@ struct spk_potential {
   spk_radial_t rb;
   // per-call device buffers
   DevBuf z, R, ii, jj, off, idxm, rij, rowptr, rev, half, scr, x0, xo, mu, saved, scratch, pre, gx, gE, gr, gR, E, flags, tmp,
-      cell, pbc, nblws, nblrow, shifts;
+      cell, pbc, nblws, nblrow, shifts, W, Wa, vws;
   // current list
   spk_graph_t g;
   bool cell_list = false;
@@ -276,8 +276,10 @@ int plan_list(spk_potential* p, int64_t N, int64_t E, bool want_filter) {
 }
 
 // inputs are on the device (z, R, ii, jj, off, idxm); runs the model and downloads energy / forces
+// host_virial [M, 3, 3] / host_atom_virial [N, 3, 3] (either may be NULL): W = dE/dstrain from the same dE/dr (spk_edge_virial_f32)
 int run_model(spk_potential* p, int64_t N, int64_t E, int64_t M, bool new_list, bool want_filter, bool have_off,
-              const int64_t* host_z, const int64_t* host_idx_m, float* host_energy, float* host_forces) {
+              const int64_t* host_z, const int64_t* host_idx_m, float* host_energy, float* host_forces, float* host_virial = nullptr,
+              float* host_atom_virial = nullptr) {
   const FileHeader& h = p->h;
   hipStream_t s = p->stream;
   const int F = h.F, H = h.head_hidden;
@@ -332,6 +334,18 @@ int run_model(spk_potential* p, int64_t N, int64_t E, int64_t M, bool new_list, 
                                 p->gr.as<float>(), nullptr, s);
   if (rc) return rc;
   if ((rc = spk_pairwise_bwd_graph_f32(p->gr.as<float>(), g, p->gR.as<float>(), s))) return rc;
+  if (host_virial || host_atom_virial) {
+    const int64_t vb = spk_edge_virial_workspace_bytes(g, M, host_atom_virial ? 1 : 0);
+    SPK_CHECK_ARG(vb >= 0, "spk_potential: bad list for the virial");
+    if ((rc = p->W.ensure((size_t)M * 36))) return rc;
+    if (host_atom_virial && (rc = p->Wa.ensure((size_t)N * 36))) return rc;
+    if ((rc = p->vws.ensure((size_t)std::max<int64_t>(vb, 1)))) return rc;
+    if ((rc = spk_edge_virial_f32(p->gr.as<float>(), p->R.as<float>(), have_off ? p->off.as<float>() : nullptr, g, p->idxm.as<int64_t>(), M,
+                                  p->W.as<float>(), host_atom_virial ? p->Wa.as<float>() : nullptr, p->vws.p, s)))
+      return rc;
+    if (host_virial) SPK_HIP_TRY(hipMemcpyAsync(host_virial, p->W.p, (size_t)M * 36, hipMemcpyDeviceToHost, s));
+    if (host_atom_virial) SPK_HIP_TRY(hipMemcpyAsync(host_atom_virial, p->Wa.p, (size_t)N * 36, hipMemcpyDeviceToHost, s));
+  }
   p->hE.resize((size_t)M);
   p->hF.resize((size_t)N * 3);
   SPK_HIP_TRY(hipMemcpyAsync(p->hE.data(), p->E.p, (size_t)M * 4, hipMemcpyDeviceToHost, s));
@@ -414,7 +428,7 @@ extern "C" void spk_potential_free(spk_potential_t* p) {
   if (!p) return;
   if (p->stream) (void)hipStreamSynchronize(p->stream);
   DevBuf* bufs[] = {&p->z, &p->R, &p->ii, &p->jj, &p->off, &p->idxm, &p->rij, &p->rowptr, &p->rev, &p->half, &p->scr, &p->x0, &p->xo, &p->mu,
-                    &p->saved, &p->scratch, &p->pre, &p->gx, &p->gE, &p->gr, &p->gR, &p->E, &p->flags, &p->tmp, &p->cell, &p->pbc, &p->nblws,
+                    &p->saved, &p->scratch, &p->pre, &p->gx, &p->gE, &p->gr, &p->gR, &p->E, &p->flags, &p->tmp, &p->cell, &p->pbc, &p->W, &p->Wa, &p->vws, &p->nblws,
                     &p->nblrow, &p->shifts};
   for (DevBuf* b : bufs) b->release();
   if (p->wpack) (void)hipFree(p->wpack);
@@ -433,9 +447,9 @@ extern "C" int spk_potential_info(const spk_potential_t* p, int32_t* info, float
   return SPK_OK;
 }
 
-extern "C" int spk_potential_compute(spk_potential_t* p, int64_t N, const int64_t* z, const float* R, int64_t E, const int64_t* idx_i,
-                                     const int64_t* idx_j, const float* offsets, int64_t M, const int64_t* idx_m, float* energy,
-                                     float* forces) {
+static int potential_compute(spk_potential_t* p, int64_t N, const int64_t* z, const float* R, int64_t E, const int64_t* idx_i,
+                             const int64_t* idx_j, const float* offsets, int64_t M, const int64_t* idx_m, float* energy, float* forces,
+                             float* virial, float* atom_virial) {
   int rc = check_atoms(p, N, z, R, M, idx_m, "spk_potential_compute");
   if (rc) return rc;
   SPK_CHECK_ARG(E >= 0 && E < (1LL << 31) && (E == 0 || (idx_i && idx_j)), "spk_potential_compute: bad neighbour list (n_edges = %lld)", (long long)E);
@@ -476,12 +490,25 @@ extern "C" int spk_potential_compute(spk_potential_t* p, int64_t N, const int64_
     if (offsets) SPK_HIP_TRY(hipMemcpyAsync(p->off.p, offsets, (size_t)E * 12, hipMemcpyHostToDevice, s));
   }
   p->cell_list = false;
-  return run_model(p, N, E, M, true, false, offsets != nullptr, z, idx_m, energy, forces);
+  return run_model(p, N, E, M, true, false, offsets != nullptr, z, idx_m, energy, forces, virial, atom_virial);
 }
 
-extern "C" int spk_potential_compute_cell(spk_potential_t* p, int64_t N, const int64_t* z, const float* R, int64_t M, const int64_t* idx_m,
-                                          const float* cell, const uint8_t* pbc, float skin, float* energy, float* forces,
-                                          int64_t* stats) {
+extern "C" int spk_potential_compute(spk_potential_t* p, int64_t N, const int64_t* z, const float* R, int64_t E, const int64_t* idx_i,
+                                     const int64_t* idx_j, const float* offsets, int64_t M, const int64_t* idx_m, float* energy,
+                                     float* forces) {
+  return potential_compute(p, N, z, R, E, idx_i, idx_j, offsets, M, idx_m, energy, forces, nullptr, nullptr);
+}
+
+extern "C" int spk_potential_compute_virial(spk_potential_t* p, int64_t N, const int64_t* z, const float* R, int64_t E, const int64_t* idx_i,
+                                            const int64_t* idx_j, const float* offsets, int64_t M, const int64_t* idx_m, float* energy,
+                                            float* forces, float* virial, float* atom_virial) {
+  SPK_CHECK_ARG(virial, "spk_potential_compute_virial: null virial");
+  return potential_compute(p, N, z, R, E, idx_i, idx_j, offsets, M, idx_m, energy, forces, virial, atom_virial);
+}
+
+static int potential_compute_cell(spk_potential_t* p, int64_t N, const int64_t* z, const float* R, int64_t M, const int64_t* idx_m,
+                                  const float* cell, const uint8_t* pbc, float skin, float* energy, float* forces, float* virial,
+                                  float* atom_virial, int64_t* stats) {
   int rc = check_atoms(p, N, z, R, M, idx_m, "spk_potential_compute_cell");
   if (rc) return rc;
   SPK_CHECK_ARG(energy && forces, "spk_potential_compute_cell: null output");
@@ -538,9 +565,22 @@ extern "C" int spk_potential_compute_cell(spk_potential_t* p, int64_t N, const i
     if (cell) p->cell_ref.assign(cell, cell + 9 * M); else p->cell_ref.clear();
     if (pbc) p->pbc_ref.assign(pbc, pbc + 3 * M); else p->pbc_ref.clear();
   }
-  rc = run_model(p, N, E, M, rebuild, skin > 0.f, true, z, idx_m, energy, forces);
+  rc = run_model(p, N, E, M, rebuild, skin > 0.f, true, z, idx_m, energy, forces, virial, atom_virial);
   if (rc) { p->cell_list = false; return rc; }
   p->cell_list = true; p->list_atoms = N; p->list_mol = M; p->list_skin = skin;
   if (stats) { stats[0] = E; stats[1] = rebuild ? 1 : 0; }
   return SPK_OK;
+}
+
+extern "C" int spk_potential_compute_cell(spk_potential_t* p, int64_t N, const int64_t* z, const float* R, int64_t M, const int64_t* idx_m,
+                                          const float* cell, const uint8_t* pbc, float skin, float* energy, float* forces,
+                                          int64_t* stats) {
+  return potential_compute_cell(p, N, z, R, M, idx_m, cell, pbc, skin, energy, forces, nullptr, nullptr, stats);
+}
+
+extern "C" int spk_potential_compute_cell_virial(spk_potential_t* p, int64_t N, const int64_t* z, const float* R, int64_t M, const int64_t* idx_m,
+                                                 const float* cell, const uint8_t* pbc, float skin, float* energy, float* forces, float* virial,
+                                                 float* atom_virial, int64_t* stats) {
+  SPK_CHECK_ARG(virial, "spk_potential_compute_cell_virial: null virial");
+  return potential_compute_cell(p, N, z, R, M, idx_m, cell, pbc, skin, energy, forces, virial, atom_virial, stats);
 }

@@ -345,12 +345,11 @@ extern "C" int spk_schnet_potential_backward_f32(const spk_schnet_t* m, const sp
 // embedding table `emb` [n_types, F] are looked up by Z inside the forward launch), dL/dE is 1 (forces of the summed energy), the
 // backward writes -dE/dR.  all_inside != 0: the caller guarantees that every molecule's atoms lie inside ONE group of the plan and
 // that every molecule has an atom -- the energies are then stored, not accumulated, and E needs no clearing launch.
-extern "C" int spk_schnet_potential_forces_f32(const spk_schnet_t* m, const spk_head_t* head, const spk_graph_t* g, const spk_radial_t* rb,
+static int schnet_potential_forces(const spk_schnet_t* m, const spk_head_t* head, const spk_graph_t* g, const spk_radial_t* rb,
                                                const float* x0, const float* emb, const int64_t* Z, int32_t n_types, const float* R,
                                                const float* offsets, const int64_t* idx_m, int64_t n_mol, int32_t all_inside, float* x_out, float* E,
-                                               float* F, float* pre_h, float* saved, void* stream_) {
+                                               float* F, float* gr, float* pre_h, float* saved, const char* who, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  const char* who = "spk_schnet_potential_forces_f32";
   SPK_TRY(check_model(m, who));
   SPK_CHECK_ARG(potential_ok(m, head, g, rb), "%s: model / list not covered by the fused potential (see spk_schnet_potential_supported)", who);
   SPK_CHECK_ARG(n_mol >= 0 && (n_mol == 0 || E), "%s: null energy buffer", who);
@@ -364,5 +363,25 @@ extern "C" int spk_schnet_potential_forces_f32(const spk_schnet_t* m, const spk_
   const SpkPackTable ptab = schnet_pack_table(m);
   const int64_t gsz = spk_cfconv_gsave_floats(g, rb, m->n_filters);
   SPK_TRY(spk_schnet_mol_forward_ex(m, g, rb, ptab, x0, nullptr, R, offsets, &h, x_out, saved, gsz, stream, x0 ? nullptr : emb, Z, n_types));
-  return spk_schnet_mol_backward_ex(m, g, rb, ptab, nullptr, nullptr, R, offsets, &h, saved, gsz, nullptr, F, nullptr, stream);
+  return spk_schnet_mol_backward_ex(m, g, rb, ptab, nullptr, nullptr, R, offsets, &h, saved, gsz, gr, F, nullptr, stream);
+}
+
+extern "C" int spk_schnet_potential_forces_f32(const spk_schnet_t* m, const spk_head_t* head, const spk_graph_t* g, const spk_radial_t* rb,
+                                               const float* x0, const float* emb, const int64_t* Z, int32_t n_types, const float* R,
+                                               const float* offsets, const int64_t* idx_m, int64_t n_mol, int32_t all_inside, float* x_out, float* E,
+                                               float* F, float* pre_h, float* saved, void* stream_) {
+  return schnet_potential_forces(m, head, g, rb, x0, emb, Z, n_types, R, offsets, idx_m, n_mol, all_inside, x_out, E, F, nullptr, pre_h, saved,
+                                 "spk_schnet_potential_forces_f32", stream_);
+}
+
+// The same, and the backward launch also writes dE/dr [E, 3] of every edge (the input of the virial, spk_edge_virial_f32); the forces are
+// those of spk_schnet_potential_forces_f32 bit for bit.
+extern "C" int spk_schnet_potential_forces_gr_f32(const spk_schnet_t* m, const spk_head_t* head, const spk_graph_t* g, const spk_radial_t* rb,
+                                                  const float* x0, const float* emb, const int64_t* Z, int32_t n_types, const float* R,
+                                                  const float* offsets, const int64_t* idx_m, int64_t n_mol, int32_t all_inside, float* x_out,
+                                                  float* E, float* F, float* gr, float* pre_h, float* saved, void* stream_) {
+  const char* who = "spk_schnet_potential_forces_gr_f32";
+  SPK_CHECK_ARG(g && (g->n_edges == 0 || gr), "%s: null edge gradient", who);
+  return schnet_potential_forces(m, head, g, rb, x0, emb, Z, n_types, R, offsets, idx_m, n_mol, all_inside, x_out, E, F, gr, pre_h, saved, who,
+                                 stream_);
 }

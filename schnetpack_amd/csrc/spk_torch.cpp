@@ -964,6 +964,126 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> painn_potential_forces_raw(const c10:
   return {std::get<0>(hdf), at::neg(gR), std::get<0>(fw), std::get<1>(fw)};
 }
 
+// Virial W [n_mol, 3, 3] = sum over each molecule's edges of dE/dr_e r_e^T from the per-edge gradient (spk_edge_virial_f32: row sums over the
+// plan's CSR, or a by-centre order built on the device for unsorted lists; no atomics, no host synchronisation)
+Tensor edge_virial_raw(const Tensor& gr, const Tensor& R, const Tensor& off, const Plan& plan, const Tensor& idx_m, int64_t n_mol) {
+  spk_graph_t g = plan.graph();
+  Tensor W = at::empty({n_mol, 3, 3}, R.options());
+  const int64_t bytes = spk_edge_virial_workspace_bytes(&g, n_mol, 0);
+  TORCH_CHECK(bytes >= 0, "edge virial: bad list");
+  Tensor ws = at::empty({std::max<int64_t>(1, bytes)}, R.options().dtype(at::kByte));
+  check(spk_edge_virial_f32(gr.numel() ? fp(gr) : nullptr, fp(R), fp(off), &g, idx_m.data_ptr<int64_t>(), n_mol, fpm(W), nullptr, ws.data_ptr(),
+                            stream_of(R)));
+  return W;
+}
+
+// Energies, forces AND the virial W = dE/dS of the strain (Strain -> ... -> Forces(calc_stress=True), atomistic/response.py:434-464) for eval:
+// (E, F = -dE/dR, W [n_mol, 3, 3], scalar_representation), no autograd node.  E and F are those of schnet_potential_forces bit for bit: the same
+// two launches (the backward also writes dE/dr of every edge) or the same three stages (whose dE/dr is kept), plus the virial launches.
+std::tuple<Tensor, Tensor, Tensor, Tensor> schnet_potential_stress_raw(const c10::optional<Tensor>& x0_in, const c10::optional<Tensor>& emb_in, const Tensor& Z_in,
+                                                                       const Tensor& R_in, const c10::optional<Tensor>& offsets_in, const Tensor& idx_i,
+                                                                       const Tensor& idx_j, const Tensor& idx_m_in, int64_t n_mol, at::TensorList ws,
+                                                                       at::TensorList head, int64_t n_filters, int64_t rbf_kind, const Tensor& p0,
+                                                                       const c10::optional<Tensor>& p1, double cutoff, int64_t head_act) {
+  const char* who = "schnet_potential_stress";
+  const bool has_x0 = x0_in.has_value() && x0_in->defined();
+  TORCH_CHECK(has_x0 || (emb_in.has_value() && emb_in->defined()), who, ": neither features nor an embedding table");
+  Tensor R = f32(R_in.detach(), who);
+  Tensor off = opt_f32(offsets_in, who);
+  Tensor idx_m = i64(idx_m_in, who), Z = i64(Z_in, who);
+  Tensor x0 = has_x0 ? f32(x0_in->detach(), who) : Tensor();
+  Tensor emb = has_x0 ? Tensor() : f32(emb_in->detach(), who);
+  const int64_t N = R.size(0), F = has_x0 ? x0.size(1) : emb.size(1);
+  c10::DeviceGuard guard(R.device());
+  c10::optional<Tensor> off_d = off.defined() ? c10::optional<Tensor>(off) : c10::optional<Tensor>();
+  PotentialCall c = potential_setup(R, off_d, idx_i, idx_j, N, F, ws, head, n_filters, rbf_kind, p0, p1, cutoff, head_act);
+  if (c.fused) {
+    const bool inside = molecules_inside_groups(*c.plan, idx_m, n_mol);
+    Tensor x = at::empty({N, F}, R.options()), E = at::empty({n_mol}, R.options()), Fo = at::empty({N, 3}, R.options());
+    Tensor gr = at::empty({c.plan->n_edges, 3}, R.options());
+    Tensor pre_h = at::empty({N, (int64_t)c.head.n_hidden}, R.options());
+    Tensor saved = at::empty({std::max<int64_t>(1, spk_schnet_saved_floats_graph(&c.m, &c.g, &c.rb))}, R.options());
+    check(spk_schnet_potential_forces_gr_f32(&c.m, &c.head, &c.g, &c.rb, fp(x0), fp(emb), Z.data_ptr<int64_t>(), emb.defined() ? (int32_t)emb.size(0) : 0,
+                                             fp(R), fp(off), idx_m.data_ptr<int64_t>(), n_mol, inside ? 1 : 0, fpm(x), fpm(E), fpm(Fo), fpm(gr), fpm(pre_h),
+                                             fpm(saved), stream_of(R)));
+    return {E, Fo, edge_virial_raw(gr, R, off, *c.plan, idx_m, n_mol), x};
+  }
+  if (!has_x0) x0 = emb.index_select(0, Z);
+  auto fw = schnet_potential_forward_raw(x0, R, off_d, idx_i, idx_j, idx_m, n_mol, ws, head, n_filters, rbf_kind, p0, p1, cutoff, head_act);
+  // the three-stage branch of schnet_potential_backward_raw with dL/dE = 1, keeping the per-edge gradient
+  Tensor r = pairwise_raw(R, idx_i, idx_j, off_d);
+  Tensor gxh = atomwise_backward_raw(at::ones({n_mol}, R.options()), Tensor(), std::get<3>(fw), head[0], head[2], idx_m, n_mol, head_act);
+  Tensor scratch = at::empty({std::max<int64_t>(1, spk_schnet_scratch_floats(&c.m, N))}, R.options());
+  auto res = schnet_backward_raw(gxh, r, std::get<2>(fw), scratch, *c.plan, ws, F, n_filters, rbf_kind, p0, p1, cutoff, true, false);
+  Tensor gr = std::get<0>(res);
+  Tensor gR = pairwise_bwd_raw(gr, idx_i, idx_j, N);
+  return {std::get<0>(fw), at::neg(gR), edge_virial_raw(gr, R, off, *c.plan, idx_m, n_mol), std::get<1>(fw)};
+}
+
+// The same for PaiNN: (E, F, W [n_mol, 3, 3], scalar_representation, vector_representation).  Batches of small molecules: the two launches
+// with the backward writing dE/dr of every edge (it writes that or the forces), the forces then from the deterministic row sum of
+// spk_pairwise_bwd_graph_f32 (equal to the stress-free call's to float round-off, not bit for bit); other lists: the three stages of
+// painn_potential_forces (bit for bit) with their dE/dr kept.
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> painn_potential_stress_raw(const c10::optional<Tensor>& q0_in, const c10::optional<Tensor>& emb_in,
+                                                                              const Tensor& Z_in, const Tensor& R_in, const c10::optional<Tensor>& offsets_in,
+                                                                              const Tensor& idx_i, const Tensor& idx_j, const Tensor& idx_m_in, int64_t n_mol,
+                                                                              at::TensorList ws, at::TensorList head, bool shared_filters, double eps,
+                                                                              int64_t rbf_kind, const Tensor& p0_in, const c10::optional<Tensor>& p1_in,
+                                                                              double cutoff, int64_t head_act) {
+  const char* who = "painn_potential_stress";
+  const bool has_q0 = q0_in.has_value() && q0_in->defined();
+  TORCH_CHECK(has_q0 || (emb_in.has_value() && emb_in->defined()), who, ": neither features nor an embedding table");
+  TORCH_CHECK(head.size() == 4, who, ": head = [outnet.0.weight, outnet.0.bias, outnet.1.weight, outnet.1.bias]");
+  Tensor R = f32(R_in.detach(), who);
+  Tensor off = opt_f32(offsets_in, who);
+  Tensor idx_m = i64(idx_m_in, who), Z = i64(Z_in, who);
+  Tensor q0 = has_q0 ? f32(q0_in->detach(), who) : Tensor();
+  Tensor emb = has_q0 ? Tensor() : f32(emb_in->detach(), who);
+  const int64_t N = R.size(0), F = has_q0 ? q0.size(1) : emb.size(1);
+  c10::DeviceGuard guard(R.device());
+  c10::optional<Tensor> off_d = off.defined() ? c10::optional<Tensor>(off) : c10::optional<Tensor>();
+  auto plan = find_plan(idx_i, idx_j, N);
+  if (!plan || plan->filter_pairs < 0) {
+    Tensor r = pairwise_raw(R, idx_i, idx_j, off_d);
+    plan = get_plan(idx_i, idx_j, N, r);
+    decide_filter(*plan, r, cutoff);
+  }
+  auto M = get_painn(ws, F, shared_filters, eps);
+  auto H = get_head(head[0], head[1], head[2], head[3]);
+  Tensor p0 = f32(p0_in, who), p1 = opt_f32(p1_in, who);
+  spk_graph_t g = plan->graph();
+  spk_radial_t rb = radial_of(rbf_kind, p0, p1, cutoff);
+  spk_head_t hd;
+  hd.w1 = fp(H->w1); hd.w1t = fp(H->w1t); hd.b1 = fp(H->b1); hd.w2 = fp(H->w2); hd.b2 = fp(H->b2);
+  hd.n_hidden = (int32_t)H->w1.size(0); hd.act = (int32_t)head_act;
+  const bool fused = H->w1.dim() == 2 && H->w1.size(1) == F && H->w2.numel() == H->w1.size(0) && H->b1.defined() &&
+                     spk_painn_potential_supported(&M->m, &hd, &g, &rb) != 0;
+  if (fused) {
+    const bool inside = molecules_inside_groups(*plan, idx_m, n_mol);
+    Tensor q = at::empty({N, F}, R.options()), mu = at::empty({N, 3, F}, R.options());
+    Tensor E = at::empty({n_mol}, R.options()), gR = at::empty({N, 3}, R.options());
+    Tensor gr = at::empty({plan->n_edges, 3}, R.options());
+    Tensor pre_h = at::empty({N, (int64_t)hd.n_hidden}, R.options());
+    Tensor saved = at::empty({std::max<int64_t>(1, spk_painn_saved_floats(&M->m, N))}, R.options());
+    Tensor scratch = at::empty({std::max<int64_t>(1, spk_painn_scratch_floats(&M->m, N))}, R.options());
+    check(spk_painn_potential_gr_f32(&M->m, &hd, &g, &rb, fp(q0), fp(emb), Z.data_ptr<int64_t>(), emb.defined() ? (int32_t)emb.size(0) : 0, fp(R), fp(off),
+                                     idx_m.data_ptr<int64_t>(), n_mol, inside ? 1 : 0, fpm(q), fpm(mu), fpm(E), fpm(gr), fpm(pre_h), fpm(saved), fpm(scratch),
+                                     stream_of(R)));
+    check(spk_pairwise_bwd_graph_f32(fp(gr), &g, fpm(gR), stream_of(R)));
+    return {E, at::neg(gR), edge_virial_raw(gr, R, off, *plan, idx_m, n_mol), q, mu};
+  }
+  if (!has_q0) q0 = emb.index_select(0, Z);
+  Tensor r = pairwise_raw(R, idx_i, idx_j, off_d);
+  std::shared_ptr<Plan> pl;
+  auto fw = painn_forward_raw(q0, r, idx_i, idx_j, ws, shared_filters, eps, rbf_kind, p0, p1_in, cutoff, &pl);
+  auto hdf = atomwise_forward_raw(std::get<0>(fw), head[0], head[1], head[2], head[3], idx_m, n_mol, head_act);
+  Tensor gq = atomwise_backward_raw(at::ones({n_mol}, R.options()), Tensor(), std::get<2>(hdf), head[0], head[2], idx_m, n_mol, head_act);
+  auto bw = painn_backward_raw(gq, Tensor(), r, std::get<2>(fw), std::get<3>(fw), *pl, ws, F, shared_filters, eps, rbf_kind, p0, p1_in, cutoff, false);
+  Tensor gr = std::get<0>(bw);
+  Tensor gR = pairwise_bwd_raw(gr, idx_i, idx_j, N);
+  return {std::get<0>(hdf), at::neg(gR), edge_virial_raw(gr, R, off, *pl, idx_m, n_mol), std::get<0>(fw), std::get<1>(fw)};
+}
+
 // ------------------------------------------------------------------------------------------------ dispatcher handles
 template <class Sig>
 c10::TypedOperatorHandle<Sig> op_handle(const char* name) {
@@ -1389,6 +1509,21 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> painn_potential_forces_meta(const c10
   const int64_t F = (q0.has_value() && q0->defined()) ? q0->size(1) : emb->size(1);
   return {at::empty({n_mol}, R.options()), at::empty_like(R), at::empty({R.size(0), F}, R.options()), at::empty({R.size(0), 3, F}, R.options())};
 }
+std::tuple<Tensor, Tensor, Tensor, Tensor> schnet_potential_stress_meta(const c10::optional<Tensor>& x0, const c10::optional<Tensor>& emb, const Tensor&,
+                                                                        const Tensor& R, const c10::optional<Tensor>&, const Tensor&, const Tensor&, const Tensor&,
+                                                                        int64_t n_mol, at::TensorList, at::TensorList, int64_t, int64_t, const Tensor&,
+                                                                        const c10::optional<Tensor>&, double, int64_t) {
+  const int64_t F = (x0.has_value() && x0->defined()) ? x0->size(1) : emb->size(1);
+  return {at::empty({n_mol}, R.options()), at::empty_like(R), at::empty({n_mol, 3, 3}, R.options()), at::empty({R.size(0), F}, R.options())};
+}
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> painn_potential_stress_meta(const c10::optional<Tensor>& q0, const c10::optional<Tensor>& emb, const Tensor&,
+                                                                               const Tensor& R, const c10::optional<Tensor>&, const Tensor&, const Tensor&,
+                                                                               const Tensor&, int64_t n_mol, at::TensorList, at::TensorList, bool, double,
+                                                                               int64_t, const Tensor&, const c10::optional<Tensor>&, double, int64_t) {
+  const int64_t F = (q0.has_value() && q0->defined()) ? q0->size(1) : emb->size(1);
+  return {at::empty({n_mol}, R.options()), at::empty_like(R), at::empty({n_mol, 3, 3}, R.options()), at::empty({R.size(0), F}, R.options()),
+          at::empty({R.size(0), 3, F}, R.options())};
+}
 std::tuple<Tensor, Tensor, Tensor, Tensor> schnet_potential_forward_meta(const Tensor& x0, const Tensor&, const c10::optional<Tensor>&, const Tensor& idx_i,
                                                                          const Tensor&, const Tensor&, int64_t n_mol, at::TensorList ws, at::TensorList head,
                                                                          int64_t nf, int64_t, const Tensor&, const c10::optional<Tensor>&, double, int64_t) {
@@ -1738,6 +1873,8 @@ TORCH_LIBRARY(spk_hip, m) {
   m.def("schnet_potential(Tensor x0, Tensor R, Tensor? offsets, Tensor idx_i, Tensor idx_j, Tensor idx_m, int n_mol, Tensor[] weights, Tensor[] head, int n_filters, int rbf_kind, Tensor rbf_p0, Tensor? rbf_p1, float cutoff, int head_act) -> (Tensor, Tensor)");
   m.def("schnet_potential_forces(Tensor? x0, Tensor? embedding, Tensor Z, Tensor R, Tensor? offsets, Tensor idx_i, Tensor idx_j, Tensor idx_m, int n_mol, Tensor[] weights, Tensor[] head, int n_filters, int rbf_kind, Tensor rbf_p0, Tensor? rbf_p1, float cutoff, int head_act) -> (Tensor, Tensor, Tensor)");  // eval: (E, forces, scalar_representation), no autograd
   m.def("painn_potential_forces(Tensor? q0, Tensor? embedding, Tensor Z, Tensor R, Tensor? offsets, Tensor idx_i, Tensor idx_j, Tensor idx_m, int n_mol, Tensor[] weights, Tensor[] head, bool shared_filters, float epsilon, int rbf_kind, Tensor rbf_p0, Tensor? rbf_p1, float cutoff, int head_act) -> (Tensor, Tensor, Tensor, Tensor)");  // eval: (E, forces, scalar_representation, vector_representation), no autograd
+  m.def("schnet_potential_stress(Tensor? x0, Tensor? embedding, Tensor Z, Tensor R, Tensor? offsets, Tensor idx_i, Tensor idx_j, Tensor idx_m, int n_mol, Tensor[] weights, Tensor[] head, int n_filters, int rbf_kind, Tensor rbf_p0, Tensor? rbf_p1, float cutoff, int head_act) -> (Tensor, Tensor, Tensor, Tensor)");  // eval: (E, forces, virial [n_mol, 3, 3], scalar_representation), no autograd
+  m.def("painn_potential_stress(Tensor? q0, Tensor? embedding, Tensor Z, Tensor R, Tensor? offsets, Tensor idx_i, Tensor idx_j, Tensor idx_m, int n_mol, Tensor[] weights, Tensor[] head, bool shared_filters, float epsilon, int rbf_kind, Tensor rbf_p0, Tensor? rbf_p1, float cutoff, int head_act) -> (Tensor, Tensor, Tensor, Tensor, Tensor)");  // eval: (E, forces, virial, scalar_representation, vector_representation)
   m.def("potential_plan(Tensor idx_i, Tensor idx_j, int n_atoms, Tensor idx_m, int n_mol) -> int");
   m.def("eval_guard(Tensor(a) y, Tensor[] params) -> Tensor(a)");      // alias of y whose backward raises the eval-only message
   m.def("schnet_potential_forward(Tensor x0, Tensor R, Tensor? offsets, Tensor idx_i, Tensor idx_j, Tensor idx_m, int n_mol, Tensor[] weights, Tensor[] head, int n_filters, int rbf_kind, Tensor rbf_p0, Tensor? rbf_p1, float cutoff, int head_act) -> (Tensor, Tensor, Tensor, Tensor)");
@@ -1785,6 +1922,8 @@ TORCH_LIBRARY_IMPL(spk_hip, CUDA, m) {   // "CUDA" is the dispatch key of ROCm d
   m.impl("schnet_potential_forward", schnet_potential_forward_raw);
   m.impl("schnet_potential_forces", schnet_potential_forces_raw);
   m.impl("painn_potential_forces", painn_potential_forces_raw);
+  m.impl("schnet_potential_stress", schnet_potential_stress_raw);
+  m.impl("painn_potential_stress", painn_potential_stress_raw);
   m.impl("eval_guard", eval_guard_dev);
   m.impl("potential_plan", potential_plan_op);
   m.impl("schnet_potential_backward", schnet_potential_backward_raw);
@@ -1826,7 +1965,8 @@ TORCH_LIBRARY_IMPL(spk_hip, CPU, m) {
   for (const char* name : {"scatter_add", "gather", "pairwise", "pairwise_backward", "dense", "radial_cutoff", "schnet", "painn", "atomwise",
                            "dense_forward", "dense_backward_input", "radial_cutoff_backward", "schnet_forward", "schnet_backward", "painn_forward",
                            "painn_backward", "atomwise_forward", "atomwise_backward", "edge_plan", "static_declare", "static_declare_range", "schnet_potential",
-                           "schnet_potential_forward", "schnet_potential_backward", "schnet_potential_forces", "painn_potential_forces", "potential_plan"})
+                           "schnet_potential_forward", "schnet_potential_backward", "schnet_potential_forces", "painn_potential_forces", "potential_plan",
+                           "schnet_potential_stress", "painn_potential_stress"})
     m.impl(name, torch::CppFunction::makeFromBoxedFunction<&no_cpu_boxed>());
   for (const char* name : kTrainOps) m.impl(name, torch::CppFunction::makeFromBoxedFunction<&no_cpu_boxed>());
   for (const char* name : kFmOps) m.impl(name, torch::CppFunction::makeFromBoxedFunction<&no_cpu_boxed>());
@@ -1855,6 +1995,8 @@ TORCH_LIBRARY_IMPL(spk_hip, Meta, m) {
   m.impl("schnet_potential_forward", schnet_potential_forward_meta);
   m.impl("schnet_potential_forces", schnet_potential_forces_meta);
   m.impl("painn_potential_forces", painn_potential_forces_meta);
+  m.impl("schnet_potential_stress", schnet_potential_stress_meta);
+  m.impl("painn_potential_stress", painn_potential_stress_meta);
   m.impl("eval_guard", eval_guard_dev);
   m.impl("schnet_potential_backward", schnet_potential_backward_meta);
   train_impl_meta(m);

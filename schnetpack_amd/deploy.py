@@ -48,7 +48,10 @@ def _find_head(model):
     if getattr(frc, "energy_key", "energy") != getattr(head, "output_key", "energy"):
         raise ValueError("deploy: Forces must differentiate the Atomwise output")
     if getattr(frc, "calc_stress", False):
-        raise ValueError("deploy: stress is not part of the deployed force call")
+        # Strain -> ... -> Forces(calc_stress=True): the virial comes from the same per-edge gradient (spk_potential_compute*_virial), the
+        # file carries nothing for it
+        if not getattr(frc, "calc_forces", True) or not any(type(m).__name__ == "Strain" for m in getattr(model, "input_modules", [])):
+            raise ValueError("deploy: stress needs forces and a Strain input module")
     return head
 
 
@@ -195,7 +198,9 @@ class DeployedPotential:
     def _p(a, ct):
         return a.ctypes.data_as(ctypes.POINTER(ct)) if a is not None else None
 
-    def compute(self, z, R, idx_i, idx_j, offsets=None, idx_m=None, n_mol=1):
+    def compute(self, z, R, idx_i, idx_j, offsets=None, idx_m=None, n_mol=1, virial=False, atom_virial=False):
+        """-> (energy [n_mol], forces [N, 3]); with ``virial`` also W = dE/dstrain [n_mol, 3, 3] (stress = W / volume), with
+        ``atom_virial`` also the per-atom virial [N, 3, 3] (by centre atom, in the caller's atom order)."""
         from . import _lib
         z = np.ascontiguousarray(z, np.int64)
         R = np.ascontiguousarray(R, np.float32)
@@ -206,13 +211,28 @@ class DeployedPotential:
         n = int(z.shape[0])
         E = np.empty(int(n_mol), np.float32)
         Fo = np.empty((n, 3), np.float32)
-        _lib.check(self._L.spk_potential_compute(
-            self._h, n, self._p(z, ctypes.c_int64), self._p(R, ctypes.c_float), int(ii.shape[0]),
-            self._p(ii, ctypes.c_int64), self._p(jj, ctypes.c_int64), self._p(off, ctypes.c_float), int(n_mol),
-            self._p(im, ctypes.c_int64), self._p(E, ctypes.c_float), self._p(Fo, ctypes.c_float)))
-        return E, Fo
+        args = (self._h, n, self._p(z, ctypes.c_int64), self._p(R, ctypes.c_float), int(ii.shape[0]),
+                self._p(ii, ctypes.c_int64), self._p(jj, ctypes.c_int64), self._p(off, ctypes.c_float), int(n_mol),
+                self._p(im, ctypes.c_int64), self._p(E, ctypes.c_float), self._p(Fo, ctypes.c_float))
+        if not (virial or atom_virial):
+            _lib.check(self._L.spk_potential_compute(*args))
+            return E, Fo
+        W = np.empty((int(n_mol), 3, 3), np.float32)
+        Wa = np.empty((n, 3, 3), np.float32) if atom_virial else None
+        _lib.check(self._L.spk_potential_compute_virial(*args, self._p(W, ctypes.c_float), self._p(Wa, ctypes.c_float)))
+        return self._with_virial(E, Fo, W, Wa, virial, atom_virial)
 
-    def compute_cell(self, z, R, cell=None, pbc=None, idx_m=None, n_mol=1, skin=0.0):
+    @staticmethod
+    def _with_virial(E, Fo, W, Wa, virial, atom_virial):
+        out = (E, Fo)
+        if virial:
+            out += (W,)
+        if atom_virial:
+            out += (Wa,)
+        return out
+
+    def compute_cell(self, z, R, cell=None, pbc=None, idx_m=None, n_mol=1, skin=0.0, virial=False, atom_virial=False):
+        """-> (energy, forces[, virial][, atom_virial]) as :meth:`compute`, on the list the runtime builds itself."""
         from . import _lib
         z = np.ascontiguousarray(z, np.int64)
         R = np.ascontiguousarray(R, np.float32)
@@ -223,12 +243,18 @@ class DeployedPotential:
         E = np.empty(int(n_mol), np.float32)
         Fo = np.empty((n, 3), np.float32)
         stats = (ctypes.c_int64 * 2)()
-        _lib.check(self._L.spk_potential_compute_cell(
-            self._h, n, self._p(z, ctypes.c_int64), self._p(R, ctypes.c_float), int(n_mol),
-            self._p(im, ctypes.c_int64), self._p(c, ctypes.c_float), self._p(pb, ctypes.c_uint8), float(skin),
-            self._p(E, ctypes.c_float), self._p(Fo, ctypes.c_float), stats))
+        args = (self._h, n, self._p(z, ctypes.c_int64), self._p(R, ctypes.c_float), int(n_mol),
+                self._p(im, ctypes.c_int64), self._p(c, ctypes.c_float), self._p(pb, ctypes.c_uint8), float(skin),
+                self._p(E, ctypes.c_float), self._p(Fo, ctypes.c_float))
+        if not (virial or atom_virial):
+            _lib.check(self._L.spk_potential_compute_cell(*args, stats))
+            self.last_stats = {"pairs": int(stats[0]), "rebuilt": bool(stats[1])}
+            return E, Fo
+        W = np.empty((int(n_mol), 3, 3), np.float32)
+        Wa = np.empty((n, 3, 3), np.float32) if atom_virial else None
+        _lib.check(self._L.spk_potential_compute_cell_virial(*args, self._p(W, ctypes.c_float), self._p(Wa, ctypes.c_float), stats))
         self.last_stats = {"pairs": int(stats[0]), "rebuilt": bool(stats[1])}
-        return E, Fo
+        return self._with_virial(E, Fo, W, Wa, virial, atom_virial)
 
 
 def main(argv=None):

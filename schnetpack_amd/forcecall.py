@@ -16,7 +16,8 @@ __all__ = ["GraphedForceCall"]
 
 
 class GraphedForceCall:
-    """``call(inputs) -> {"energy", "forces"}`` for an eval-mode ``NeuralNetworkPotential``.
+    """``call(inputs) -> {"energy", "forces"}`` for an eval-mode ``NeuralNetworkPotential`` (and ``"stress"`` when the model
+    outputs it: ``Strain`` + ``Forces(calc_stress=True)``; the batch then carries ``_cell``, copied like the positions).
 
     ``inputs`` is the reference's batch dict (``_atomic_numbers``, ``_positions``, ``_idx_i``,
     ``_idx_j``, ``_offsets``, ``_idx_m``, optionally ``_n_molecules`` / ``_n_atoms``).  Positions and
@@ -25,9 +26,10 @@ class GraphedForceCall:
     tensors are static output buffers: they are overwritten by the next call.
     """
 
-    def __init__(self, model, energy_key: str = "energy", force_key: str = "forces", use_graph: bool = True):
+    def __init__(self, model, energy_key: str = "energy", force_key: str = "forces", use_graph: bool = True,
+                 stress_key: str = "stress"):
         self.model = model.eval()
-        self.energy_key, self.force_key = energy_key, force_key
+        self.energy_key, self.force_key, self.stress_key = energy_key, force_key, stress_key
         self.use_graph = use_graph
         self.graph: Optional[torch.cuda.CUDAGraph] = None
         self._key = None
@@ -42,13 +44,16 @@ class GraphedForceCall:
 
     def _eager(self, static):
         out = self.model(dict(static))
+        if self.stress_key in out:
+            return out[self.energy_key].detach(), out[self.force_key].detach(), out[self.stress_key].detach()
         return out[self.energy_key].detach(), out[self.force_key].detach()
 
     def _capture(self, inputs):
         self._static = {k: v for k, v in inputs.items()}
         self._static[properties.R] = inputs[properties.R].detach().clone()
-        if inputs.get(properties.offsets) is not None:
-            self._static[properties.offsets] = inputs[properties.offsets].detach().clone()
+        for k in (properties.offsets, properties.cell):
+            if inputs.get(k) is not None:
+                self._static[k] = inputs[k].detach().clone()
         self._src = (inputs[properties.idx_i], inputs[properties.idx_j])   # keep the list alive
         self.graph = None
         self._out = self._eager(self._static)          # also builds the edge plan (one sync) outside the capture
@@ -76,14 +81,21 @@ class GraphedForceCall:
         with torch.no_grad():   # the model marks the static positions as requiring grad (a leaf): plain data copies
             if inputs[properties.R] is not self._static[properties.R]:
                 self._static[properties.R].copy_(inputs[properties.R].detach())
-            off = inputs.get(properties.offsets)
-            if off is not None and off is not self._static[properties.offsets]:
-                self._static[properties.offsets].copy_(off.detach())
+            for k in (properties.offsets, properties.cell):
+                v = inputs.get(k)
+                if v is not None and k in self._static and v is not self._static[k]:
+                    self._static[k].copy_(v.detach())
         if self.graph is not None:
             self.graph.replay()
         else:
             self._out = self._eager(self._static)
-        return {self.energy_key: self._out[0], self.force_key: self._out[1]}
+        return self._result()
+
+    def _result(self) -> Dict[str, torch.Tensor]:
+        res = {self.energy_key: self._out[0], self.force_key: self._out[1]}
+        if len(self._out) > 2:
+            res[self.stress_key] = self._out[2]
+        return res
 
     @property
     def positions(self) -> torch.Tensor:
@@ -96,4 +108,4 @@ class GraphedForceCall:
             self.graph.replay()
         else:
             self._out = self._eager(self._static)
-        return {self.energy_key: self._out[0], self.force_key: self._out[1]}
+        return self._result()

@@ -74,6 +74,8 @@ def _fused_potential_call(orig_call):
         inputs = self.initialize_derivatives(args[0])
         if mode == 2:
             inputs = M.potential_forces_forward(self, inputs)
+        elif mode == 3:
+            inputs = M.potential_stress_forward(self, inputs)
         else:
             inputs = M.potential_forward(self, inputs)
             for i, m in enumerate(self.output_modules):

@@ -6,7 +6,7 @@ import torch
 import torch.nn as nn
 
 from . import properties
-from .atomistic import Atomwise, Forces, PairwiseDistances
+from .atomistic import Atomwise, Forces, PairwiseDistances, Strain
 from .nn import CosineCutoff, GaussianRBF, BesselRBF
 from .representation import PaiNN, SchNet
 
@@ -23,22 +23,36 @@ def _is_forces(m) -> bool:
             and all(hasattr(m, a) for a in ("calc_forces", "calc_stress", "energy_key", "force_key")))
 
 
+def _is_strain(m) -> bool:
+    """The mirror's ``Strain`` or the reference's own (atomistic/response.py:434-464), not a subclass."""
+    t = type(m)
+    return t is Strain or (t.__name__ == "Strain" and t.__module__ == "schnetpack.atomistic.response")
+
+
 def classify_potential(model) -> int:
     """0: module-by-module.  1: the standard potential -- ``PairwiseDistances`` -> fused ``SchNet`` -> ``Atomwise`` (default
     head, summed or averaged over the molecule) -> ``Forces`` without stress: representation + head are ONE operator.
     2: ... and the only other output is Forces' -dE/dR of a summed energy: energies AND forces from the two launches.
+    3: ``Strain`` -> ``PairwiseDistances`` -> ... -> ``Forces(calc_forces=True, calc_stress=True)`` of the summed energy: energies,
+    forces and the virial dE/dstrain from the same operators (``*_potential_stress``).
     Works on any model with the reference's ``NeuralNetworkPotential`` layout (model/base.py:132-190), i.e. also on the
     reference's own class around the HIP modules."""
     rep, ins, outs = model.representation, list(model.input_modules), list(model.output_modules)
     is_painn = isinstance(rep, PaiNN)
     if not (isinstance(rep, (SchNet, PaiNN)) and rep._fused and len(rep.interactions) > 0):
         return 0
-    if not (len(ins) == 1 and type(ins[0]) is PairwiseDistances and len(outs) >= 1):
+    strained = len(ins) == 2 and _is_strain(ins[0]) and type(ins[1]) is PairwiseDistances
+    if not ((strained or (len(ins) == 1 and type(ins[0]) is PairwiseDistances)) and len(outs) >= 1):
         return 0
     head = outs[0]
     if not (isinstance(head, Atomwise) and head._fused_head and head.per_atom_output_key is None
             and head.aggregation_mode in ("sum", "avg")):
         return 0
+    if strained:
+        frc = outs[1] if len(outs) == 2 else None
+        ok = (frc is not None and _is_forces(frc) and frc.calc_forces and frc.calc_stress and frc.energy_key == head.output_key
+              and head.aggregation_mode == "sum")
+        return 3 if ok else 0
     if not all(_is_forces(m) and not m.calc_stress for m in outs[1:]):
         return 0
     if (len(outs) == 2 and outs[1].calc_forces and outs[1].energy_key == head.output_key and head.aggregation_mode == "sum"):
@@ -100,6 +114,40 @@ def potential_forces_forward(model, inputs: Dict[str, torch.Tensor]) -> Dict[str
     inputs["scalar_representation"] = x
     inputs[head.output_key] = E
     inputs[frc.force_key] = F
+    return inputs
+
+
+def potential_stress_forward(model, inputs: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """Energies, forces and stress straight from the operators (eval only, like :func:`potential_forces_forward`): the operator returns the
+    virial W = dE/dstrain [n_mol, 3, 3]; stress = W / V with the signed cell volume, as ``Forces`` computes it (atomistic/response.py:81-90).
+    ``Strain`` itself does not run: at zero strain it leaves positions, offsets and cell as they are."""
+    rep, head, frc = model.representation, model.output_modules[0], model.output_modules[1]
+    idx_m = inputs[properties.idx_m]
+    kind, p0, p1 = rep.radial_basis.kernel_params()
+    l0, l1 = head.outnet[0], head.outnet[1]
+    plain = type(rep.embedding) is nn.Embedding and len(rep.electronic_embeddings) == 0
+    common = (inputs[properties.Z], inputs[properties.R], inputs.get(properties.offsets), inputs[properties.idx_i], inputs[properties.idx_j], idx_m,
+              head._n_molecules(inputs, idx_m), rep.interaction_weights(), [l0.weight, l0.bias, l1.weight, l1.bias])
+    with torch.no_grad():
+        if isinstance(rep, PaiNN):
+            E, F, W, x, mu = torch.ops.spk_hip.painn_potential_stress(
+                None if plain else rep.embed(inputs), rep.embedding.weight if plain else None, *common, rep.share_filters, rep.epsilon, kind, p0, p1,
+                rep.cutoff_fn.cutoff_value(), head._head_act)
+            inputs["vector_representation"] = mu
+        else:
+            E, F, W, x = torch.ops.spk_hip.schnet_potential_stress(
+                None if plain else rep.embed(inputs), rep.embedding.weight if plain else None, *common, rep.n_filters, kind, p0, p1,
+                rep.cutoff_fn.cutoff_value(), head._head_act)
+        cell = inputs[properties.cell]
+        volume = torch.sum(cell[:, 0, :] * torch.cross(cell[:, 1, :], cell[:, 2, :], dim=1), dim=1, keepdim=True)[:, :, None]
+        S = W / volume
+    if torch.is_grad_enabled():
+        guard = [l0.weight]
+        E, F, S = torch.ops.spk_hip.eval_guard(E, guard), torch.ops.spk_hip.eval_guard(F, guard), torch.ops.spk_hip.eval_guard(S, guard)
+    inputs["scalar_representation"] = x
+    inputs[head.output_key] = E
+    inputs[frc.force_key] = F
+    inputs[frc.stress_key] = S
     return inputs
 
 
@@ -174,6 +222,8 @@ class NeuralNetworkPotential(nn.Module):
     model_outputs: List[str]
     _potential: Final[bool]
     _potential_forces: Final[bool]
+    #: eval mode of ``Strain`` -> standard potential -> ``Forces(calc_stress=True)``: energies, forces and stress from one operator
+    _potential_stress: bool
     #: training mode of the standard potential through the force-matching engine (``spk_hip::schnet_fm`` / ``painn_fm``: weight
     #: gradients of a loss(E, F) by forward-over-reverse).  Set to False for the operator-by-operator path (any-order autograd).
     fm_engine: bool
@@ -197,9 +247,10 @@ class NeuralNetworkPotential(nn.Module):
                     outs.append(k)
         self.model_outputs = outs
         mode = classify_potential(self)
-        self._potential = mode >= 1
+        self._potential = mode in (1, 2)
         # ... and when the only other output is Forces' -dE/dR, energies AND forces come from the two launches directly
         self._potential_forces = mode == 2
+        self._potential_stress = mode == 3
         self._fm_head_act = classify_fm(self)
         self.fm_engine = self._fm_head_act > 0
 
@@ -215,6 +266,10 @@ class NeuralNetworkPotential(nn.Module):
     def _potential_forces_forward(self, inputs: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
         return potential_forces_forward(self, inputs)
 
+    @torch.jit.unused
+    def _potential_stress_forward(self, inputs: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+        return potential_stress_forward(self, inputs)
+
     def forward(self, inputs: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
         for p in self.required_derivatives:
             if p in inputs:
@@ -229,6 +284,9 @@ class NeuralNetworkPotential(nn.Module):
             return {k: inputs[k] for k in self.model_outputs}
         if self._potential_forces and not self.training and not torch.jit.is_scripting():
             inputs = self._potential_forces_forward(inputs)
+            return {k: inputs[k] for k in self.model_outputs}
+        if self._potential_stress and not self.training and not torch.jit.is_scripting():
+            inputs = self._potential_stress_forward(inputs)
             return {k: inputs[k] for k in self.model_outputs}
         if self.training and self.fm_engine and not torch.jit.is_scripting():
             pos = inputs[properties.R]

@@ -175,6 +175,45 @@ def ring_graph_batch(n_atoms: int, degree: int, seed: int = 0, dmin: float = 0.8
     }
 
 
+def periodic_molecule_batch(name: str = "aspirin", n_frames: int = 8, edge: float = 11.0, tilt: float = 0.2, seed: int = 0,
+                            cutoff: float = 5.0, jitter: float = 0.05) -> Dict[str, torch.Tensor]:
+    """``n_frames`` jittered copies of a molecule, each in its OWN periodic cell (the stress workload of a molecular batch): even frames
+    a cube of edge ``edge``, odd frames (``tilt`` != 0) the triclinic cell with rows (L, 0, 0), (t L, L, 0), (t L, t L, L).  Every cell is
+    at least 2 cutoff thick in every direction, so a pair has at most one image inside the cutoff, the list stays block-diagonal by
+    frame (the molecule-resident plan can cover it) and a brute-force search over the 27 nearest images is exact.  Pairs sorted by
+    (i, j); ``offsets`` = image shift @ cell; ``cell`` [n_frames, 3, 3] (rows = cell vectors)."""
+    if name == "aspirin":
+        Z0, R0 = ASPIRIN_Z, np.asarray(ASPIRIN_R)
+    elif name == "ethanol":
+        Z0, R0 = ETHANOL_Z, np.asarray(ETHANOL_R)
+    else:
+        raise ValueError(name)
+    if edge < 2 * cutoff + 1:
+        raise ValueError("periodic_molecule_batch: cell edge %g below 2 cutoff + 1" % edge)
+    rng = np.random.RandomState(seed)
+    shifts = np.array([(a, b, c) for a in (-1, 0, 1) for b in (-1, 0, 1) for c in (-1, 0, 1)], dtype=np.float32)
+    systems, cells = [], []
+    for k in range(n_frames):
+        t = tilt if k % 2 == 1 else 0.0
+        cell = (np.array([[1, 0, 0], [t, 1, 0], [t, t, 1]], dtype=np.float64) * edge).astype(np.float32)
+        vol = abs(float(np.linalg.det(cell.astype(np.float64))))
+        heights = [vol / np.linalg.norm(np.cross(cell[(q + 1) % 3], cell[(q + 2) % 3]).astype(np.float64)) for q in range(3)]
+        if min(heights) < 2 * cutoff:
+            raise ValueError("periodic_molecule_batch: tilt %g leaves the cell thinner than 2 cutoff" % tilt)
+        R = (R0 + jitter * rng.randn(*R0.shape) if jitter > 0 else R0.copy()).astype(np.float32)
+        offs = shifts @ cell                                    # [27, 3]
+        diff = R[None, :, None, :] - R[:, None, None, :] + offs[None, None, :, :]     # [i, j, image, 3]
+        d = np.sqrt((diff * diff).sum(-1, dtype=np.float32))
+        mask = d < np.float32(cutoff)
+        mask[np.arange(len(R)), np.arange(len(R)), 13] = False  # (image 13 = no shift)
+        ii, jj, ss = np.nonzero(mask)                           # row-major => sorted by (i, j)
+        systems.append({"Z": Z0, "R": R, "idx_i": ii.astype(np.int64), "idx_j": jj.astype(np.int64), "offsets": offs[ss].astype(np.float32)})
+        cells.append(cell)
+    batch = collate(systems)
+    batch["cell"] = torch.from_numpy(np.stack(cells))
+    return batch
+
+
 def water_box(n_side: int = 22, cutoff: float = 5.0, seed: int = 0, jitter: float = 0.3):
     """Bulk-water-like periodic box (SURVEY.md §8(d) cfg 5): n_side^3 molecules on a jittered
     cubic lattice at 0.0334 molecules/A^3, rigid TIP3P-like geometry, random orientations.

@@ -1,0 +1,251 @@
+"""Stress from the standard potential on the device (model.classify_potential == 3: Strain -> PairwiseDistances -> SchNet / PaiNN ->
+Atomwise -> Forces(calc_stress=True)), through torch.ops.spk_hip.*_potential_stress, GraphedForceCall and the deployed runtime.
+Oracle: the same model module by module in fp64 on the host (the mirrors' ATen route: the reference's formulas, Strain included);
+second oracle: the module-by-module route on the device.  Tolerance 1e-5 relative."""
+import copy
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import rel_err
+from oracle import refshim
+from schnetpack_amd import _lib, model as M, synthetic as S
+from schnetpack_amd.atomistic import Forces, PairwiseDistances, Strain
+from schnetpack_amd.forcecall import GraphedForceCall
+
+pytestmark = pytest.mark.gpu
+TOL = 1e-5
+
+
+@pytest.fixture(scope="module")
+def dev():
+    if not torch.cuda.is_available():
+        pytest.skip("needs a ROCm device")
+    return torch.device("cuda:0")
+
+
+def _models(kind, radial, seed=0):
+    torch.manual_seed(seed)
+    base = M.build_model(kind, radial=radial)
+    head = base.output_modules[0]
+    st = M.NeuralNetworkPotential(base.representation, input_modules=[Strain(), PairwiseDistances()],
+                                  output_modules=[head, Forces(calc_forces=True, calc_stress=True)])
+    return st, base
+
+
+def _inputs(b, device, dtype=torch.float32):
+    return {"_atomic_numbers": b["Z"].to(device), "_positions": b["R"].to(dtype).clone().to(device), "_idx_i": b["idx_i"].to(device),
+            "_idx_j": b["idx_j"].to(device), "_offsets": b["offsets"].to(dtype).clone().to(device), "_idx_m": b["idx_m"].to(device),
+            "_cell": b["cell"].reshape(-1, 3, 3).to(dtype).clone().to(device), "_n_molecules": int(b["n_mol"])}
+
+
+def _batch(regime):
+    if regime == "box":
+        return S.water_box(n_side=4, seed=2)
+    return S.periodic_molecule_batch("aspirin", 8, edge=11.0, tilt=0.2, seed=4)
+
+
+@pytest.mark.parametrize("regime", ["mol", "box"])
+@pytest.mark.parametrize("radial", ["gaussian", "bessel"])
+@pytest.mark.parametrize("kind", ["schnet", "painn"])
+def test_stress_operator(dev, kind, radial, regime):
+    b = _batch(regime)
+    st, base = _models(kind, radial)
+    st, base = st.to(dev).eval(), base.to(dev).eval()
+    assert M.classify_potential(st) == 3
+    _lib.profile_enable(True)
+    _lib.profile_report()
+    out = st(_inputs(b, dev))
+    prof = _lib.profile_report()
+    _lib.profile_enable(False)
+    assert "edge_virial" in prof and "virial_mol" in prof, prof
+    if regime == "mol":                     # the molecule-resident launches ran
+        assert (kind + "_mol_fwd") in prof and (kind + "_mol_bwd") in prof, prof
+    out2 = st(_inputs(b, dev))
+    plain = base(_inputs(b, dev))
+    # oracle: fp64 host, module by module (Strain + autograd through the ATen route)
+    ref = copy.deepcopy(st).double().cpu()(_inputs(b, "cpu", torch.float64))
+    assert out["stress"].shape == (int(b["n_mol"]), 3, 3)
+    assert rel_err(out["stress"].cpu(), ref["stress"].detach()) < TOL
+    assert rel_err(out["forces"].cpu(), ref["forces"].detach()) < TOL
+    assert rel_err(out["energy"].cpu(), ref["energy"].detach()) < TOL
+    if kind == "painn" and regime == "mol":
+        # the molecule-resident PaiNN launches sum in a fixed order: deterministic, energies bit-identical to the stress-free call; its
+        # backward writes either the forces or dE/dr, so the forces come from the row sum of dE/dr (equal to float round-off)
+        assert torch.equal(out["stress"], out2["stress"]) and torch.equal(out["forces"], out2["forces"])
+        assert torch.equal(out["energy"], plain["energy"])
+        assert rel_err(out["forces"].cpu(), plain["forces"].cpu()) <= 2e-6
+    else:
+        # (SchNet's molecule-resident backward accumulates its per-pair sums with LDS float atomics, and the stage kernels of a small box
+        # may sum with float atomics: run-to-run round-off of dE/dr itself, not of the virial reduction -- test_edge_virial_kernel)
+        assert rel_err(out["energy"].cpu(), plain["energy"].cpu()) <= 2e-6 and rel_err(out["forces"].cpu(), plain["forces"].cpu()) <= 2e-6
+        assert rel_err(out["stress"].cpu(), out2["stress"].cpu()) <= 2e-6
+    # second oracle: the module-by-module route on the device
+    st._potential_stress = False
+    try:
+        mbm = st(_inputs(b, dev))
+    finally:
+        st._potential_stress = True
+    assert rel_err(out["stress"].cpu(), mbm["stress"].detach().cpu()) < TOL
+
+
+def test_graphed_force_call_returns_the_stress(dev):
+    b = _batch("mol")
+    st, _ = _models("painn", "gaussian")          # (deterministic launches: replay == eager bit for bit)
+    st = st.to(dev).eval()
+    inp = _inputs(b, dev)
+    eager = st(dict(inp))
+    gfc = GraphedForceCall(st)
+    r1 = gfc(inp)
+    inp2 = dict(inp)
+    inp2["_positions"] = inp["_positions"] + 0.01 * torch.randn_like(inp["_positions"])
+    r2 = gfc(inp2)
+    assert gfc.graph is not None and gfc.n_captures == 1
+    eager2 = st(dict(inp2))
+    assert torch.equal(r2["stress"], eager2["stress"]) and torch.equal(r2["forces"], eager2["forces"])
+    assert not torch.equal(eager["stress"], eager2["stress"])
+
+
+@pytest.mark.skipif(not refshim.available(), reason="neither the reference package nor oracle/_ref present")
+def test_installed_reference_model_routes_to_stress_operator(dev):
+    import sys
+    import schnetpack_amd.install as inst
+    ns = refshim.load()
+    sys.modules["ase.data"].atomic_masses = np.ones(119)
+    spk = sys.modules["schnetpack"]
+    b = _batch("mol")
+    try:
+        inst.install(spk)
+        torch.manual_seed(0)
+        rb, cf = spk.nn.GaussianRBF(20, 5.0), spk.nn.CosineCutoff(5.0)
+        rep = sys.modules["schnetpack.representation.schnet"].SchNet(128, 3, rb, cf)
+        aw = sys.modules["schnetpack.atomistic.atomwise"].Atomwise(n_in=128, output_key="energy")
+        pd = sys.modules["schnetpack.atomistic.distances"].PairwiseDistances()
+        m = ns.model.NeuralNetworkPotential(rep, input_modules=[ns.response.Strain(), pd],
+                                            output_modules=[aw, ns.response.Forces(calc_forces=True, calc_stress=True)]).to(dev).eval()
+        inp = _inputs(b, dev)
+        inp["_n_atoms"] = torch.bincount(b["idx_m"]).to(dev)
+        out = m(inp)
+        assert m.__dict__["_spk_hip_mode"] == 3
+        ref = m.double().cpu()
+        ref.__dict__["_spk_hip_mode"] = 0
+        inp64 = _inputs(b, "cpu", torch.float64)
+        inp64["_n_atoms"] = torch.bincount(b["idx_m"])
+        out_ref = ref(inp64)
+    finally:
+        inst.uninstall()
+    assert rel_err(out["stress"].cpu(), out_ref["stress"].detach()) < TOL
+
+
+def _deployed(st):
+    from schnetpack_amd import deploy
+    return deploy.DeployedPotential(deploy.export_potential(st))
+
+
+@pytest.mark.parametrize("kind", ["schnet", "painn"])
+def test_deployed_virial_on_the_box(dev, kind):
+    b = _batch("box")
+    st, _ = _models(kind, "gaussian")
+    st = st.to(dev).eval()
+    pot = _deployed(st)
+    Z, R, cell = b["Z"].numpy(), b["R"].numpy(), b["cell"].numpy().reshape(1, 3, 3)
+    pbc = np.ones((1, 3), np.uint8)
+    V = float(np.linalg.det(cell[0].astype(np.float64)))
+    out = st(_inputs(b, dev))
+    E, F, W = pot.compute_cell(Z, R, cell, pbc, skin=1.0, virial=True)
+    assert W.shape == (1, 3, 3)
+    assert rel_err(torch.from_numpy(W / V), out["stress"].cpu()) < TOL
+    assert rel_err(torch.from_numpy(F), out["forces"].cpu()) < TOL
+    # a displacement below skin / 2 keeps the (cutoff + skin) list: pairs beyond the cutoff contribute nothing
+    rng = np.random.RandomState(0)
+    R2 = (R + rng.uniform(-0.1, 0.1, R.shape)).astype(np.float32)
+    E2, F2, W2 = pot.compute_cell(Z, R2, cell, pbc, skin=1.0, virial=True)
+    assert not pot.last_stats["rebuilt"]
+    fresh = _deployed(st)                          # a list built for the displaced positions (no skin)
+    E4, F4, W4 = fresh.compute_cell(Z, R2, cell, pbc, skin=0.0, virial=True)
+    assert rel_err(torch.from_numpy(W2), torch.from_numpy(W4)) < TOL and rel_err(torch.from_numpy(F2), torch.from_numpy(F4)) < TOL
+    # the plain call is unchanged by the virial form
+    E3, F3 = pot.compute_cell(Z, R2, cell, pbc, skin=1.0)
+    assert rel_err(torch.from_numpy(F3), torch.from_numpy(F2)) < 2e-6
+
+
+def test_deployed_virial_on_a_permuted_list(dev):
+    b = _batch("box")
+    st, _ = _models("schnet", "gaussian")
+    st = st.to(dev).eval()
+    pot = _deployed(st)
+    Z, R = b["Z"].numpy(), b["R"].numpy()
+    ii, jj, off = b["idx_i"].numpy(), b["idx_j"].numpy(), b["offsets"].numpy()
+    E0, F0, W0, Wa0 = pot.compute(Z, R, ii, jj, off, virial=True, atom_virial=True)
+    perm = np.lexsort((ii, jj))                         # ordered by neighbour, like a LAMMPS list by local index
+    E1, F1, W1, Wa1 = pot.compute(Z, R, ii[perm], jj[perm], off[perm], virial=True, atom_virial=True)
+    assert rel_err(torch.from_numpy(W1), torch.from_numpy(W0)) < TOL and rel_err(torch.from_numpy(Wa1), torch.from_numpy(Wa0)) < TOL
+    assert rel_err(torch.from_numpy(Wa1.sum(0)), torch.from_numpy(W1[0])) < TOL
+    V = float(np.linalg.det(b["cell"].numpy().astype(np.float64)))
+    out = st(_inputs(b, dev))
+    assert rel_err(torch.from_numpy(W1 / V), out["stress"].cpu()) < TOL
+
+
+def test_virial_on_an_unsorted_list(dev):
+    """A list not sorted by idx_i takes the device by-centre order (spk_transpose_plan) inside the operator."""
+    b = _batch("box")
+    st, _ = _models("schnet", "gaussian")
+    st = st.to(dev).eval()
+    ref = st(_inputs(b, dev))
+    ii, jj = b["idx_i"].numpy(), b["idx_j"].numpy()
+    perm = torch.from_numpy(np.lexsort((ii, jj)))
+    b2 = dict(b)
+    b2["idx_i"], b2["idx_j"], b2["offsets"] = b["idx_i"][perm], b["idx_j"][perm], b["offsets"][perm]
+    out = st(_inputs(b2, dev))
+    assert rel_err(out["stress"].cpu(), ref["stress"].cpu()) < TOL
+
+
+@pytest.mark.parametrize("sort", [True, False])
+def test_edge_virial_kernel(dev, sort):
+    """spk_edge_virial_f32 on a given dE/dr: fp64 oracle, per-atom sums, bit-identical repeats; one molecule of 5 000 atoms (many chunk
+    partials) between small ones, and an empty molecule."""
+    from schnetpack_amd import ops  # noqa: F401
+    gen = torch.Generator().manual_seed(3)
+    sizes = [7, 5000, 1, 0, 130]
+    idx_m = torch.cat([torch.full((n,), m, dtype=torch.int64) for m, n in enumerate(sizes)])
+    N, n_mol = int(idx_m.numel()), len(sizes)
+    R = torch.randn(N, 3, generator=gen) * 4
+    ii, jj = [], []
+    a0 = 0
+    for n in sizes:
+        if n > 1:
+            k = 12 * n
+            ii.append(a0 + torch.randint(0, n, (k,), generator=gen))
+            jj.append(a0 + torch.randint(0, n, (k,), generator=gen))
+        a0 += n
+    ii, jj = torch.cat(ii), torch.cat(jj)
+    order = torch.argsort(ii * N + jj) if sort else torch.randperm(ii.numel(), generator=gen)
+    ii, jj = ii[order].contiguous(), jj[order].contiguous()
+    E = int(ii.numel())
+    off = torch.randn(E, 3, generator=gen)
+    gr = torch.randn(E, 3, generator=gen)
+    r = (R[jj].double() - R[ii].double()) + off.double()
+    Wref = torch.zeros(n_mol, 3, 3, dtype=torch.float64).index_add_(0, idx_m[ii], gr.double()[:, :, None] * r[:, None, :])
+    Waref = torch.zeros(N, 3, 3, dtype=torch.float64).index_add_(0, ii, gr.double()[:, :, None] * r[:, None, :])
+    d = {k: v.to(dev) for k, v in dict(R=R, ii=ii, jj=jj, off=off, gr=gr, idx_m=idx_m).items()}
+    g = _lib.GraphT()
+    g.n_atoms, g.n_edges = N, E
+    g.idx_i, g.idx_j = d["ii"].data_ptr(), d["jj"].data_ptr()
+    if sort:
+        rowptr = torch.searchsorted(ii, torch.arange(N + 1)).to(torch.int32).to(dev)
+        g.rowptr, g.sorted = rowptr.data_ptr(), 1
+    L = _lib.lib()
+    ws = torch.empty(max(1, int(L.spk_edge_virial_workspace_bytes(g, n_mol, 1))), dtype=torch.uint8, device=dev)
+    outs = []
+    for _ in range(2):
+        W = torch.full((n_mol, 3, 3), float("nan"), device=dev)
+        Wa = torch.full((N, 3, 3), float("nan"), device=dev)
+        _lib.check(L.spk_edge_virial_f32(d["gr"].data_ptr(), d["R"].data_ptr(), d["off"].data_ptr(), g, d["idx_m"].data_ptr(), n_mol,
+                                         W.data_ptr(), Wa.data_ptr(), ws.data_ptr(), torch.cuda.current_stream().cuda_stream))
+        torch.cuda.synchronize()
+        outs.append((W.cpu(), Wa.cpu()))
+    (W, Wa), (W2, Wa2) = outs
+    assert torch.equal(W, W2) and torch.equal(Wa, Wa2)
+    assert float(W[3].abs().max()) == 0.0 and float(W[2].abs().max()) == 0.0      # no atoms / no edges
+    assert rel_err(W, Wref) < TOL and rel_err(Wa, Waref) < TOL
