@@ -412,8 +412,389 @@ def collate_goldens(ns):
     print("wrote collate_reference.npz", len(arrs), "arrays")
 
 
+# ------------------------------------------------------------------------------------------------ MD step fixtures
+# md_pile / md_verlet / md_simulate / md_fold: the reference's own PILE-L thermostat, velocity-Verlet steps, simulator loop and
+# replica folding, lifted method by method with ``ast`` (the modules around them pull in ase / hydra / tqdm) and run against
+# small stand-ins that carry exactly the attributes those methods read.  Only arrays and short tags are stored.
+#
+# The reference's ``units.py`` needs ase, so the lifted code sees a ``spk_units`` stand-in whose kB / fs / hbar are the
+# project's KB_MD / FS_MD / HBAR_MD (stored in each fixture that uses them).  The unit constants themselves are therefore
+# NOT pinned by these fixtures: ase's CODATA year differs from the project's values in the 7th digit.
+MD_FIXTURES = ("md_pile", "md_verlet", "md_simulate", "md_fold")
+PILE_BEADS = (1, 2, 3, 4, 5, 8, 16, 32, 64)
+# (omega, dt, tau_fs, thermostat_centroid, damping_factor); set 2 is the TRPMD form
+PILE_SETS = ((55.0, 5e-4, 100.0, True, 1.0), (157.0, 2e-4, 10.0, True, 1.0), (40.0, 5e-4, 1.0, False, 0.5), (314.0, 5e-4, 1000.0, True, 1.0))
+PILE_T, PILE_SEED, PILE_STEP, PILE_WHICH = 300.0, 0x5EED0123456789, 7, 1
+# the GPU trajectory test (tests/test_gpu_md_reference.py) bounds positions at 1e-5 and momenta at 1e-4
+SIM_TOL_Q, SIM_TOL_P = 1e-5, 1e-4
+# time step and time constant (fs; FS_MD makes it 0.4 time units): centroid c1 = exp(-dt / 2 tau) = 0.61, and with the seeded
+# SchNet's forces (|F| ~ 0.2 .. 0.8) a kick dt/2 F is ~ 0.1 next to momenta of ~ 0.4 .. 2, so (1 - c1) dt/2 F -- what a swapped
+# thermostat / kick pair changes per step -- is percent-level.  At the dt = 0.02 of the NVE tests the orders differ by 4e-4 only.
+SIM = dict(n_beads=4, n_steps=6, dt=0.4, omega=3.0, tau_fs=400.0, T=3.0, seed=0xC0FFEE1234)
+
+
+def _md_path(*parts):
+    return os.path.join(refshim.REF_SRC, "schnetpack", "md", *parts)
+
+
+def _lift(path, cls, names, env):
+    """{name: function} of methods ``names`` of class ``cls`` in the reference file ``path``, compiled in memory against ``env``
+    (annotations dropped: they name classes of modules that cannot be imported here)."""
+    import ast
+    tree = ast.parse(open(path).read())
+    node = [n for n in tree.body if isinstance(n, ast.ClassDef) and n.name == cls][0]
+    out = {}
+    for fn in node.body:
+        if isinstance(fn, ast.FunctionDef) and fn.name in names:
+            fn.decorator_list, fn.returns = [], None
+            for a in fn.args.args + fn.args.kwonlyargs:
+                a.annotation = None
+            exec(compile(ast.Module([fn], []), os.path.basename(path), "exec"), env)
+            out[fn.name] = env[fn.name]
+    missing = set(names) - set(out)
+    assert not missing, (path, cls, missing)
+    return out
+
+
+class _TorchWithNoise:
+    """``torch`` as the lifted thermostat sees it: ``randn_like`` hands out the prepared noise tensors in order."""
+
+    def __init__(self, noise):
+        self._noise = list(noise)
+
+    def randn_like(self, x):
+        n = self._noise.pop(0)
+        assert n.shape == x.shape
+        return n.to(x.dtype)
+
+    def __getattr__(self, name):
+        return getattr(torch, name)
+
+
+def _md_units():
+    import types
+    from schnetpack_amd import md as MD
+    return types.SimpleNamespace(kB=MD.KB_MD, fs=MD.FS_MD, hbar=MD.HBAR_MD)
+
+
+def _nm_transformer():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("_ref_nmt", _md_path("utils", "normal_model_transformation.py"))
+    nmt = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(nmt)
+    return nmt.NormalModeTransformer
+
+
+class _RingSystem:
+    """The attributes of md/system.py that integrators and thermostats touch (normal-mode properties of :444-482)."""
+
+    def __init__(self, q, p, m, n_beads, forces=None):
+        self.positions, self.momenta, self.masses, self.n_replicas = q, p, m, n_beads
+        self.forces = forces
+        self.nm_transform = _nm_transformer()(n_beads).to(p.dtype)       # Simulator.to(precision) casts this buffer
+    positions_normal = property(lambda s: s.nm_transform.beads2normal(s.positions),
+                                lambda s, v: setattr(s, "positions", s.nm_transform.normal2beads(v)))
+    momenta_normal = property(lambda s: s.nm_transform.beads2normal(s.momenta),
+                              lambda s, v: setattr(s, "momenta", s.nm_transform.normal2beads(v)))
+
+
+def _pile_hook_class(noise):
+    """The reference's PILELocalThermostat as a plain class: SimulationHook's no-op stages, ThermostatHook's begin / end /
+    simulation-start stages and the two PILE-L methods, all lifted."""
+    env = {"torch": _TorchWithNoise(noise), "spk_units": _md_units()}
+    fns = _lift(_md_path("simulation_hooks", "basic_hooks.py"), "SimulationHook",
+                ("on_step_begin", "on_step_middle", "on_step_end", "on_step_finalize", "on_simulation_start", "on_simulation_end"), env)
+    fns.update(_lift(_md_path("simulation_hooks", "thermostats.py"), "ThermostatHook", ("on_simulation_start", "on_step_begin", "on_step_end"), env))
+    fns.update(_lift(_md_path("simulation_hooks", "thermostats_rpmd.py"), "PILELocalThermostat", ("_init_thermostat", "_apply_thermostat"), env))
+
+    def __init__(self, temperature_bath, time_constant, thermostat_centroid=True, damping_factor=1.0):
+        # the buffers of ThermostatHook.__init__ / PILELocalThermostat.__init__: python floats become float32 tensors
+        self.temperature_bath = torch.tensor(temperature_bath)
+        self.time_constant = torch.tensor(time_constant * env["spk_units"].fs)
+        self.thermostat_centroid = torch.tensor(thermostat_centroid)
+        self.damping_factor = torch.tensor(damping_factor)
+        self.initialized = False
+    fns["__init__"] = __init__
+    fns["to"] = lambda self, *a: self          # c1 / c2 / thermostat_factor are plain attributes: nn.Module.to leaves them
+    return type("LiftedPILELocalThermostat", (), fns)
+
+
+def _lifted_ring_polymer(n_beads, omega, dt):
+    """Namespace with the state of the reference's RingPolymer and its lifted ``_init_propagator`` / ``_main_step`` / ``half_step``."""
+    import types
+    env = {"torch": torch, "np": np}
+    fns = _lift(_md_path("integrators.py"), "RingPolymer", ("_init_propagator", "_main_step"), env)
+    fns.update(_lift(_md_path("integrators.py"), "Integrator", ("half_step", "main_step"), env))
+    me = types.SimpleNamespace(n_beads=n_beads, omega=omega, time_step=dt)
+    me.omega_normal, me.propagator = fns["_init_propagator"](me)
+    me._main_step = lambda system: fns["_main_step"](me, system)
+    me.main_step = lambda system: fns["main_step"](me, system)
+    me.half_step = lambda system: fns["half_step"](me, system)
+    return me
+
+
+def pile_masses_and_momenta(n_beads):
+    """7 atoms, masses in [1, 16] with one hydrogen-to-heavy pair (1.008 and 200), thermal-scale momenta (float64)."""
+    from schnetpack_amd import md as MD
+    g = torch.Generator().manual_seed(100 + n_beads)
+    m = torch.rand(1, 7, 1, generator=g, dtype=torch.float64) * 15 + 1
+    m[0, 0, 0], m[0, 1, 0] = 1.008, 200.0
+    p = torch.randn(n_beads, 7, 3, generator=g, dtype=torch.float64) * (m * MD.KB_MD * n_beads * PILE_T).sqrt()
+    return m, p
+
+
+def md_pile_arrays():
+    """tests/golden/md_pile.npz: the lifted ``RingPolymer._init_propagator`` (omega_normal), ``PILELocalThermostat._init_thermostat``
+    (c1, c2, thermostat_factor -- float32, the reference's natural dtype: omega_normal is a float32 buffer) and ``_apply_thermostat``
+    on seeded momenta with ``torch.randn_like`` returning ``md_oracle.pile_noise(n_beads, 7, seed, step, which)``, once with a
+    float32 system (``f32_``) and once with a float64 system (``f64_``; the coefficients stay float32 as in the reference), plus
+    the reference's NormalModeTransformer matrix.  Unit constants: the project's (stored), NOT pinned here."""
+    import types
+    from oracle import md_oracle as MDO
+    u = _md_units()
+    arrs = {"n_beads": np.array(PILE_BEADS), "sets": np.array([[o, dt, tau, float(c), d] for o, dt, tau, c, d in PILE_SETS]),
+            "temperature": PILE_T, "seed": np.uint64(PILE_SEED), "step": PILE_STEP, "which": PILE_WHICH,
+            "unit_kB": u.kB, "unit_fs": u.fs, "unit_hbar": u.hbar}
+    for nb in PILE_BEADS:
+        m, p = pile_masses_and_momenta(nb)
+        noise = MDO.pile_noise(nb, 7, PILE_SEED, PILE_STEP, PILE_WHICH)
+        arrs.update({"b%d_C" % nb: _nm_transformer()(nb).c_transform.numpy(), "b%d_m" % nb: m.numpy(), "b%d_p" % nb: p.numpy()})
+        for s, (omega, dt, tau_fs, centroid, damping) in enumerate(PILE_SETS):
+            integ = _lifted_ring_polymer(nb, omega, dt)
+            t = "b%d_s%d_" % (nb, s)
+            for tag, dtype in (("f32", torch.float32), ("f64", torch.float64)):
+                th = _pile_hook_class([noise])(PILE_T, tau_fs, centroid, damping)
+                system = _RingSystem(None, p.to(dtype).clone(), m.to(dtype), nb)
+                sim = types.SimpleNamespace(integrator=integ, system=system, device=None, dtype=dtype)
+                th.on_simulation_start(sim)
+                th.on_step_end(sim)
+                if tag == "f32":
+                    assert th.c1.dtype == torch.float32 and system.momenta.dtype == torch.float32
+                    arrs.update({t + "omega_normal": integ.omega_normal.numpy(), t + "c1": th.c1.reshape(-1).numpy(),
+                                 t + "c2": th.c2.reshape(-1).numpy()})
+                assert th.thermostat_factor.dtype == dtype
+                arrs.update({t + tag + "_thermostat_factor": th.thermostat_factor.numpy(), t + tag + "_p_out": system.momenta.numpy()})
+    return arrs
+
+
+def md_verlet_arrays():
+    """tests/golden/md_verlet.npz: the lifted ``Integrator.half_step`` and ``VelocityVerlet._main_step`` (md/integrators.py:59-110)
+    on a seeded [3, 11, 3] float64 state: half step, main step, half step."""
+    import types
+    env = {"torch": torch}
+    half = _lift(_md_path("integrators.py"), "Integrator", ("half_step",), env)["half_step"]
+    main = _lift(_md_path("integrators.py"), "VelocityVerlet", ("_main_step",), env)["_main_step"]
+    g = torch.Generator().manual_seed(31)
+    R, p, F = (torch.randn(3, 11, 3, generator=g, dtype=torch.float64) for _ in range(3))
+    m = torch.rand(1, 11, 1, generator=g, dtype=torch.float64) * 15 + 1
+    me = types.SimpleNamespace(time_step=0.37)
+    st = types.SimpleNamespace(positions=R.clone(), momenta=p.clone(), forces=F, masses=m)
+    arrs = {"dt": me.time_step, "R": R.numpy(), "p": p.numpy(), "F": F.numpy(), "m": m.numpy()}
+    half(me, st)
+    arrs["p_half"] = st.momenta.numpy().copy()
+    main(me, st)
+    arrs["R_main"] = st.positions.numpy().copy()
+    half(me, st)
+    arrs["p_end"] = st.momenta.numpy().copy()
+    return arrs
+
+
+def sim_setup():
+    """The system of the ring-polymer trajectory fixture: 2 aspirin molecules x 4 beads, seeded SchNet weights, the starting
+    q0 / p0 of tests/test_gpu_md.py::test_rpmd_loop_conserves_ring_polymer_energy_and_follows_oracle."""
+    from oracle import nbl_oracle as NB
+    rep_p, head_p = O.init_schnet_params(), O.init_atomwise_params(128, seed=1)
+    b = S.molecule_batch("aspirin", 2, seed=2, jitter=0.02)
+    N, B = int(b["Z"].shape[0]), SIM["n_beads"]
+    masses = torch.where(b["Z"] == 1, 1.008, torch.where(b["Z"] == 6, 12.011, 15.999))
+    g = torch.Generator().manual_seed(3)
+    q0 = b["R"][None].repeat(B, 1, 1) + 0.03 * torch.randn(B, N, 3, generator=g)
+    p0 = 0.2 * torch.randn(B, N, 3, generator=g) * masses[None, :, None].sqrt()
+
+    def forces(q):           # per bead, exact lists, float64
+        out = []
+        for k in range(B):
+            i, j, _, off = NB.batch_neighbor_list(q[k].float(), b["idx_m"], None, None, 5.0)
+            bb = dict(b, R=q[k], idx_i=i, idx_j=j, offsets=off.double())
+            out.append(O.energy_and_forces("schnet", rep_p, head_p, bb, 3, dtype=torch.float64)["forces"])
+        return torch.stack(out)
+
+    return dict(b=b, rep_p=rep_p, head_p=head_p, masses=masses, q0=q0, p0=p0, forces=forces)
+
+
+def sim_oracle_trajectory(setup, c1, c2, order="reference"):
+    """The NVT ring-polymer step of tests/test_gpu_pimd.py:110-116 through ``oracle/md_oracle.py`` (float64) with the thermostat
+    coefficients given.  ``order``: "reference" (thermostat, kick, main step, forces, kick, thermostat), or one of the two
+    wrong orders the fixture must tell apart: "after_first_kick" (begin-of-step thermostat after the first kick) and
+    "before_second_kick" (end-of-step thermostat before the second kick).  Returns q, p after every step."""
+    from oracle import md_oracle as MDO
+    from schnetpack_amd import md as MD
+    B, dt, seed = SIM["n_beads"], SIM["dt"], SIM["seed"]
+    N = int(setup["q0"].shape[1])
+    C = MDO.normal_mode_matrix(B)
+    _, prop = MDO.ring_polymer_propagator(B, SIM["omega"], dt)
+    kT = MD.KB_MD * B * SIM["T"]
+    q, p, m = setup["q0"].double(), setup["p0"].double(), setup["masses"].double()[None, :, None]
+    F = setup["forces"](q)
+    qs, ps = [], []
+    for step in range(SIM["n_steps"]):
+        th = lambda p, which: MDO.pile_apply(p, m, C, c1, c2, kT, MDO.pile_noise(B, N, seed, step, which))
+        if order == "after_first_kick":
+            p = th(MDO.half_step(p, F, dt), 0)
+        else:
+            p = MDO.half_step(th(p, 0), F, dt)
+        q, p = MDO.ring_polymer_main_step(q, p, m, C, prop)
+        F = setup["forces"](q)
+        if order == "before_second_kick":
+            p = MDO.half_step(th(p, 1), F, dt)
+        else:
+            p = th(MDO.half_step(p, F, dt), 1)
+        qs.append(q)
+        ps.append(p)
+    return torch.stack(qs), torch.stack(ps)
+
+
+def _rel(a, b):
+    return float((a - b).abs().max() / b.abs().max())
+
+
+def md_simulate_arrays():
+    """tests/golden/md_simulate.npz: the lifted ``Simulator.simulate`` (md/simulator.py:93-161) for 6 steps with the lifted
+    RingPolymer integrator, the lifted PILE-L thermostat and a recording hook (in this order), a float64 system and a calculator
+    stand-in that returns ``oracle/spk_oracle.py`` SchNet forces in float64; noise = ``md_oracle.pile_noise(seed, step, which)``.
+    Stores q, p after every step, the event order of the first step, the reference's (float32) thermostat coefficients and the
+    end states of two WRONG step orders integrated through ``md_oracle`` -- each must be at least 100x the GPU test's tolerance
+    away from the reference trajectory, or the fixture could not tell the orders apart.  Unit constants: the project's, NOT pinned."""
+    import types
+    from contextlib import nullcontext
+    from oracle import md_oracle as MDO
+    setup = sim_setup()
+    B, n_steps, dt = SIM["n_beads"], SIM["n_steps"], SIM["dt"]
+    N = int(setup["q0"].shape[1])
+    events = []
+    noise = [MDO.pile_noise(B, N, SIM["seed"], step, which) for step in range(n_steps) for which in (0, 1)]
+    th = _pile_hook_class(noise)(SIM["T"], SIM["tau_fs"])
+    lifted_apply = type(th)._apply_thermostat
+
+    def logged_apply(self, simulator):
+        events.append("thermostat")
+        lifted_apply(self, simulator)
+    type(th)._apply_thermostat = logged_apply
+
+    class Recorder:
+        def __init__(self, tag):
+            self.tag = tag
+        def __getattr__(self, name):
+            if not name.startswith("on_"):
+                raise AttributeError(name)
+            return lambda simulator: events.append(name[3:] + " " + self.tag)
+    traj_q, traj_p = [], []
+
+    class Snapshot(Recorder):
+        def on_step_finalize(self, simulator):
+            events.append("step_finalize " + self.tag)
+            traj_q.append(simulator.system.positions.clone())
+            traj_p.append(simulator.system.momenta.clone())
+
+    integ = _lifted_ring_polymer(B, SIM["omega"], dt)
+    half, main = integ.half_step, integ.main_step
+    integ.half_step = lambda system: (events.append("half_step"), half(system))[1]
+    integ.main_step = lambda system: (events.append("main_step"), main(system))[1]
+    system = _RingSystem(setup["q0"].double(), setup["p0"].double(), setup["masses"].double()[None, :, None], B)
+    assert system.positions.dtype == torch.float64
+
+    def calculate(sysm):
+        events.append("calculate")
+        sysm.forces = setup["forces"](sysm.positions)
+    sim = types.SimpleNamespace(system=system, integrator=integ, calculator=types.SimpleNamespace(calculate=calculate),
+                                simulator_hooks=[th, Snapshot("recorder")], step=0, effective_steps=0, n_steps=None, progress=False,
+                                gradients_required=False, device=None, dtype=torch.float64)
+    simulate = _lift(_md_path("simulator.py"), "Simulator", ("simulate",), {"torch": torch, "nullcontext": nullcontext, "trange": None})["simulate"]
+    simulate(sim, n_steps)
+    assert sim.step == n_steps and len(traj_q) == n_steps and not type(th)._apply_thermostat is lifted_apply
+    q_ref, p_ref = torch.stack(traj_q), torch.stack(traj_p)
+    c1, c2 = th.c1.reshape(-1), th.c2.reshape(-1)
+    assert c1.dtype == torch.float32 and float(c1[0]) <= 0.98, c1
+    per_step = (len(events) - 3) // n_steps          # initial calculate, simulation_start, ..., simulation_end
+    first = events[:2] + events[2:2 + per_step] + events[-1:]
+    # sensitivity: the two wrong orders, through the oracle with the SAME coefficients
+    arrs = {"n_beads": B, "n_steps": n_steps, "dt": dt, "omega": SIM["omega"], "tau_fs": SIM["tau_fs"], "temperature": SIM["T"],
+            "seed": np.uint64(SIM["seed"]), "q0": setup["q0"].numpy(), "p0": setup["p0"].numpy(), "masses": setup["masses"].numpy(),
+            "c1": c1.numpy(), "c2": c2.numpy(), "q": q_ref.numpy(), "p": p_ref.numpy(), "events_first_step": np.array(first),
+            "weights_checksum": checksum(setup["rep_p"]) + checksum(setup["head_p"]),
+            "unit_kB": _md_units().kB, "unit_fs": _md_units().fs, "tol_q": SIM_TOL_Q, "tol_p": SIM_TOL_P}
+    for order in ("after_first_kick", "before_second_kick"):
+        qw, pw = sim_oracle_trajectory(setup, c1, c2, order)
+        dq, dp = _rel(qw[-1], q_ref[-1]), _rel(pw[-1], p_ref[-1])
+        print("  wrong order %-18s end state: positions %.3e (tol %.0e), momenta %.3e (tol %.0e)" % (order, dq, SIM_TOL_Q, dp, SIM_TOL_P))
+        assert dq >= 100 * SIM_TOL_Q and dp >= 100 * SIM_TOL_P, (order, dq, dp)
+        arrs.update({"wrong_%s_q" % order: qw[-1].numpy(), "wrong_%s_p" % order: pw[-1].numpy()})
+    return arrs
+
+
+def fold_system():
+    """System stand-in for the replica folding: 2 replicas x (aspirin, ethanol), different cells, mixed pbc."""
+    import types
+    Z = torch.tensor(S.ASPIRIN_Z + S.ETHANOL_Z)
+    R = torch.cat([torch.tensor(S.ASPIRIN_R), torch.tensor(S.ETHANOL_R)]).float()
+    n_atoms = torch.tensor([len(S.ASPIRIN_Z), len(S.ETHANOL_Z)])
+    cells = torch.tensor([[[12.0, 0.0, 0.0], [1.5, 11.0, 0.0], [0.0, -0.5, 13.0]], [[9.0, 0.0, 0.0], [0.0, 9.5, 0.0], [0.0, 0.0, 30.0]]])
+    pbc = torch.tensor([[True, True, True], [True, True, False]])
+    return types.SimpleNamespace(n_replicas=2, n_molecules=2, total_n_atoms=int(Z.shape[0]), device=torch.device("cpu"), atom_types=Z,
+                                 n_atoms=n_atoms, index_m=torch.repeat_interleave(torch.arange(2), n_atoms),
+                                 positions=R[None].repeat(2, 1, 1), cells=cells[None].repeat(2, 1, 1, 1), pbc=pbc[None])
+
+
+def md_fold_arrays():
+    """tests/golden/md_fold.npz: the lifted ``MDCalculator._get_system_molecules`` (md/calculators/base_calculator.py:154-194) on
+    ``fold_system()``; the one-replica inputs are stored beside the folded batch."""
+    import importlib.util
+    import types
+    spec = importlib.util.spec_from_file_location("_ref_properties", os.path.join(refshim.REF_SRC, "schnetpack", "properties.py"))
+    props = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(props)
+    fold = _lift(_md_path("calculators", "base_calculator.py"), "MDCalculator", ("_get_system_molecules",), {"torch": torch, "properties": props})
+    system = fold_system()
+    out = fold["_get_system_molecules"](types.SimpleNamespace(position_conversion=1.0), system)
+    arrs = {"in_Z": system.atom_types.numpy(), "in_n_atoms": system.n_atoms.numpy(), "in_idx_m": system.index_m.numpy(),
+            "in_positions": system.positions[0].numpy(), "in_cells": system.cells[0].numpy(), "in_pbc": system.pbc[0].numpy(),
+            "n_replicas": system.n_replicas}
+    names = {props.Z: "Z", props.n_atoms: "n_atoms", props.idx_m: "idx_m", props.R: "positions", props.cell: "cells", props.pbc: "pbc"}
+    assert set(out) == set(names)
+    arrs.update({names[k]: v.numpy() for k, v in out.items()})
+    arrs["keys"] = np.array(sorted(out))
+    return arrs
+
+
+def md_arrays(name):
+    return {"md_pile": md_pile_arrays, "md_verlet": md_verlet_arrays, "md_simulate": md_simulate_arrays, "md_fold": md_fold_arrays}[name]()
+
+
+def save_npz_reproducible(path, arrs):
+    """An .npz whose bytes depend on the arrays alone (numpy's own writer stamps every member with the current time)."""
+    import io
+    import zipfile
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED) as zf:
+        for k, v in arrs.items():
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.asanyarray(v), allow_pickle=False)
+            info = zipfile.ZipInfo(k + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            zf.writestr(info, buf.getvalue())
+
+
+def md_step_goldens(names=MD_FIXTURES):
+    for name in names:
+        arrs = md_arrays(name)
+        path = os.path.join(OUT, name + ".npz")
+        save_npz_reproducible(path, arrs)
+        print("wrote %s.npz: %d arrays, %d bytes" % (name, len(arrs), os.path.getsize(path)))
+
+
 if __name__ == "__main__":
-    if len(sys.argv) > 1 and sys.argv[1] == "collate":
+    if len(sys.argv) > 1 and all(a in MD_FIXTURES for a in sys.argv[1:]):
+        md_step_goldens(sys.argv[1:])
+    elif len(sys.argv) > 1 and sys.argv[1] == "collate":
         collate_goldens(refshim.load())
     elif len(sys.argv) > 1 and sys.argv[1] == "deep":
         deep_model_goldens(refshim.load())
@@ -436,3 +817,4 @@ if __name__ == "__main__":
         deep_bessel_goldens(refshim.load())
         trained_model_goldens(refshim.load())
         collate_goldens(refshim.load())
+        md_step_goldens()

@@ -1,7 +1,8 @@
 """CPU restatement of the MD steps on the path's edge.  TEST
 INFRASTRUCTURE ONLY.  Plain torch (fp64 in the tests), each function citing the reference lines.
 Pinned by tests/golden/md_ring_polymer.npz, which oracle/make_golden.py produces by executing the
-reference's own ``RingPolymer._init_propagator`` / ``_main_step`` and ``NormalModeTransformer``.
+reference's own ``RingPolymer._init_propagator`` / ``_main_step`` and ``NormalModeTransformer``, and by md_pile.npz / md_verlet.npz /
+md_simulate.npz (its lifted PILE-L thermostat, Verlet steps and ``Simulator.simulate`` loop; tests/test_md_reference.py).
 """
 import math
 
@@ -93,7 +94,7 @@ def pile_apply(p: Tensor, masses: Tensor, C: Tensor, c1: Tensor, c2: Tensor, kB_
 
 def philox4x32_10(c0, c1, c2, c3, k0, k1):
     """Philox-4x32-10 (Salmon et al., SC'11) on numpy uint32 arrays / scalars: the counter-based generator of
-    spk_md_pile_f32 restated (no reference counterpart -- the reference draws torch.randn_like)."""
+    spk_md_pile_f32 restated (no reference counterpart -- the reference draws torch.randn_like; held to the published Random123 known answers)."""
     import numpy as np
     c0, c1, c2, c3 = (np.asarray(x, dtype=np.uint64) & 0xFFFFFFFF for x in (c0, c1, c2, c3))
     k0, k1 = np.uint64(k0) & np.uint64(0xFFFFFFFF), np.uint64(k1) & np.uint64(0xFFFFFFFF)

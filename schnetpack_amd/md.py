@@ -16,7 +16,7 @@ import torch
 from . import _lib
 from ._lib import check, fptr, lib, stream
 
-__all__ = ["PILELocalThermostat", "pile_matrices", "VelocityVerlet", "RingPolymer", "NVESimulation", "RPMDSimulation", "MDState", "normal_mode_matrix", "ring_polymer_propagator", "ring_polymer_matrices",
+__all__ = ["PILELocalThermostat", "pile_coefficients", "pile_matrices", "VelocityVerlet", "RingPolymer", "NVESimulation", "RPMDSimulation", "MDState", "fold_replicas", "normal_mode_matrix", "ring_polymer_propagator", "ring_polymer_matrices",
            "KB_MD", "HBAR_MD", "FS_MD"]
 
 # reference MD internal units (kJ/mol, nm, Dalton): time unit = 1 ps (units.py:10-40)
@@ -171,19 +171,26 @@ def _ring_polymer_hip(q_all, p_all, masses, A, bead0, n_local, q_out=None, p_out
     return q_out, p_out
 
 
-def pile_matrices(n_beads: int, omega: float, time_step: float, time_constant: float, thermostat_centroid: bool = True,
-                  damping_factor: float = 1.0) -> torch.Tensor:
-    """M [2, B, B] = (C^T diag(c1) C, C^T diag(c2)) of the PILE-L thermostat (md/simulation_hooks/thermostats_rpmd.py:66-92):
-    gamma_k = 2 omega_k (centroid: 1 / time_constant) x damping factor, c1 = exp(-dt/2 gamma), c2 = sqrt(1 - c1^2); the
-    transform to normal modes, the scaling and the back-transform folded into bead-space matrices (float64 -> float32)."""
-    C = normal_mode_matrix(n_beads)
+def pile_coefficients(n_beads: int, omega: float, time_step: float, time_constant: float, thermostat_centroid: bool = True,
+                      damping_factor: float = 1.0):
+    """(c1 [B], c2 [B]) of the PILE-L thermostat (md/simulation_hooks/thermostats_rpmd.py:66-92), float64: gamma_k = 2 omega_k
+    (centroid: 1 / time_constant) x damping factor, c1 = exp(-dt/2 gamma), c2 = sqrt(1 - c1^2).  The reference evaluates this in
+    float32, where 1 - c1^2 cancels; tests/golden/md_pile.npz holds its values and tests/test_md_reference.py the bound."""
     on = 2.0 * omega * torch.sin(torch.arange(n_beads).float() * math.pi / n_beads)
     gamma = 2.0 * on.double()
     if thermostat_centroid:
         gamma[0] = 1.0 / time_constant
     gamma = gamma * damping_factor
     c1 = torch.exp(-0.5 * time_step * gamma)
-    c2 = torch.sqrt(1.0 - c1 ** 2)
+    return c1, torch.sqrt(1.0 - c1 ** 2)
+
+
+def pile_matrices(n_beads: int, omega: float, time_step: float, time_constant: float, thermostat_centroid: bool = True,
+                  damping_factor: float = 1.0) -> torch.Tensor:
+    """M [2, B, B] = (C^T diag(c1) C, C^T diag(c2)) with the ``pile_coefficients``: the transform to normal modes, the scaling
+    and the back-transform of the PILE-L thermostat folded into bead-space matrices (float64 -> float32)."""
+    C = normal_mode_matrix(n_beads)
+    c1, c2 = pile_coefficients(n_beads, omega, time_step, time_constant, thermostat_centroid, damping_factor)
     return torch.stack([C.t() @ torch.diag(c1) @ C, C.t() @ torch.diag(c2)]).float().contiguous()
 
 
@@ -475,6 +482,25 @@ class NVESimulation:
         return float(self.energy.sum() + self.kinetic_energy())
 
 
+def fold_replicas(inputs, n_beads: int):
+    """``n_beads`` replicas of a batch folded into the batch dimension, replica-major, as the reference's
+    ``MDCalculator._get_system_molecules`` does (md/calculators/base_calculator.py:154-194): atom types, atom counts, cells and
+    pbc repeated, ``idx_m`` of replica r shifted by ``r * n_molecules``.  Every replica starts at the positions given."""
+    from . import properties as P
+    B = int(n_beads)
+    n_mol = int(inputs[P.n_atoms].shape[0])
+    rep = dict(inputs)
+    rep[P.R] = inputs[P.R].detach().float().repeat(B, 1)
+    rep[P.Z] = inputs[P.Z].repeat(B)
+    rep[P.idx_m] = (inputs[P.idx_m][None, :] + n_mol * torch.arange(B, device=inputs[P.idx_m].device)[:, None]).reshape(-1)
+    rep[P.n_atoms] = inputs[P.n_atoms].repeat(B)
+    if inputs.get(P.cell) is not None:
+        rep[P.cell] = inputs[P.cell].reshape(-1, 3, 3).repeat(B, 1, 1)
+    if inputs.get(P.pbc) is not None:
+        rep[P.pbc] = inputs[P.pbc].reshape(-1, 3).repeat(B, 1).reshape(-1)
+    return rep
+
+
 class RPMDSimulation(NVESimulation):
     """Ring-polymer MD (md/integrators.py:113-229) of ``n_beads`` replicas of ONE batch of systems: the beads are folded
     into the batch dimension exactly as the reference does (md/calculators/base_calculator.py:166-183), so one force call
@@ -520,16 +546,7 @@ class RPMDSimulation(NVESimulation):
         self._dist = self._world > 1 or (group is not None and os.environ.get("SPK_MD_FORCE_COLLECTIVES") == "1")
         self.n_local = B = hi - self._lo                      # beads in THIS rank's batch
         N = int(inputs[P.R].shape[0])
-        n_mol = int(inputs[P.n_atoms].shape[0])
-        rep = dict(inputs)
-        rep[P.R] = inputs[P.R].detach().float().repeat(B, 1)
-        rep[P.Z] = inputs[P.Z].repeat(B)
-        rep[P.idx_m] = (inputs[P.idx_m][None, :] + n_mol * torch.arange(B, device=inputs[P.idx_m].device)[:, None]).reshape(-1)
-        rep[P.n_atoms] = inputs[P.n_atoms].repeat(B)
-        if inputs.get(P.cell) is not None:
-            rep[P.cell] = inputs[P.cell].reshape(-1, 3, 3).repeat(B, 1, 1)
-        if inputs.get(P.pbc) is not None:
-            rep[P.pbc] = inputs[P.pbc].reshape(-1, 3).repeat(B, 1).reshape(-1)
+        rep = fold_replicas(inputs, B)
         self._n1 = N
         super().__init__(model, rep, masses, time_step, cutoff, cutoff_shell, use_graph, complete_list=complete_list)
 

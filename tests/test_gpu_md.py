@@ -270,7 +270,9 @@ def test_nve_periodic_water_box_painn_conserves_energy(dev):
 @pytest.mark.parametrize("n_beads,n_local,bead0", [(4, 4, 0), (8, 8, 0), (8, 2, 4), (5, 5, 0), (16, 10, 3)])
 def test_pile_thermostat_kernel_matches_oracle_with_the_same_noise(dev, n_beads, n_local, bead0):
     """spk_md_pile_f32 against the reference's formula (thermostats_rpmd.py:102-119, restated in oracle/md_oracle.py) fed the
-    SAME normal-mode noise -- the counter-based stream restated on the host (Philox-4x32-10 + Box-Muller)."""
+    SAME normal-mode noise -- the counter-based stream restated on the host (Philox-4x32-10 + Box-Muller).  The restatement itself is
+    held to the reference's own thermostat by tests/golden/md_pile.npz (tests/test_md_reference.py), the kernel to that fixture in
+    tests/test_gpu_md_reference.py."""
     from oracle import md_oracle as MDO
     from schnetpack_amd import md as MD
     g = torch.Generator().manual_seed(5)

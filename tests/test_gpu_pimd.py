@@ -70,6 +70,8 @@ def _sim(model, b, dev, n_beads, shell=1.0, **kw):
 
 
 def test_pimd_nvt_steps_follow_the_oracle_fed_the_same_noise(dev):
+    """The step sequence integrated below through ``md_oracle`` is the one tests/test_md_reference.py holds to six steps of the
+    reference's ``Simulator.simulate`` (tests/golden/md_simulate.npz); the coefficients to tests/golden/md_pile.npz."""
     from schnetpack_amd import md as MD
     rep_p, head_p = O.init_painn_params(), O.init_atomwise_params(128, seed=1)
     # amplify the (random-init) potential so that the forces matter next to the 300 K noise: head output x 400
