@@ -229,7 +229,10 @@ __global__ __launch_bounds__(256) void k_nbl_binoffsets(NblSys* __restrict__ sys
 }
 
 __global__ void k_nbl_bin(const float* __restrict__ R, const int64_t* __restrict__ idx_m, const NblSys* __restrict__ sys,
-                          int64_t N, int* __restrict__ key, int* __restrict__ ids, int* __restrict__ wrap) {
+                          int64_t N, int* __restrict__ key, int* __restrict__ ids, int* __restrict__ wrap,
+                          const int64_t* __restrict__ total) {
+  if (total[1] & 6) return;   // idx_m out of range / not ascending (k_nbl_atom0): sys[idx_m[a]] and the bin ids cannot be trusted
+                              // (key[] / ids[] stay unwritten then: the sort and k_nbl_bounds read them inside the workspace, nothing uses the result)
   for (int64_t a = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; a < N; a += (int64_t)gridDim.x * blockDim.x) {
     const NblSys& s = sys[idx_m ? idx_m[a] : 0];
     float f[3];
@@ -277,7 +280,9 @@ __global__ __launch_bounds__(256) void k_nbl_pairs(const float* __restrict__ R, 
                                                    const NblSys* __restrict__ sys, const int* __restrict__ key,
                                                    const int* __restrict__ ids_sorted, const int* __restrict__ wrap,
                                                    const int* __restrict__ bin_start, int64_t N, float cutoff,
-                                                   int* __restrict__ counts, NblOut out) {
+                                                   const int64_t* __restrict__ total, int* __restrict__ counts, NblOut out) {
+  if (total[1] & 6) return;   // bad idx_m: the host reports it after the count, nothing here may be indexed by it
+                              // (counts[] stays unwritten then: k_nbl_scan sums garbage, but the host checks flags 2 and 4 first and never uses E)
   const int lane = threadIdx.x & 63;
   const uint64_t lt = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
   const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
@@ -368,7 +373,7 @@ static int nbl_prepare(NblWs& w, const float* R, const int64_t* idx_m, const flo
   hipLaunchKernelGGL(k_nbl_atom0_fix, dim3(1), dim3(64), 0, stream, N, n_sys, w.atom0);
   hipLaunchKernelGGL(k_nbl_desc, dim3((unsigned)n_sys), dim3(256), 0, stream, R, cell, pbc, w.atom0, cutoff, w.sys, w.total);
   hipLaunchKernelGGL(k_nbl_binoffsets, dim3(1), dim3(256), 0, stream, w.sys, n_sys);
-  hipLaunchKernelGGL(k_nbl_bin, dim3(spk_grid_for(N, 256, spk_num_cus() * 8)), dim3(256), 0, stream, R, idx_m, w.sys, N, w.key, w.ids, w.wrap);
+  hipLaunchKernelGGL(k_nbl_bin, dim3(spk_grid_for(N, 256, spk_num_cus() * 8)), dim3(256), 0, stream, R, idx_m, w.sys, N, w.key, w.ids, w.wrap, w.total);
   SPK_LAUNCH_CHECK();
   size_t tmp = w.sort_tmp_bytes;
   // bin ids are < N + n_sys: sort only the bits that can be set
@@ -403,7 +408,7 @@ extern "C" int spk_nbl_count_f32(const float* R, const int64_t* idx_m, const flo
   if (rc != SPK_OK) return rc;
   NblOut out = {nullptr, nullptr, nullptr, nullptr, nullptr};
   hipLaunchKernelGGL((k_nbl_pairs<false>), dim3(spk_grid_for(n_atoms * 64, 256, spk_num_cus() * 32)), dim3(256), 0, stream,
-                     R, idx_m, w.sys, w.key, w.ids_sorted, w.wrap, w.bin_start, n_atoms, cutoff, w.counts, out);
+                     R, idx_m, w.sys, w.key, w.ids_sorted, w.wrap, w.bin_start, n_atoms, cutoff, w.total, w.counts, out);
   hipLaunchKernelGGL(k_nbl_scan, dim3(1), dim3(1024), 0, stream, w.counts, n_atoms, rowptr, w.total);
   SPK_LAUNCH_CHECK();
   int64_t host[2] = {0, 0};
@@ -430,7 +435,7 @@ extern "C" int spk_nbl_fill_f32(const float* R, const int64_t* idx_m, int64_t n_
   nbl_carve(w, (void*)workspace, n_atoms, n_sys);
   NblOut out = {idx_i, idx_j, shifts, offsets, rowptr};
   hipLaunchKernelGGL((k_nbl_pairs<true>), dim3(spk_grid_for(n_atoms * 64, 256, spk_num_cus() * 32)), dim3(256), 0, stream,
-                     R, idx_m, w.sys, w.key, w.ids_sorted, w.wrap, w.bin_start, n_atoms, cutoff, w.counts, out);
+                     R, idx_m, w.sys, w.key, w.ids_sorted, w.wrap, w.bin_start, n_atoms, cutoff, w.total, w.counts, out);
   SPK_LAUNCH_CHECK();
   return SPK_OK;
 }

@@ -33,6 +33,12 @@ def neighbor_list(R: torch.Tensor, cutoff: float, idx_m: Optional[torch.Tensor] 
     one system; cell [M,3,3] (or [3,3]); pbc [M,3] / [3M] / [3] bool.  Returns ``_idx_i``, ``_idx_j``
     (int64, idx_i ascending), ``_offsets`` [E,3] = S.cell, ``rowptr`` [N+1] int32 (CSR of idx_i) and,
     on request, ``shifts`` [E,3] int32.
+
+    Contract: atoms may lie anywhere (also many cells outside the cell along a periodic axis); S and
+    ``_offsets`` refer to the positions as given, not to wrapped ones.  The inequality is strict (a pair
+    at exactly the cutoff is outside).  Every pair (i, j, S) comes with (j, i, -S), whose offsets are the
+    negated offsets to the bit.  Systems without atoms are legal; ``idx_m`` outside [0, n_systems) or not
+    ascending raises :class:`SpkHipError`.
     """
     _lib.require_device(R)
     if R.dtype != torch.float32:
