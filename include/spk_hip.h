@@ -289,6 +289,44 @@ int spk_md_pile_f32(const float* p_all, const float* masses, const float* M, flo
                     uint64_t step, const int64_t* step_dev, int32_t which, int32_t n_beads, int64_t n_atoms,
                     int32_t bead0, int32_t n_local, float* p_out, void* stream);
 
+/* ------------------------------------------------------------------ md/simulation_hooks/thermostats.py, md/system.py
+ * Classical NVT thermostats on momenta p [n_replicas, n_atoms, 3] of a batch of n_mol molecules per replica: masses [n_atoms],
+ * idx_m [n_atoms] ascending (atoms of a molecule contiguous; molecules without atoms are legal anywhere), n_atoms_mol [n_mol] int64.
+ * fp32, no float atomics, no host synchronisation, no allocation, capturable.  err (device int32, may be NULL) is OR-ed with 1 when
+ * idx_m is not ascending and with 2 when an entry lies outside [0, n_mol); such an index is reported, never used as an address.
+ *
+ * spk_md_kinetic_f32          ke2[r, m] = sum over the atoms of molecule m of |p|^2 / mass = 2 E_kin        (system.py:374-386);
+ *                             chunk partials, then one wave per (replica, molecule): bit-identical from call to call, exactly 0
+ *                             for a molecule without atoms.  workspace: spk_md_kinetic_workspace_bytes (-1 on bad sizes).
+ * spk_md_nhc_global_f32       Nose-Hoover chain, one chain per (replica, molecule)       (thermostats.py:398-468, _propagate_thermostat):
+ *                             multi_step x integration_order Yoshida-Suzuki sub-steps sub_steps[k] = time_step w_k / multi_step
+ *                             (HOST array [integration_order], order 1, 3, 5 or 7) over velocities / forces [n_replicas * n_mol,
+ *                             chain_length], starting from ke2; degrees of freedom 3 n_atoms_mol[m]; thermostat masses
+ *                             dof link_mass (innermost) and link_mass = kT / omega^2 (:375-396).  scale [n_replicas * n_mol] is the
+ *                             factor for the momenta.  A molecule without atoms keeps its chain and gets scale 1.
+ *                             chain_length in [1, 16]; chain_length 1 as the reference: its outermost link is its innermost.
+ * spk_md_nhc_massive_f32      the same chain per momentum component (:348-354, :483-487): kinetic term p^2 / mass, one degree of
+ *                             freedom, all masses link_mass; propagates and scales p in ONE launch.  Chain state is link-major,
+ *                             velocities / forces [chain_length, n_replicas * n_atoms * 3].
+ * spk_md_berendsen_scale_f32  scale[r, m] = sqrt(1 + dt_over_tau (T0 / T - 1)), T = ke2 / (3 n_atoms_mol kB)
+ *                             (thermostats.py:172-189, system.py:407-421); 1 for a molecule without atoms or with ke2 == 0, where
+ *                             the reference divides by zero.
+ * spk_md_scale_molecules_f32  p[r, a, :] *= scale[r, idx_m[a]]: system.expand_atoms (system.py:245-255) and the product of
+ *                             thermostats.py:187-189 / :508-511, shared by the global chain and Berendsen. */
+int64_t spk_md_kinetic_workspace_bytes(int64_t n_replicas, int64_t n_atoms, int64_t n_mol);
+int spk_md_kinetic_f32(const float* p, const float* masses, const int64_t* idx_m, int64_t n_replicas, int64_t n_atoms,
+                       int64_t n_mol, float* ke2, int32_t* err, void* workspace, void* stream);
+int spk_md_nhc_global_f32(const float* ke2, const int64_t* n_atoms_mol, int64_t n_replicas, int64_t n_mol,
+                          int32_t chain_length, int32_t multi_step, int32_t integration_order, const float* sub_steps,
+                          float kT, float link_mass, float* velocities, float* forces, float* scale, void* stream);
+int spk_md_nhc_massive_f32(float* p, const float* masses, int64_t n_replicas, int64_t n_atoms, int32_t chain_length,
+                           int32_t multi_step, int32_t integration_order, const float* sub_steps, float kT,
+                           float link_mass, float* velocities, float* forces, void* stream);
+int spk_md_berendsen_scale_f32(const float* ke2, const int64_t* n_atoms_mol, int64_t n_replicas, int64_t n_mol,
+                               float dt_over_tau, float temperature_bath, float kB, float* scale, void* stream);
+int spk_md_scale_molecules_f32(float* p, const float* scale, const int64_t* idx_m, int64_t n_replicas, int64_t n_atoms,
+                               int64_t n_mol, int32_t* err, void* stream);
+
 /* ------------------------------------------------------------------ atomistic/atomwise.py:69-88
  * The default output head, build_mlp(n_in, 1, n_layers=2) (nn/blocks.py:38-57) + sum over idx_m:
  *   y_n = w2 . act(W1 x_n + b1) + b2,   E[idx_m[n]] += y_n           (E [n_mol] is overwritten)

@@ -16,7 +16,8 @@ import torch
 from . import _lib
 from ._lib import check, fptr, lib, stream
 
-__all__ = ["PILELocalThermostat", "pile_coefficients", "pile_matrices", "VelocityVerlet", "RingPolymer", "NVESimulation", "RPMDSimulation", "MDState", "fold_replicas", "normal_mode_matrix", "ring_polymer_propagator", "ring_polymer_matrices",
+__all__ = ["BerendsenThermostat", "LangevinThermostat", "NHCThermostat", "NVTSimulation", "nhc_sub_steps", "langevin_coefficients", "YS_WEIGHTS",
+           "PILELocalThermostat","pile_coefficients", "pile_matrices", "VelocityVerlet", "RingPolymer", "NVESimulation", "RPMDSimulation", "MDState", "fold_replicas", "normal_mode_matrix", "ring_polymer_propagator", "ring_polymer_matrices",
            "KB_MD", "HBAR_MD", "FS_MD"]
 
 # reference MD internal units (kJ/mol, nm, Dalton): time unit = 1 ps (units.py:10-40)
@@ -259,6 +260,333 @@ class PILELocalThermostat:
         return state.momenta
 
 
+# ------------------------------------------------------------------------------------------------ classical NVT thermostats
+# Yoshida-Suzuki weights of the chain integrator (md/utils/thermostat_utils.py:18-44; Yoshida, Phys. Lett. A 150 (1990) 262).  The
+# reference has no entry for order 1; the trivial weight [1] is what a single unsplit sub-step is.
+YS_WEIGHTS = {
+    1: (1.0,),
+    3: (1.35120719195966, -1.70241438391932, 1.35120719195966),
+    5: (0.41449077179438, 0.41449077179438, -0.65796308717750, 0.41449077179438, 0.41449077179438),
+    7: (0.78451361047756, 0.23557321335936, -1.17767998417887, 1.31518632068390, -1.17767998417887, 0.23557321335936, 0.78451361047756),
+}
+
+
+def nhc_sub_steps(time_step: float, multi_step: int = 2, integration_order: int = 3):
+    """``time_step * w_k / multi_step`` (thermostats.py:332-341), float64 list of ``integration_order`` entries."""
+    if integration_order not in YS_WEIGHTS:
+        raise ValueError("Order %d not supported for YS integration weights (1, 3, 5, 7)" % integration_order)
+    if multi_step < 1:
+        raise ValueError("multi_step must be at least 1")
+    return [float(time_step) * w / int(multi_step) for w in YS_WEIGHTS[integration_order]]
+
+
+class _ThermostatHip:
+    """The device side of the classical thermostats (csrc/spk_md_thermo.hip through the C ABI).  A ``compute_fn`` handed to a
+    thermostat is an object with these methods (tests/md_thermostat_oracle.py has a float64 host stand-in); every method works in
+    place on buffers the thermostat owns, so a captured graph replays it."""
+
+    @staticmethod
+    def workspace(n_rep, n_atoms, n_mol, device):
+        nbytes = int(lib().spk_md_kinetic_workspace_bytes(n_rep, n_atoms, n_mol))
+        if nbytes < 0:
+            raise _lib.SpkHipError("spk_md_kinetic_workspace_bytes: bad sizes")
+        return torch.empty(max(nbytes, 4) // 4, dtype=torch.int32, device=device)
+
+    @staticmethod
+    def kinetic(p, masses, idx_m, n_mol, ke2, err, ws):
+        n_rep, n_atoms = int(p.shape[0]), int(p.shape[1])
+        with torch.cuda.device(p.device):
+            check(lib().spk_md_kinetic_f32(fptr(p), fptr(masses), _lib.iptr(idx_m), n_rep, n_atoms, int(n_mol), fptr(ke2),
+                                           _lib.iptr(err, torch.int32), _lib.iptr(ws, torch.int32), stream()))
+
+    @staticmethod
+    def _steps(sub_steps):
+        import ctypes
+        return (ctypes.c_float * len(sub_steps))(*sub_steps)
+
+    @classmethod
+    def nhc_global(cls, ke2, n_atoms_mol, n_rep, chain_length, multi_step, order, sub_steps, kT, link_mass, vel, frc, scale):
+        with torch.cuda.device(ke2.device):
+            check(lib().spk_md_nhc_global_f32(fptr(ke2), _lib.iptr(n_atoms_mol), int(n_rep), int(n_atoms_mol.shape[0]), int(chain_length),
+                                              int(multi_step), int(order), cls._steps(sub_steps), float(kT), float(link_mass), fptr(vel),
+                                              fptr(frc), fptr(scale), stream()))
+
+    @classmethod
+    def nhc_massive(cls, p, masses, chain_length, multi_step, order, sub_steps, kT, link_mass, vel, frc):
+        with torch.cuda.device(p.device):
+            check(lib().spk_md_nhc_massive_f32(fptr(p), fptr(masses), int(p.shape[0]), int(p.shape[1]), int(chain_length), int(multi_step),
+                                               int(order), cls._steps(sub_steps), float(kT), float(link_mass), fptr(vel), fptr(frc), stream()))
+
+    @staticmethod
+    def berendsen_scale(ke2, n_atoms_mol, n_rep, dt_over_tau, temperature_bath, kb, scale):
+        with torch.cuda.device(ke2.device):
+            check(lib().spk_md_berendsen_scale_f32(fptr(ke2), _lib.iptr(n_atoms_mol), int(n_rep), int(n_atoms_mol.shape[0]), float(dt_over_tau),
+                                                   float(temperature_bath), float(kb), fptr(scale), stream()))
+
+    @staticmethod
+    def scale_molecules(p, scale, idx_m, n_mol, err):
+        with torch.cuda.device(p.device):
+            check(lib().spk_md_scale_molecules_f32(fptr(p), fptr(scale), _lib.iptr(idx_m), int(p.shape[0]), int(p.shape[1]), int(n_mol),
+                                                   _lib.iptr(err, torch.int32), stream()))
+
+
+class _ClassicalThermostat:
+    """What the three classical thermostats share (``ThermostatHook``, thermostats.py:41-146): bath temperature, time constant in fs,
+    the molecule layout of the batch and the per-molecule kinetic reduction.  ``fs`` / ``kb`` as in ``PILELocalThermostat``."""
+
+    ring_polymer = False
+
+    def __init__(self, temperature_bath: float, time_constant: float, compute_fn=None, fs: float = FS_MD, kb: float = KB_MD):
+        self.temperature_bath, self.time_constant = float(temperature_bath), float(time_constant) * float(fs)
+        self.kb = float(kb)
+        self._compute = compute_fn or self._default_compute()
+        self.time_step = None
+        self._idx_m = self._n_atoms_mol = None
+        self._ready = None
+
+    @staticmethod
+    def _default_compute():
+        return _ThermostatHip
+
+    def init(self, simulation_or_integrator, idx_m: Optional[torch.Tensor] = None, n_atoms: Optional[torch.Tensor] = None):
+        """``on_simulation_start``: the time step of the integrator and the molecule layout -- ``idx_m`` / ``n_atoms`` given, or
+        those of a simulation's batch (``inputs``), or ONE molecule of all atoms."""
+        sim = simulation_or_integrator
+        integrator = getattr(sim, "integrator", sim)
+        if getattr(integrator, "ring_polymer", False):
+            raise ValueError("%s is a classical thermostat (ring_polymer = False): ring-polymer states keep PILELocalThermostat through "
+                             "RPMDSimulation" % type(self).__name__)
+        self.time_step = float(integrator.time_step)
+        inputs = getattr(sim, "inputs", None)
+        if idx_m is None and inputs is not None:
+            from . import properties as P
+            idx_m, n_atoms = inputs[P.idx_m], inputs[P.n_atoms]
+        if idx_m is not None:
+            idx_m, n_atoms = idx_m.long().contiguous(), n_atoms.long().contiguous()
+            if idx_m.numel() > 1 and bool((idx_m[1:] < idx_m[:-1]).any()):
+                raise ValueError("idx_m must ascend (atoms of a molecule contiguous)")
+            if idx_m.numel() and (int(idx_m.min()) < 0 or int(idx_m.max()) >= int(n_atoms.shape[0])):
+                raise ValueError("idx_m outside [0, n_molecules)")
+        self._idx_m, self._n_atoms_mol = idx_m, n_atoms
+        self._ready = None
+        self._init_thermostat()
+        return self
+
+    def _init_thermostat(self):
+        pass
+
+    def _prepare(self, state):
+        """Buffers on the device of the state, allocated once (before any graph capture: ``NVTSimulation`` calls this at set-up)."""
+        p = state.momenta
+        key = (p.device, p.dtype, tuple(p.shape))
+        if self._ready == key:
+            return
+        if self.time_step is None:
+            raise RuntimeError("%s.init(simulation_or_integrator) has not been called" % type(self).__name__)
+        if p.dim() != 3 or p.shape[2] != 3:
+            raise ValueError("momenta must be [n_replicas, n_atoms, 3]")
+        n_rep, N = int(p.shape[0]), int(p.shape[1])
+        dev = p.device
+        if self._idx_m is None:
+            self._idx_m, self._n_atoms_mol = torch.zeros(N, dtype=torch.long), torch.tensor([N], dtype=torch.long)
+        if int(self._idx_m.shape[0]) != N:
+            raise ValueError("idx_m has %d entries for %d atoms" % (int(self._idx_m.shape[0]), N))
+        self._idx_m, self._n_atoms_mol = self._idx_m.to(dev), self._n_atoms_mol.to(dev)
+        self.n_replicas, self.n_atoms, self.n_molecules = n_rep, N, int(self._n_atoms_mol.shape[0])
+        self._masses = state.masses.reshape(-1).to(dev, p.dtype).contiguous()
+        if self._masses.numel() != N:
+            raise ValueError("masses: expected %d entries, got %d" % (N, self._masses.numel()))
+        self._ke2 = torch.zeros(n_rep * self.n_molecules, dtype=p.dtype, device=dev)
+        self._scale = torch.ones(n_rep * self.n_molecules, dtype=p.dtype, device=dev)
+        self._err = torch.zeros(1, dtype=torch.int32, device=dev)
+        self._ws = self._compute.workspace(n_rep, N, self.n_molecules, dev)
+        self._prepare_thermostat(p)
+        self._ready = key
+
+    def _prepare_thermostat(self, p):
+        pass
+
+    def _momenta(self, state):
+        p = state.momenta
+        if not p.is_contiguous():
+            raise ValueError("momenta must be contiguous (they are updated in place)")
+        self._prepare(state)
+        return p
+
+    def kinetic_energy2(self, state) -> torch.Tensor:
+        """``2 E_kin`` per replica and molecule, [n_replicas, n_molecules] (a view of the thermostat's buffer)."""
+        p = self._momenta(state)
+        self._compute.kinetic(p, self._masses, self._idx_m, self.n_molecules, self._ke2, self._err, self._ws)
+        return self._ke2.view(self.n_replicas, self.n_molecules)
+
+    def state_dict(self):
+        return {}
+
+    def load_state_dict(self, sd):
+        pass
+
+
+class BerendsenThermostat(_ClassicalThermostat):
+    """``BerendsenThermostat`` of the reference (thermostats.py:149-189): ``p <- p sqrt(1 + dt / tau (T0 / T - 1))`` per replica and
+    molecule.  Deviation: a molecule without atoms or without kinetic energy keeps its momenta (the reference yields NaN there)."""
+
+    def __init__(self, temperature_bath: float, time_constant: float, compute_fn=None, fs: float = FS_MD, kb: float = KB_MD):
+        super().__init__(temperature_bath, time_constant, compute_fn, fs, kb)
+
+    def apply(self, state, step: int = 0, which: int = 0, step_dev=None):
+        p = self._momenta(state)
+        c = self._compute
+        c.kinetic(p, self._masses, self._idx_m, self.n_molecules, self._ke2, self._err, self._ws)
+        c.berendsen_scale(self._ke2, self._n_atoms_mol, self.n_replicas, self.time_step / self.time_constant, self.temperature_bath, self.kb, self._scale)
+        c.scale_molecules(p, self._scale, self._idx_m, self.n_molecules, self._err)
+        return p
+
+
+def langevin_coefficients(time_step: float, time_constant: float):
+    """(c1, c2) of thermostats.py:226-237, float64: gamma = 1 / time_constant, c1 = exp(-dt/2 gamma), c2 = sqrt(1 - c1^2)."""
+    c1 = torch.exp(-0.5 * time_step * (torch.ones(1, dtype=torch.float64) / time_constant))
+    return c1, torch.sqrt(1.0 - c1 ** 2)
+
+
+class LangevinThermostat(_ClassicalThermostat):
+    """``LangevinThermostat`` of the reference (thermostats.py:192-261): ``p <- c1 p + sqrt(m kB T) c2 xi``.  No kernel of its own:
+    this is ``spk_md_pile_f32`` at ONE bead with M = ([[c1]], [[c2]]) and noise_scale = sqrt(kB T) -- the centroid mode of PILE-L
+    (whose friction 1 / time_constant does not depend on the ring-polymer frequency) is this thermostat.  Noise: that kernel's
+    Philox stream keyed by (seed, step, which); ``step_dev`` for graph replays.  ``compute_fn`` has the signature of ``_pile_hip``."""
+
+    def __init__(self, temperature_bath: float, time_constant: float, seed: int = 0, compute_fn=None, fs: float = FS_MD, kb: float = KB_MD):
+        super().__init__(temperature_bath, time_constant, compute_fn, fs, kb)
+        self.seed = int(seed)
+        self.M = None
+
+    @staticmethod
+    def _default_compute():
+        return _pile_hip
+
+    def _init_thermostat(self):
+        self.c1, self.c2 = langevin_coefficients(self.time_step, self.time_constant)
+        self.M = torch.stack([self.c1.reshape(1, 1), self.c2.reshape(1, 1)]).float().contiguous()
+        self.noise_scale = math.sqrt(self.kb * self.temperature_bath)
+
+    def _prepare(self, state):
+        p = state.momenta
+        key = (p.device, p.dtype, tuple(p.shape))
+        if self._ready == key:
+            return
+        if self.M is None:
+            raise RuntimeError("LangevinThermostat.init(simulation_or_integrator) has not been called")
+        n_rep, N = int(p.shape[0]), int(p.shape[1])
+        self._M_dev = self.M.to(p.device, p.dtype)
+        self._m_rep = state.masses.reshape(-1).to(p.device, p.dtype).repeat(n_rep).contiguous()
+        if self._m_rep.numel() != n_rep * N:
+            raise ValueError("masses: expected %d entries, got %d" % (N, self._m_rep.numel() // max(n_rep, 1)))
+        self._out = torch.empty(1, n_rep * N, 3, dtype=p.dtype, device=p.device)
+        self._ready = key
+
+    def apply(self, state, step: int = 0, which: int = 0, step_dev=None):
+        p = self._momenta(state)
+        # replicas of a classical system are independent: one bead of n_replicas x n_atoms atoms, every component its own counter
+        self._compute(p.view(1, -1, 3), self._m_rep, self._M_dev, self.noise_scale, self.seed, step, step_dev, which, 0, 1, self._out)
+        with torch.no_grad():
+            p.copy_(self._out.view(p.shape))
+        return p
+
+
+class NHCThermostat(_ClassicalThermostat):
+    """``NHCThermostat`` of the reference (thermostats.py:264-511): a Nose-Hoover chain per (replica, molecule), or with ``massive``
+    per momentum component, propagated by ``multi_step`` x ``integration_order`` Yoshida-Suzuki sub-steps.  The chain state lives in
+    device tensors owned by this object; ``state_dict`` / ``load_state_dict`` expose it under the reference's buffer names and
+    shapes (``velocities``, ``forces``, ``masses``: [n_replicas, n_molecules, 1, chain_length], massive [n_replicas, n_atoms, 3,
+    chain_length]) so that a run can be continued.  ``integration_order`` 1 (one unsplit sub-step) is accepted on top of the
+    reference's 3, 5, 7."""
+
+    def __init__(self, temperature_bath: float, time_constant: float, chain_length: int = 3, massive: bool = False, multi_step: int = 2,
+                 integration_order: int = 3, compute_fn=None, fs: float = FS_MD, kb: float = KB_MD):
+        super().__init__(temperature_bath, time_constant, compute_fn, fs, kb)
+        if int(chain_length) < 1:
+            raise ValueError("chain_length must be at least 1")
+        self.chain_length, self.massive = int(chain_length), bool(massive)
+        self.multi_step, self.integration_order = int(multi_step), int(integration_order)
+        nhc_sub_steps(1.0, self.multi_step, self.integration_order)          # validates both
+        self.frequency = 1.0 / self.time_constant
+        self.kb_temperature = self.temperature_bath * self.kb
+        self.link_mass = self.kb_temperature / self.frequency ** 2
+        self.sub_steps = None
+        self._pending = None
+
+    def _init_thermostat(self):
+        self.sub_steps = nhc_sub_steps(self.time_step, self.multi_step, self.integration_order)
+
+    def _prepare_thermostat(self, p):
+        L = self.chain_length
+        n = 3 * self.n_replicas * self.n_atoms if self.massive else self.n_replicas * self.n_molecules
+        shape = (L, n) if self.massive else (n, L)          # massive: link-major, what the kernel reads coalesced
+        self._vel = torch.zeros(shape, dtype=p.dtype, device=p.device)
+        self._frc = torch.zeros(shape, dtype=p.dtype, device=p.device)
+        if self._pending is not None:
+            sd, self._pending = self._pending, None
+            self.load_state_dict(sd)
+
+    def _public(self, t):
+        L = self.chain_length
+        if self.massive:
+            return t.t().reshape(self.n_replicas, self.n_atoms, 3, L)
+        return t.reshape(self.n_replicas, self.n_molecules, 1, L)
+
+    @property
+    def degrees_of_freedom(self) -> torch.Tensor:
+        if self.massive:
+            return torch.ones(self.n_replicas, self.n_atoms, 3, dtype=torch.float64)
+        return (3 * self._n_atoms_mol[None, :, None]).double().cpu()
+
+    @property
+    def masses(self) -> torch.Tensor:
+        """Thermostat masses (thermostats.py:375-396): dof kT / omega^2 for the innermost link, kT / omega^2 for the rest (float64)."""
+        dof = self.degrees_of_freedom
+        m = torch.full(tuple(dof.shape) + (self.chain_length,), self.link_mass, dtype=torch.float64)
+        m[..., 0] = dof * self.link_mass
+        return m.expand(self.n_replicas, *m.shape[1:]).contiguous()
+
+    def state_dict(self):
+        if self._ready is None:
+            raise RuntimeError("NHCThermostat: no chain state before the first application")
+        return {"velocities": self._public(self._vel).clone(), "forces": self._public(self._frc).clone(), "masses": self.masses}
+
+    def load_state_dict(self, sd):
+        """Chain velocities and forces of an earlier run, copied INTO the owned buffers (a captured graph keeps pointing at them);
+        before the first application they are kept and loaded when the buffers exist.  ``masses`` must be those of this thermostat."""
+        if self._ready is None and getattr(self, "_vel", None) is None:
+            self._pending = dict(sd)
+            return
+        want = tuple(self._public(self._vel).shape)
+        for name, buf in (("velocities", self._vel), ("forces", self._frc)):
+            t = sd[name]
+            if tuple(t.shape) != want:
+                raise ValueError("%s: expected shape %s, got %s" % (name, want, tuple(t.shape)))
+            t = t.to(buf.device, buf.dtype)
+            with torch.no_grad():
+                buf.copy_(t.reshape(-1, self.chain_length).t() if self.massive else t.reshape(-1, self.chain_length))
+        if "masses" in sd and not torch.allclose(sd["masses"].double().cpu(), self.masses, rtol=1e-5, atol=0.0):
+            raise ValueError("masses of the loaded chain state are not those of this thermostat (temperature / time constant differ)")
+
+    def apply(self, state, step: int = 0, which: int = 0, step_dev=None):
+        p = self._momenta(state)
+        c = self._compute
+        args = (self.chain_length, self.multi_step, self.integration_order, self.sub_steps, self.kb_temperature, self.link_mass, self._vel, self._frc)
+        if self.massive:
+            c.nhc_massive(p, self._masses, *args)
+        else:
+            c.kinetic(p, self._masses, self._idx_m, self.n_molecules, self._ke2, self._err, self._ws)
+            c.nhc_global(self._ke2, self._n_atoms_mol, self.n_replicas, *args, self._scale)
+            c.scale_molecules(p, self._scale, self._idx_m, self.n_molecules, self._err)
+        return p
+
+    @property
+    def scaling_factor(self) -> torch.Tensor:
+        """Factor of the last global application, [n_replicas, n_molecules]."""
+        return self._scale.view(self.n_replicas, self.n_molecules)
+
+
 class MDState:
     """Minimal stand-in for ``schnetpack.md.System`` (md/system.py): the tensors the integrators touch."""
 
@@ -480,6 +808,70 @@ class NVESimulation:
 
     def total_energy(self):
         return float(self.energy.sum() + self.kinetic_energy())
+
+
+class NVTSimulation(NVESimulation):
+    """Classical dynamics at a set temperature: ``NVESimulation`` with a thermostat hook at the begin and the end of every step, in
+    the order of the reference's ``Simulator.simulate`` (md/simulator.py:124-150):
+
+        thermostat  ->  kick + drift + skin test (1 kernel)  ->  force call  ->  kick  ->  thermostat  ->  step counter += 1
+
+    all of it ONE HIP-graph replay with ``use_graph=True``.  The skin / complete-list machinery is the parent's, untouched; a list
+    rebuild re-captures the step around the same chain-state and step-counter tensors.  ``thermostat``: ``BerendsenThermostat``,
+    ``LangevinThermostat`` or ``NHCThermostat`` (None: plain NVE).  The step counter is a device word incremented inside the
+    captured step (fresh Langevin noise per replay).  Ring-polymer thermostats, GLE and barostats are refused: ``RPMDSimulation``
+    keeps PILE-L, the other two are not built."""
+
+    def __init__(self, model, inputs, masses, time_step, cutoff, thermostat=None, cutoff_shell=1.0, use_graph=True, max_check_every=4,
+                 complete_list="auto", barostat=None):
+        if barostat is not None or getattr(thermostat, "pressure_control", False):
+            raise NotImplementedError("NVTSimulation: barostats (NPT) are not built; a strained cell changes the neighbour-list contract")
+        if thermostat is not None:
+            if getattr(thermostat, "ring_polymer", False):
+                raise ValueError("NVTSimulation integrates classical states: %s is a ring-polymer thermostat (use RPMDSimulation)"
+                                 % type(thermostat).__name__)
+            if not isinstance(thermostat, _ClassicalThermostat):
+                raise NotImplementedError("NVTSimulation: thermostat must be a BerendsenThermostat, LangevinThermostat or NHCThermostat "
+                                          "(GLE is not built), got %s" % type(thermostat).__name__)
+        self.thermostat = thermostat
+        super().__init__(model, inputs, masses, time_step, cutoff, cutoff_shell, use_graph, max_check_every, complete_list)
+
+    def _setup_state(self, R, masses):
+        super()._setup_state(R, masses)
+        self._stepc = torch.zeros(1, dtype=torch.int64, device=R.device)
+        kb = self.thermostat.kb if self.thermostat is not None else KB_MD
+        self._meter = _ClassicalThermostat(0.0, 1.0, kb=kb).init(self)
+        self._meter._prepare(self.state)
+        if self.thermostat is not None:          # buffers before the first capture
+            self.thermostat.init(self)
+            self.thermostat._prepare(self.state)
+
+    def _step_body(self):
+        th = self.thermostat
+        if th is not None:
+            th.apply(self.state, 0, 0, self._stepc)
+        super()._step_body()
+        if th is not None:
+            th.apply(self.state, 0, 1, self._stepc)
+        with torch.no_grad():
+            self._stepc.add_(1)
+
+    @property
+    def step_count(self) -> int:
+        return int(self._stepc.item())
+
+    def kinetic_energy(self) -> torch.Tensor:
+        """Kinetic energy per molecule, [n_molecules] (``spk_md_kinetic_f32``; ``System.kinetic_energy``, md/system.py:374-386)."""
+        return 0.5 * self._meter.kinetic_energy2(self.state).reshape(-1)
+
+    def temperature(self) -> torch.Tensor:
+        """Instantaneous temperature per molecule, [n_molecules] (md/system.py:407-421); 0 for a molecule without atoms."""
+        ke2 = self._meter.kinetic_energy2(self.state).reshape(-1)
+        n = self._meter._n_atoms_mol.to(ke2.dtype)
+        return torch.where(n > 0, ke2 / (3.0 * n.clamp_min(1.0) * self._meter.kb), torch.zeros_like(ke2))
+
+    def total_energy(self):
+        return float(self.energy.sum() + self.kinetic_energy().sum())
 
 
 def fold_replicas(inputs, n_beads: int):
