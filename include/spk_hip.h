@@ -327,6 +327,44 @@ int spk_md_berendsen_scale_f32(const float* ke2, const int64_t* n_atoms_mol, int
 int spk_md_scale_molecules_f32(float* p, const float* scale, const int64_t* idx_m, int64_t n_replicas, int64_t n_atoms,
                                int64_t n_mol, int32_t* err, void* stream);
 
+/* ------------------------------------------------------------------ md/simulation_hooks/thermostats_rpmd.py
+ * Ring-polymer thermostats in normal-mode space next to spk_md_pile_f32: p_all [n_beads, n_atoms, 3], masses [n_atoms], the beads
+ * [bead0, bead0 + n_local) of this rank written to p_out [n_local, n_atoms, 3] (p_out != p_all), n_beads <= 64.  idx_m / n_atoms_mol /
+ * err as for the classical thermostats above; the per-molecule sums are spk_md_kinetic_f32 on the centroid workspace.
+ *
+ * spk_md_rp_centroid_f32   p_c[a, c] = sum_b C[0][b] p_b = (sum_b p_b) / sqrt(n_beads), the centroid normal-mode momentum, and with
+ *                          xi_c != NULL the centroid noise xi_c [n_atoms, 3]: mode 0 of the Philox stream of spk_md_pile_f32 for the
+ *                          same (seed, step / step_dev, which).
+ * spk_md_rp_nhc_f32        NHCRingPolymerThermostat (:373-501) in ONE launch: p_nm[k] = sum_b C[k][b] p_b (C [n_beads, n_beads] =
+ *                          normal_mode_matrix), a Nose-Hoover chain per (mode, component) as in spk_md_nhc_massive_f32 with kinetic
+ *                          term p_nm^2 / mass, one degree of freedom, kT = n_beads kB T and every link mass link_masses[k] =
+ *                          kT / omega_k^2 (device array [n_beads]); p_out[b] = sum_k C[k][b] scale_k p_nm[k].  Chain state is
+ *                          link-major, velocities / forces [chain_length, n_beads, n_atoms * 3]; EVERY caller updates all modes (the
+ *                          kernel is deterministic: bead-parallel ranks hold identical state without an exchange).  scale_centroid
+ *                          [n_mol] != NULL (global centroid, local = False): mode 0 of atom a is multiplied by
+ *                          scale_centroid[idx_m[a]] (from spk_md_nhc_global_f32 on the centroid kinetic sums) instead, and the
+ *                          mode-0 rows of the chain state are left alone.  chain_length in [1, 16], order 1, 3, 5 or 7, sub_steps a
+ *                          HOST array as for spk_md_nhc_massive_f32.
+ * spk_md_pile_alpha_f32    alpha [n_mol] of the stochastic velocity rescaling of PILEGlobalThermostat (:147-208) per molecule: K = ke2[m]
+ *                          (centroid kinetic sum), S = noise2[m] (sum of xi_c^2), R1 = xi_c[first_atom[m], 0], g = one_minus_c1_kT / K,
+ *                          alpha^2 = c1 + S g + 2 R1 sqrt(c1 g), alpha = sqrt(alpha^2) sign(R1 + sqrt(c1 / g)).  A molecule without
+ *                          atoms or with K == 0 (the reference divides by zero) gets alpha = 1.
+ * spk_md_pile_global_f32   PILE-G application: spk_md_pile_f32 with M [2, n_beads, n_beads] built from c1[0] = c2[0] = 0 (same Philox
+ *                          counters: mode k >= 1 draws what it draws in spk_md_pile_f32) plus alpha[idx_m[a]] p_c / sqrt(n_beads). */
+int spk_md_rp_centroid_f32(const float* p_all, int32_t n_beads, int64_t n_atoms, float* p_c, float* xi_c, uint64_t seed,
+                           uint64_t step, const int64_t* step_dev, int32_t which, void* stream);
+int spk_md_rp_nhc_f32(const float* p_all, const float* masses, const float* C, const float* link_masses, int32_t n_beads,
+                      int64_t n_atoms, int32_t bead0, int32_t n_local, int32_t chain_length, int32_t multi_step,
+                      int32_t integration_order, const float* sub_steps, float kT, float* velocities, float* forces,
+                      const float* scale_centroid, const int64_t* idx_m, int64_t n_mol, int32_t* err, float* p_out, void* stream);
+int spk_md_pile_alpha_f32(const float* ke2, const float* noise2, const float* xi_c, const int64_t* n_atoms_mol,
+                          const int64_t* first_atom, int64_t n_mol, int64_t n_atoms, float c1_centroid, float one_minus_c1_kT,
+                          float* alpha, int32_t* err, void* stream);
+int spk_md_pile_global_f32(const float* p_all, const float* masses, const float* M, float noise_scale, uint64_t seed,
+                           uint64_t step, const int64_t* step_dev, int32_t which, int32_t n_beads, int64_t n_atoms,
+                           int32_t bead0, int32_t n_local, const float* p_c, const float* alpha, const int64_t* idx_m,
+                           int64_t n_mol, int32_t* err, float* p_out, void* stream);
+
 /* ------------------------------------------------------------------ atomistic/atomwise.py:69-88
  * The default output head, build_mlp(n_in, 1, n_layers=2) (nn/blocks.py:38-57) + sum over idx_m:
  *   y_n = w2 . act(W1 x_n + b1) + b2,   E[idx_m[n]] += y_n           (E [n_mol] is overwritten)

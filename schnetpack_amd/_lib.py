@@ -129,6 +129,12 @@ _PROTOS = {
     "spk_md_nhc_massive_f32": (ctypes.c_int, [c_f, c_f, c_i64, c_i64, c_i32, c_i32, c_i32, P(ctypes.c_float), ctypes.c_float, ctypes.c_float, c_f, c_f, c_f]),
     "spk_md_berendsen_scale_f32": (ctypes.c_int, [c_f, c_f, c_i64, c_i64, ctypes.c_float, ctypes.c_float, ctypes.c_float, c_f, c_f]),
     "spk_md_scale_molecules_f32": (ctypes.c_int, [c_f, c_f, c_f, c_i64, c_i64, c_i64, c_f, c_f]),
+    "spk_md_rp_centroid_f32": (ctypes.c_int, [c_f, c_i32, c_i64, c_f, c_f, ctypes.c_uint64, ctypes.c_uint64, c_f, c_i32, c_f]),
+    "spk_md_rp_nhc_f32": (ctypes.c_int, [c_f, c_f, c_f, c_f, c_i32, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, P(ctypes.c_float), ctypes.c_float, c_f, c_f, c_f, c_f,
+                                         c_i64, c_f, c_f, c_f]),
+    "spk_md_pile_alpha_f32": (ctypes.c_int, [c_f, c_f, c_f, c_f, c_f, c_i64, c_i64, ctypes.c_float, ctypes.c_float, c_f, c_f, c_f]),
+    "spk_md_pile_global_f32": (ctypes.c_int, [c_f, c_f, c_f, ctypes.c_float, ctypes.c_uint64, ctypes.c_uint64, c_f, c_i32, c_i32, c_i64, c_i32, c_i32, c_f, c_f, c_f,
+                                              c_i64, c_f, c_f, c_f]),
     "spk_pack_weight_f32": (ctypes.c_int, [c_f, c_i32, c_i32, c_i32, c_f, c_f]),
     "spk_schnet_packed_floats": (c_i64, [P(SchnetT)]),
     "spk_schnet_pack_weights_f32": (ctypes.c_int, [P(SchnetT), c_f, c_f]),

@@ -2,6 +2,7 @@
 // integrators fused, and the ring-polymer main step as one bead-mixing kernel.  HBM-bound; every
 // array is read and written once per step.
 #include "spk_common.h"
+#include "spk_md_common.h"
 #include <atomic>
 
 // p += 1/2 dt F                                   (md/integrators.py:59-70, Integrator.half_step)
@@ -158,27 +159,7 @@ extern "C" int spk_md_ring_polymer_step_f32(const float* q_all, const float* p_a
 // xi_k for all modes from the counter alone, so the only exchange of a thermostat application is the all-gather of the
 // momenta ("identical RNG streams"); the result does not depend on how beads are spread over ranks.
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void spk_philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t (&out)[4]) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n1 = (uint32_t)p1, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1, n3 = (uint32_t)p0;
-    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-// two standard normals from two 32-bit words (Box-Muller; u in (0, 1])
-__device__ __forceinline__ void spk_box_muller(uint32_t a, uint32_t b, float& n0, float& n1) {
-  const float u = ((float)(a >> 8) + 1.0f) * (1.0f / 16777216.0f);
-  const float v = (float)(b >> 8) * (1.0f / 16777216.0f);
-  const float r = sqrtf(-2.0f * logf(u));
-  float s, c;
-  sincosf(6.283185307179586f * v, &s, &c);
-  n0 = r * c; n1 = r * s;
-}
-
-#define PILE_CHUNK 8   // local beads per pass (accumulators per thread); more local beads = more passes, noise regenerated per pass
+// The per-component body (chunks of local beads, Philox counters) is spk_pile_component of spk_md_common.h, shared with PILE-G.
 __global__ void k_md_pile(const float* __restrict__ p_all, const float* __restrict__ masses, const float* __restrict__ M, float scale,
                           uint32_t seed_lo, uint32_t seed_hi, uint64_t step_host, const int64_t* __restrict__ step_dev, uint32_t which,
                           int B, int64_t n_atoms, int bead0, int n_local, float* __restrict__ p_out) {
@@ -189,33 +170,7 @@ __global__ void k_md_pile(const float* __restrict__ p_all, const float* __restri
   const int64_t n3 = 3 * n_atoms;
   for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < n3; t += (int64_t)gridDim.x * blockDim.x) {
     const float sm = sqrtf(masses[t / 3]) * scale;
-    for (int b0 = 0; b0 < n_local; b0 += PILE_CHUNK) {
-      float det[PILE_CHUNK], noi[PILE_CHUNK];
-#pragma unroll
-      for (int u = 0; u < PILE_CHUNK; ++u) { det[u] = 0.f; noi[u] = 0.f; }
-      for (int n = 0; n < B; ++n) {
-        const float pv = p_all[(int64_t)n * n3 + t];
-#pragma unroll
-        for (int u = 0; u < PILE_CHUNK; ++u)
-          if (b0 + u < n_local) det[u] = fmaf(sM[(bead0 + b0 + u) * B + n], pv, det[u]);
-      }
-      for (int k2 = 0; k2 < (B + 1) / 2; ++k2) {       // modes 2 k2 and 2 k2 + 1 from one Philox block
-        uint32_t w[4];
-        spk_philox4x32_10((uint32_t)t, (uint32_t)((uint64_t)t >> 32) ^ ((uint32_t)k2 << 8) ^ which, (uint32_t)step, (uint32_t)(step >> 32), seed_lo, seed_hi, w);
-        float x0, x1;
-        spk_box_muller(w[0], w[1], x0, x1);
-#pragma unroll
-        for (int u = 0; u < PILE_CHUNK; ++u)
-          if (b0 + u < n_local) {
-            const float* row = sM + B * B + (bead0 + b0 + u) * B;
-            noi[u] = fmaf(row[2 * k2], x0, noi[u]);
-            if (2 * k2 + 1 < B) noi[u] = fmaf(row[2 * k2 + 1], x1, noi[u]);
-          }
-      }
-#pragma unroll
-      for (int u = 0; u < PILE_CHUNK; ++u)
-        if (b0 + u < n_local) p_out[(int64_t)(b0 + u) * n3 + t] = det[u] + sm * noi[u];
-    }
+    spk_pile_component<false>(p_all, sM, sm, seed_lo, seed_hi, step, which, B, n3, t, bead0, n_local, 0.f, p_out);
   }
 }
 

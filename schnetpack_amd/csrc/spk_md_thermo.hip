@@ -10,16 +10,13 @@
 //   k_kin_mol     one wave per (replica, molecule): lane l sums the chunk partials l, l + 64, ... in order, then a fixed butterfly.
 //                 A 32 k-atom molecule is 500 partials over 64 lanes, 600 three-atom molecules are 600 waves.
 #include "spk_common.h"
+#include "spk_md_common.h"
 
 namespace {
 
 constexpr int kKinChunk = 64;
-constexpr int kMaxOrder = 7;
-constexpr int kMaxChain = 16;
 
 inline size_t thermo_align(size_t b) { return (b + 255) & ~(size_t)255; }
-
-struct YsSteps { float dt[kMaxOrder]; };
 
 // P[r, a] = sum over the atoms a .. of a's molecule inside a's chunk of |p_a|^2 / m_a, for every atom that starts such a segment.
 // idx_m is only ever COMPARED here and clamped into [-1, n_mol] before it bounds the molptr loop: a malformed index (descending,
@@ -72,39 +69,6 @@ __global__ __launch_bounds__(256) void k_kin_mol(const float* __restrict__ P, co
 #pragma unroll
   for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d, 64);
   if (lane == 0) ke2[w] = s;
-}
-
-// One multi_step x integration_order Yoshida-Suzuki pass over ONE chain held in registers (thermostats.py:398-468, operation for
-// operation): ke = the kinetic term of the chain, dof_kT = degrees of freedom x kB T, m0 / mq = thermostat mass of the innermost /
-// every other link.  Returns the factor the momenta are multiplied by.  LMAX bounds the unrolled loops; L <= LMAX.
-template <int LMAX>
-__device__ __forceinline__ float nhc_propagate(float (&v)[LMAX], float (&f)[LMAX], int L, float ke, float dof_kT, float kT, float m0, float mq,
-                                               int multi_step, int order, const YsSteps& ys) {
-  f[0] = (ke - dof_kT) / m0;
-  float scale = 1.0f;
-  for (int ms = 0; ms < multi_step; ++ms) {
-    for (int k = 0; k < order; ++k) {
-      const float ts = ys.dt[k];
-#pragma unroll
-      for (int c = 0; c < LMAX; ++c) if (c == L - 1) v[c] += 0.25f * f[c] * ts;            // outermost link
-#pragma unroll
-      for (int c = LMAX - 2; c >= 0; --c) if (c <= L - 2) {
-        const float coeff = expf(-0.125f * ts * v[c + 1]);
-        v[c] = v[c] * (coeff * coeff) + 0.25f * f[c] * coeff * ts;
-      }
-      scale *= expf(-0.5f * ts * v[0]);
-      f[0] = (scale * scale * ke - dof_kT) / m0;
-#pragma unroll
-      for (int c = 0; c < LMAX - 1; ++c) if (c <= L - 2) {
-        const float coeff = expf(-0.125f * ts * v[c + 1]);
-        v[c] = v[c] * (coeff * coeff) + 0.25f * f[c] * coeff * ts;
-        f[c + 1] = ((c == 0 ? m0 : mq) * v[c] * v[c] - kT) / mq;
-      }
-#pragma unroll
-      for (int c = 0; c < LMAX; ++c) if (c == L - 1) v[c] += 0.25f * f[c] * ts;
-    }
-  }
-  return scale;
 }
 
 // global form: one thread per (replica, molecule) chain; state [n_chains, L].  A molecule without atoms keeps its chain, scale = 1.
@@ -173,18 +137,7 @@ __global__ void k_scale_molecules(float* __restrict__ p, const float* __restrict
   if (bad && err) atomicOr(err, bad);
 }
 
-int check_chain(const char* who, int32_t chain_length, int32_t multi_step, int32_t order, const float* sub_steps, YsSteps* ys) {
-  SPK_CHECK_ARG(chain_length >= 1 && chain_length <= kMaxChain, "%s: chain_length must be in [1, %d]", who, kMaxChain);
-  SPK_CHECK_ARG(multi_step >= 1, "%s: multi_step must be at least 1", who);
-  SPK_CHECK_ARG(order == 1 || order == 3 || order == 5 || order == 7, "%s: integration_order must be 1, 3, 5 or 7", who);
-  SPK_CHECK_ARG(sub_steps != nullptr, "%s: null sub-step array", who);
-  for (int k = 0; k < kMaxOrder; ++k) ys->dt[k] = k < order ? sub_steps[k] : 0.f;
-  return SPK_OK;
-}
-
 }  // namespace
-
-#define SPK_TRY(expr) do { int _rc = (expr); if (_rc) return _rc; } while (0)
 
 extern "C" int64_t spk_md_kinetic_workspace_bytes(int64_t n_replicas, int64_t n_atoms, int64_t n_mol) {
   if (n_replicas < 0 || n_atoms < 0 || n_mol < 0) return -1;

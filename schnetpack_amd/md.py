@@ -17,7 +17,7 @@ from . import _lib
 from ._lib import check, fptr, lib, stream
 
 __all__ = ["BerendsenThermostat", "LangevinThermostat", "NHCThermostat", "NVTSimulation", "nhc_sub_steps", "langevin_coefficients", "YS_WEIGHTS",
-           "PILELocalThermostat","pile_coefficients", "pile_matrices", "VelocityVerlet", "RingPolymer", "NVESimulation", "RPMDSimulation", "MDState", "fold_replicas", "normal_mode_matrix", "ring_polymer_propagator", "ring_polymer_matrices",
+           "PILELocalThermostat", "PILEGlobalThermostat", "TRPMDThermostat", "NHCRingPolymerThermostat", "rp_nhc_frequencies", "pile_coefficients", "pile_matrices", "VelocityVerlet", "RingPolymer", "NVESimulation", "RPMDSimulation", "MDState", "fold_replicas", "normal_mode_matrix", "ring_polymer_propagator", "ring_polymer_matrices",
            "KB_MD", "HBAR_MD", "FS_MD"]
 
 # reference MD internal units (kJ/mol, nm, Dalton): time unit = 1 ps (units.py:10-40)
@@ -207,6 +207,23 @@ def _pile_hip(p_all, masses, M, noise_scale, seed, step, step_dev, which, bead0,
     return p_out
 
 
+def _apply_to_state(thermostat, state, step: int = 0, which: int = 0, step_dev=None, out=None):
+    """``apply`` of every ring-polymer thermostat: the momenta of all beads (bead-parallel: ONE all-gather over ``thermostat.group``)
+    go to ``thermostat.apply_beads``, which returns the thermostatted beads of this rank; they become ``state.momenta``."""
+    p = state.momenta
+    lo, hi, world = thermostat._range()
+    if world > 1:
+        import torch.distributed as dist
+        local = p.contiguous()
+        allb = torch.empty((world,) + tuple(local.shape), dtype=local.dtype, device=local.device)
+        dist.all_gather_into_tensor(allb.view(-1), local.view(-1), group=thermostat.group)
+        p_all = allb.reshape(thermostat.n_beads, p.shape[1], 3)
+    else:
+        p_all = p.contiguous()
+    state.momenta = thermostat.apply_beads(p_all, state.masses, lo, hi - lo, step, step_dev, which, out)
+    return state.momenta
+
+
 class PILELocalThermostat:
     """Mirror of the reference's ``PILELocalThermostat`` (md/simulation_hooks/thermostats_rpmd.py:33-119; constructor
     arguments and the two application points of md/simulation_hooks/thermostats.py:97-123) for the device ring polymer:
@@ -232,32 +249,40 @@ class PILELocalThermostat:
         self.M = None
         self._M_dev = None
 
-    def init(self, integrator: RingPolymer):
-        """``_init_thermostat``: coefficients from the normal-mode frequencies of the integrator."""
+    def init(self, integrator: RingPolymer, idx_m: Optional[torch.Tensor] = None, n_atoms: Optional[torch.Tensor] = None):
+        """``_init_thermostat``: coefficients from the normal-mode frequencies of the integrator.  The molecule layout is accepted
+        for the common signature of the ring-polymer thermostats; PILE-L couples nothing across atoms and does not use it."""
         self.n_beads = integrator.n_beads
-        self.M = pile_matrices(self.n_beads, integrator.omega, integrator.time_step, self.time_constant, self.thermostat_centroid,
-                               self.damping_factor)
+        self.M = self._matrices(integrator)
         self.noise_scale = math.sqrt(self.kb * self.n_beads * self.temperature_bath)
         self._range = integrator._bead_range if self.group is None else RingPolymer(integrator.time_step, self.n_beads, 1.0, omega=1.0,
                                                                                     group=self.group)._bead_range
         return self
 
+    def _matrices(self, integrator):
+        return pile_matrices(self.n_beads, integrator.omega, integrator.time_step, self.time_constant, self.thermostat_centroid,
+                             self.damping_factor)
+
     def apply(self, state, step: int = 0, which: int = 0, step_dev=None, out=None):
-        p = state.momenta
-        lo, hi, world = self._range()
-        n_local = hi - lo
-        if self._M_dev is None or self._M_dev.device != p.device:
-            self._M_dev = self.M.to(p.device)
-        if world > 1:
-            import torch.distributed as dist
-            local = p.contiguous()
-            allb = torch.empty((world,) + tuple(local.shape), dtype=local.dtype, device=local.device)
-            dist.all_gather_into_tensor(allb.view(-1), local.view(-1), group=self.group)
-            p_all = allb.reshape(self.n_beads, p.shape[1], 3)
-        else:
-            p_all = p.contiguous()
-        state.momenta = self._compute(p_all, state.masses, self._M_dev, self.noise_scale, self.seed, step, step_dev, which, lo, n_local, out)
-        return state.momenta
+        return _apply_to_state(self, state, step, which, step_dev, out)
+
+    def apply_beads(self, p_all, masses, bead0, n_local, step=0, step_dev=None, which=0, out=None):
+        """The one entry ``RPMDSimulation`` calls for every ring-polymer thermostat: the momenta of ALL beads [n_beads, n_atoms, 3]
+        in, the thermostatted beads [bead0, bead0 + n_local) out (``out`` or a new tensor; never ``p_all``)."""
+        if self._M_dev is None or self._M_dev.device != p_all.device:
+            self._M_dev = self.M.to(p_all.device)
+        return self._compute(p_all, masses, self._M_dev, self.noise_scale, self.seed, step, step_dev, which, bead0, n_local, out)
+
+    def prepare(self, p_all, masses):
+        """Device buffers before a graph capture; PILE-L owns only its matrices."""
+        if self._M_dev is None or self._M_dev.device != p_all.device:
+            self._M_dev = self.M.to(p_all.device)
+
+    def state_dict(self):
+        return {}
+
+    def load_state_dict(self, sd):
+        pass
 
 
 # ------------------------------------------------------------------------------------------------ classical NVT thermostats
@@ -587,6 +612,355 @@ class NHCThermostat(_ClassicalThermostat):
         return self._scale.view(self.n_replicas, self.n_molecules)
 
 
+# ------------------------------------------------------------------------------------------------ ring-polymer thermostats beyond PILE-L
+def rp_nhc_frequencies(n_beads: int, omega: float, time_constant: float) -> torch.Tensor:
+    """Frequencies [B] (float64) behind the thermostat masses of ``NHCRingPolymerThermostat._init_masses``
+    (md/simulation_hooks/thermostats_rpmd.py:417-455): the ring-polymer ``omega_normal`` (float32 sine, as the integrator forms it)
+    with the centroid entry replaced by 0.5 / time_constant.  A private copy: the integrator's own frequencies are not touched (the
+    reference overwrites ``integrator.omega_normal[0]`` in place, a side effect that is not reproduced)."""
+    on = (2.0 * omega * torch.sin(torch.arange(n_beads).float() * math.pi / n_beads)).double()
+    on[0] = 0.5 / time_constant
+    return on
+
+
+class _RingPolymerThermostatHip(_ThermostatHip):
+    """Device side of the ring-polymer thermostats (csrc/spk_md_rp_thermo.hip) on top of the classical entries."""
+
+    @staticmethod
+    def centroid(p_all, p_c, xi_c, seed, step, step_dev, which):
+        with torch.cuda.device(p_all.device):
+            check(lib().spk_md_rp_centroid_f32(fptr(p_all), int(p_all.shape[0]), int(p_all.shape[1]), fptr(p_c), fptr(xi_c), int(seed), int(step),
+                                               _lib.iptr(step_dev) if step_dev is not None else None, int(which), stream()))
+
+    @classmethod
+    def rp_nhc(cls, p_all, masses, C, link_masses, bead0, n_local, chain_length, multi_step, order, sub_steps, kT, vel, frc, scale_c, idx_m, n_mol, err, out):
+        with torch.cuda.device(p_all.device):
+            check(lib().spk_md_rp_nhc_f32(fptr(p_all), fptr(masses), fptr(C), fptr(link_masses), int(p_all.shape[0]), int(p_all.shape[1]), int(bead0),
+                                          int(n_local), int(chain_length), int(multi_step), int(order), cls._steps(sub_steps), float(kT), fptr(vel), fptr(frc),
+                                          fptr(scale_c), _lib.iptr(idx_m) if idx_m is not None else None, int(n_mol), _lib.iptr(err, torch.int32),
+                                          fptr(out), stream()))
+
+    @staticmethod
+    def pile_alpha(ke2, noise2, xi_c, n_atoms_mol, first_atom, n_atoms, c1, one_minus_c1_kT, alpha, err):
+        with torch.cuda.device(ke2.device):
+            check(lib().spk_md_pile_alpha_f32(fptr(ke2), fptr(noise2), fptr(xi_c), _lib.iptr(n_atoms_mol), _lib.iptr(first_atom), int(n_atoms_mol.shape[0]),
+                                              int(n_atoms), float(c1), float(one_minus_c1_kT), fptr(alpha), _lib.iptr(err, torch.int32), stream()))
+
+    @staticmethod
+    def pile_global(p_all, masses, M, noise_scale, seed, step, step_dev, which, bead0, n_local, p_c, alpha, idx_m, n_mol, err, out):
+        with torch.cuda.device(p_all.device):
+            check(lib().spk_md_pile_global_f32(fptr(p_all), fptr(masses), fptr(M), float(noise_scale), int(seed), int(step),
+                                               _lib.iptr(step_dev) if step_dev is not None else None, int(which), int(p_all.shape[0]), int(p_all.shape[1]),
+                                               int(bead0), int(n_local), fptr(p_c), fptr(alpha), _lib.iptr(idx_m), int(n_mol), _lib.iptr(err, torch.int32),
+                                               fptr(out), stream()))
+
+
+class _MoleculeLayoutRP:
+    """The molecule layout of ONE bead and the centroid workspaces the global ring-polymer thermostats share (a mix-in without
+    constructor arguments; the user sets ``n_beads`` and ``_compute``).
+
+    Lifetime.  ``_set_layout`` (from ``init``) records the layout; with ``idx_m`` given, ``n_atoms`` / ``n_molecules`` are known from
+    then on, without it (one molecule of all atoms) from the first ``prepare`` / application.  ``_prepare_layout`` allocates the device
+    buffers once per (device, momenta shape) -- a thermostat made without ``idx_m`` follows a new atom count, one made with it
+    refuses it.  The atom masses are copied INTO the owned buffer whenever another tensor, or the same tensor after an in-place
+    write, is handed in: a captured graph keeps the buffer's address, and nobody is served the masses of an earlier call."""
+
+    _layout_src = None            # (idx_m, n_atoms) as given to init, None: one molecule of all atoms
+    _layout_ready = _masses_src = None
+    _idx_m = _n_atoms_mol = None
+    n_atoms = n_molecules = None
+
+    def _set_layout(self, idx_m, n_atoms):
+        if idx_m is not None:
+            idx_m, n_atoms = idx_m.long().contiguous(), n_atoms.long().contiguous()
+            if idx_m.numel() > 1 and bool((idx_m[1:] < idx_m[:-1]).any()):
+                raise ValueError("idx_m must ascend (atoms of a molecule contiguous)")
+            if idx_m.numel() and (int(idx_m.min()) < 0 or int(idx_m.max()) >= int(n_atoms.shape[0])):
+                raise ValueError("idx_m outside [0, n_molecules)")
+            self._layout_src = (idx_m, n_atoms)
+            self.n_atoms, self.n_molecules = int(idx_m.shape[0]), int(n_atoms.shape[0])
+        else:
+            self._layout_src, self.n_atoms, self.n_molecules = None, None, None
+        self._idx_m, self._n_atoms_mol = idx_m, n_atoms
+        self._layout_ready = self._masses_src = None
+
+    def _need_layout(self, what):
+        if self.n_atoms is None:
+            raise RuntimeError("%s.%s: the number of atoms is not known yet -- pass idx_m / n_atoms to init(), or call prepare(momenta, masses) "
+                               "or apply the thermostat once" % (type(self).__name__, what))
+
+    def _prepare_layout(self, p_all, masses) -> bool:
+        """Buffers on the device of the momenta, allocated once per (device, shape); True when they are new."""
+        key = (p_all.device, tuple(p_all.shape))
+        new = self._layout_ready != key
+        if new:
+            if p_all.dim() != 3 or p_all.shape[2] != 3 or int(p_all.shape[0]) != self.n_beads:
+                raise ValueError("momenta must be [n_beads = %d, n_atoms, 3]" % self.n_beads)
+            N, dev = int(p_all.shape[1]), p_all.device
+            idx_m, n_mol = self._layout_src or (torch.zeros(N, dtype=torch.long), torch.tensor([N], dtype=torch.long))
+            if int(idx_m.shape[0]) != N:
+                raise ValueError("idx_m has %d entries for %d atoms" % (int(idx_m.shape[0]), N))
+            self._idx_m, self._n_atoms_mol = idx_m.to(dev), n_mol.to(dev)
+            self._first_atom = (torch.cumsum(self._n_atoms_mol, 0) - self._n_atoms_mol).contiguous()
+            self.n_atoms, self.n_molecules = N, int(self._n_atoms_mol.shape[0])
+            self._masses = torch.empty(N, dtype=torch.float32, device=dev)
+            self._masses_src = None
+            self._ones = torch.ones(N, dtype=torch.float32, device=dev)
+            self._p_c = torch.zeros(1, N, 3, dtype=torch.float32, device=dev)
+            self._xi_c = torch.zeros(1, N, 3, dtype=torch.float32, device=dev)
+            self._ke2 = torch.zeros(self.n_molecules, dtype=torch.float32, device=dev)
+            self._s2 = torch.zeros(self.n_molecules, dtype=torch.float32, device=dev)
+            self._scale = torch.ones(self.n_molecules, dtype=torch.float32, device=dev)
+            self._err = torch.zeros(1, dtype=torch.int32, device=dev)
+            self._ws = self._compute.workspace(1, N, self.n_molecules, dev)
+            self._layout_ready = key
+        # the source tensor is held, so "the same object at the same version" cannot be another tensor in recycled memory
+        if self._masses_src is None or self._masses_src[0] is not masses or self._masses_src[1] != masses._version:
+            with torch.no_grad():
+                self._masses.copy_(_flat_masses(masses, self.n_atoms))
+            self._masses_src = (masses, masses._version)
+        return new
+
+    def centroid_kinetic2(self, p_all, masses) -> torch.Tensor:
+        """sum over the atoms of a molecule of |p_c|^2 / m for the centroid normal-mode momentum p_c = sum_b p_b / sqrt(B), [n_molecules]
+        (a view of the thermostat's buffer)."""
+        p_all = p_all.contiguous()
+        self._prepare_layout(p_all, masses)
+        self._compute.centroid(p_all, self._p_c, None, 0, 0, None, 0)
+        self._compute.kinetic(self._p_c, self._masses, self._idx_m, self.n_molecules, self._ke2, self._err, self._ws)
+        return self._ke2
+
+
+class _RingPolymerThermostat(_MoleculeLayoutRP):
+    """What the ring-polymer thermostats of csrc/spk_md_rp_thermo.hip share: bath temperature, time constant in fs, the bead range of
+    a bead-parallel group and ``apply`` = ONE all-gather of the momenta + ``apply_beads`` (as ``PILELocalThermostat``)."""
+
+    ring_polymer = True
+
+    def __init__(self, temperature_bath: float, time_constant: float, group=None, compute_fn=None, fs: float = FS_MD, kb: float = KB_MD):
+        self.temperature_bath, self.time_constant = float(temperature_bath), float(time_constant) * float(fs)
+        self.kb, self.group = float(kb), group
+        self._compute = compute_fn or _RingPolymerThermostatHip
+        self.n_beads = None
+
+    def init(self, integrator: RingPolymer, idx_m: Optional[torch.Tensor] = None, n_atoms: Optional[torch.Tensor] = None):
+        self.n_beads, self.time_step, self.omega = integrator.n_beads, float(integrator.time_step), float(integrator.omega)
+        self.kb_temperature = self.kb * self.n_beads * self.temperature_bath          # kT of the ring polymer: n_beads kB T
+        self._range = integrator._bead_range if self.group is None else RingPolymer(integrator.time_step, self.n_beads, 1.0, omega=1.0,
+                                                                                    group=self.group)._bead_range
+        self._set_layout(idx_m, n_atoms)
+        self._init_thermostat()
+        return self
+
+    def _init_thermostat(self):
+        pass
+
+    def prepare(self, p_all, masses):
+        self._prepare_layout(p_all, masses)
+
+    def apply(self, state, step: int = 0, which: int = 0, step_dev=None, out=None):
+        return _apply_to_state(self, state, step, which, step_dev, out)
+
+    def state_dict(self):
+        return {}
+
+    def load_state_dict(self, sd):
+        pass
+
+
+class NHCRingPolymerThermostat(_RingPolymerThermostat):
+    """``NHCRingPolymerThermostat`` of the reference (md/simulation_hooks/thermostats_rpmd.py:373-501): the massive Nose-Hoover chain
+    on the NORMAL-MODE momenta, kT = n_beads kB T, every link of mode k with the mass kT / omega_k^2 (``rp_nhc_frequencies``).
+    ``local=False``: the centroid of every molecule is ONE chain on the molecule's whole centroid kinetic energy with 3 n_atoms
+    degrees of freedom (``spk_md_nhc_global_f32``).  One launch (``spk_md_rp_nhc_f32``) transforms, propagates every chain, scales and
+    transforms back; the chain state of ALL modes lives on every rank of a bead-parallel run and is advanced identically there.
+
+    ``state_dict`` / ``load_state_dict``: ``velocities`` / ``forces`` / ``masses`` in the reference's shape [n_beads, n_atoms, 3,
+    chain_length]; with ``local=False`` the centroid rows are the molecule chains broadcast over their atoms (loading takes them
+    from the first atom of every molecule).  The reference's in-place edit of the integrator's ``omega_normal[0]`` is not
+    reproduced: the ``RingPolymer`` propagator stays as it is.  ``integration_order`` 1 is accepted on top of 3, 5, 7."""
+
+    def __init__(self, temperature_bath: float, time_constant: float, local: bool = True, chain_length: int = 3, multi_step: int = 2,
+                 integration_order: int = 3, group=None, compute_fn=None, fs: float = FS_MD, kb: float = KB_MD):
+        super().__init__(temperature_bath, time_constant, group, compute_fn, fs, kb)
+        if int(chain_length) < 1:
+            raise ValueError("chain_length must be at least 1")
+        self.local, self.chain_length = bool(local), int(chain_length)
+        self.multi_step, self.integration_order = int(multi_step), int(integration_order)
+        nhc_sub_steps(1.0, self.multi_step, self.integration_order)          # validates both
+        self.frequency = 1.0 / self.time_constant
+        self.sub_steps = None
+        self._vel = self._frc = None
+        self._pending = None
+
+    def _init_thermostat(self):
+        self.sub_steps = nhc_sub_steps(self.time_step, self.multi_step, self.integration_order)
+        self.frequencies = rp_nhc_frequencies(self.n_beads, self.omega, self.time_constant)
+        self.link_masses = self.kb_temperature / self.frequencies ** 2                  # [B] float64
+        self.C = normal_mode_matrix(self.n_beads).float().contiguous()
+        self._vel = self._frc = None
+
+    def prepare(self, p_all, masses):
+        if not self._prepare_layout(p_all, masses) and self._vel is not None:
+            return
+        if self.sub_steps is None:
+            raise RuntimeError("NHCRingPolymerThermostat.init(integrator) has not been called")
+        dev, L, B, N = p_all.device, self.chain_length, self.n_beads, self.n_atoms
+        self._C_dev, self._lm_dev = self.C.to(dev), self.link_masses.float().to(dev)
+        self._vel = torch.zeros(L, B, 3 * N, dtype=torch.float32, device=dev)         # link-major: what the kernel reads coalesced
+        self._frc = torch.zeros(L, B, 3 * N, dtype=torch.float32, device=dev)
+        self._cvel = torch.zeros(self.n_molecules, L, dtype=torch.float32, device=dev)   # local=False: the molecules' centroid chains
+        self._cfrc = torch.zeros(self.n_molecules, L, dtype=torch.float32, device=dev)
+        if self._pending is not None:
+            sd, self._pending = self._pending, None
+            self.load_state_dict(sd)
+
+    @property
+    def degrees_of_freedom(self) -> torch.Tensor:
+        """[n_beads, n_atoms, 3] (float64): 1, and 3 n_atoms of the atom's molecule on the global centroid.  Needs the atom count:
+        ``init`` with ``idx_m``, or the first ``prepare`` / application (RuntimeError before)."""
+        self._need_layout("degrees_of_freedom")
+        dof = torch.ones(self.n_beads, self.n_atoms, 3, dtype=torch.float64)
+        if not self.local:
+            dof[0] = (3 * self._n_atoms_mol[self._idx_m]).double().cpu()[:, None]
+        return dof
+
+    @property
+    def masses(self) -> torch.Tensor:
+        """Thermostat masses [n_beads, n_atoms, 3, chain_length] (float64): kT / omega_k^2, innermost link x degrees of freedom.
+        Available when ``degrees_of_freedom`` is."""
+        self._need_layout("masses")
+        m = self.link_masses[:, None, None, None].expand(self.n_beads, self.n_atoms, 3, self.chain_length).clone()
+        m[..., 0] *= self.degrees_of_freedom
+        return m
+
+    def _public(self, t, ct):
+        L, B, N = self.chain_length, self.n_beads, self.n_atoms
+        out = t.permute(1, 2, 0).reshape(B, N, 3, L).clone()
+        if not self.local:
+            out[0] = ct[self._idx_m][:, None, :].expand(N, 3, L)
+        return out
+
+    def state_dict(self):
+        if self._vel is None:
+            raise RuntimeError("NHCRingPolymerThermostat: no chain state before the buffers exist (prepare / first application)")
+        return {"velocities": self._public(self._vel, self._cvel), "forces": self._public(self._frc, self._cfrc), "masses": self.masses}
+
+    def load_state_dict(self, sd):
+        """Chain state of an earlier run, copied INTO the owned buffers (a captured graph keeps pointing at them); before the
+        buffers exist it is kept and loaded when they do."""
+        if self._vel is None:
+            self._pending = dict(sd)
+            return
+        L, B, N = self.chain_length, self.n_beads, self.n_atoms
+        live = self._n_atoms_mol > 0
+        for name, buf, cbuf in (("velocities", self._vel, self._cvel), ("forces", self._frc, self._cfrc)):
+            t = sd[name]
+            if tuple(t.shape) != (B, N, 3, L):
+                raise ValueError("%s: expected shape %s, got %s" % (name, (B, N, 3, L), tuple(t.shape)))
+            t = t.to(buf.device, buf.dtype)
+            with torch.no_grad():
+                if self.local:
+                    buf.copy_(t.reshape(B, 3 * N, L).permute(2, 0, 1))
+                else:
+                    buf[:, 1:].copy_(t[1:].reshape(B - 1, 3 * N, L).permute(2, 0, 1))
+                    cbuf[live] = t[0, self._first_atom[live], 0, :]
+        if "masses" in sd and not torch.allclose(sd["masses"].double().cpu(), self.masses, rtol=1e-5, atol=0.0):
+            raise ValueError("masses of the loaded chain state are not those of this thermostat (temperature / time constant differ)")
+
+    def apply_beads(self, p_all, masses, bead0, n_local, step=0, step_dev=None, which=0, out=None):
+        self.prepare(p_all, masses)
+        c = self._compute
+        if out is None:
+            out = torch.empty(n_local, self.n_atoms, 3, dtype=torch.float32, device=p_all.device)
+        chain = (self.chain_length, self.multi_step, self.integration_order, self.sub_steps, self.kb_temperature)
+        scale = None
+        if not self.local:
+            c.centroid(p_all, self._p_c, None, 0, 0, None, 0)
+            c.kinetic(self._p_c, self._masses, self._idx_m, self.n_molecules, self._ke2, self._err, self._ws)
+            c.nhc_global(self._ke2, self._n_atoms_mol, 1, *chain, float(self.link_masses[0]), self._cvel, self._cfrc, self._scale)
+            scale = self._scale
+        c.rp_nhc(p_all, self._masses, self._C_dev, self._lm_dev, bead0, n_local, *chain, self._vel, self._frc, scale,
+                 self._idx_m, self.n_molecules, self._err, out)
+        return out
+
+    @property
+    def scaling_factor(self) -> torch.Tensor:
+        """Centroid factor of the last ``local=False`` application, [n_molecules]."""
+        return self._scale
+
+
+class PILEGlobalThermostat(_MoleculeLayoutRP, PILELocalThermostat):
+    """``PILEGlobalThermostat`` of the reference (md/simulation_hooks/thermostats_rpmd.py:122-208): PILE-L on the modes k >= 1 (same
+    coefficients, same Philox counters as ``PILELocalThermostat`` with the same seed) and, on the centroid of every molecule, the
+    stochastic velocity rescaling of Bussi, Donadio and Parrinello: p_c <- alpha p_c with
+
+        alpha^2 = c + S g + 2 R1 sqrt(c g),  alpha = sqrt(alpha^2) sign(R1 + sqrt(c / g)),  g = (1 - c) n_beads kB T / K
+
+    K = the molecule's centroid kinetic sum, S = the sum of its squared centroid noise, c = c1[0].
+
+    Two deviations from the reference.  (1) R1 of a molecule is the centroid noise of the x component of ITS first atom.  The
+    reference takes element [0, 0, 0] of the batch's noise -- atom 0 of the whole batch -- for every molecule, which couples the
+    molecules of a batch and gives all but the first an R1 that is not among its own S terms (not Bussi's distribution); for one
+    molecule the two coincide.  (2) A molecule without atoms or with K = 0 (every run starts from zero momenta) gets alpha = 1: its
+    centroid is left alone and no noise is added there; the reference divides by zero."""
+
+    def __init__(self, temperature_bath: float, time_constant: float, seed: int = 0, group=None, compute_fn=None, fs: float = FS_MD,
+                 kb: float = KB_MD):
+        # the layout mix-in takes no arguments; PILE-L's constructor does everything, with the device entries of this class as ``compute_fn``
+        super().__init__(temperature_bath, time_constant, True, 1.0, seed, group, compute_fn or _RingPolymerThermostatHip, fs, kb)
+
+    def init(self, integrator: RingPolymer, idx_m: Optional[torch.Tensor] = None, n_atoms: Optional[torch.Tensor] = None):
+        super().init(integrator)
+        self.kb_temperature = self.kb * self.n_beads * self.temperature_bath
+        self._set_layout(idx_m, n_atoms)
+        self._M_dev = None
+        return self
+
+    def _matrices(self, integrator):
+        """M of PILE-L with the centroid taken out (c1[0] = c2[0] = 0); c1[0] goes to the rescaling."""
+        C = normal_mode_matrix(self.n_beads)
+        c1, c2 = pile_coefficients(self.n_beads, integrator.omega, integrator.time_step, self.time_constant, True, 1.0)
+        self.c1_centroid = float(c1[0])
+        c1, c2 = c1.clone(), c2.clone()
+        c1[0] = c2[0] = 0.0
+        return torch.stack([C.t() @ torch.diag(c1) @ C, C.t() @ torch.diag(c2)]).float().contiguous()
+
+    def prepare(self, p_all, masses):
+        self._prepare_layout(p_all, masses)
+        if self._M_dev is None or self._M_dev.device != p_all.device:
+            self._M_dev = self.M.to(p_all.device)
+
+    def apply_beads(self, p_all, masses, bead0, n_local, step=0, step_dev=None, which=0, out=None):
+        self.prepare(p_all, masses)
+        c = self._compute
+        if out is None:
+            out = torch.empty(n_local, self.n_atoms, 3, dtype=torch.float32, device=p_all.device)
+        c.centroid(p_all, self._p_c, self._xi_c, self.seed, step, step_dev, which)
+        c.kinetic(self._p_c, self._masses, self._idx_m, self.n_molecules, self._ke2, self._err, self._ws)
+        c.kinetic(self._xi_c, self._ones, self._idx_m, self.n_molecules, self._s2, self._err, self._ws)
+        c.pile_alpha(self._ke2, self._s2, self._xi_c, self._n_atoms_mol, self._first_atom, self.n_atoms, self.c1_centroid,
+                     (1.0 - self.c1_centroid) * self.kb_temperature, self._scale, self._err)
+        c.pile_global(p_all, self._masses, self._M_dev, self.noise_scale, self.seed, step, step_dev, which, bead0, n_local, self._p_c,
+                      self._scale, self._idx_m, self.n_molecules, self._err, out)
+        return out
+
+    @property
+    def alpha(self) -> torch.Tensor:
+        """Centroid factor of the last application, [n_molecules]."""
+        return self._scale
+
+
+class TRPMDThermostat(PILELocalThermostat):
+    """``TRPMDThermostat`` of the reference (md/simulation_hooks/thermostats_rpmd.py:211-234): PILE-L without a centroid thermostat
+    and with the friction of the modes k >= 1 multiplied by ``damping_factor`` -- ``PILELocalThermostat(temperature_bath, 1.0,
+    thermostat_centroid=False, damping_factor=damping_factor)``, bit for bit."""
+
+    def __init__(self, temperature_bath: float, damping_factor: float, seed: int = 0, group=None, compute_fn=None, fs: float = FS_MD,
+                 kb: float = KB_MD):
+        super().__init__(temperature_bath, 1.0, False, damping_factor, seed, group, compute_fn, fs, kb)
+
+
 class MDState:
     """Minimal stand-in for ``schnetpack.md.System`` (md/system.py): the tensors the integrators touch."""
 
@@ -898,8 +1272,14 @@ class RPMDSimulation(NVESimulation):
     into the batch dimension exactly as the reference does (md/calculators/base_calculator.py:166-183), so one force call
     and one device neighbour list serve all beads of a rank.  Single process -- one step is one graph replay:
 
-        [PILE-L]  ->  kick (p += dt/2 F)  ->  ring-polymer main step (k_md_ring_polymer: bead mixing + skin test)  ->
-        force call of all beads  ->  kick  ->  [PILE-L]
+        [thermostat]  ->  kick (p += dt/2 F)  ->  ring-polymer main step (k_md_ring_polymer: bead mixing + skin test)  ->
+        force call of all beads  ->  kick  ->  [thermostat]
+
+    ``thermostat``: ``PILELocalThermostat``, ``PILEGlobalThermostat``, ``TRPMDThermostat`` or ``NHCRingPolymerThermostat``; the
+    simulation hands every one of them the momenta of all beads, the rank's bead range, the device step counter and its output
+    buffer (``apply_beads``).  GLE and PIGLET are not built.  ``centroid_kinetic_energy()`` / ``centroid_temperature()`` per molecule
+    work where this process holds the momenta of all beads (single process, ``exchange="forces"``); with ``exchange="state"`` over
+    several ranks they raise NotImplementedError.
 
     The conserved quantity (no thermostat) is the ring-polymer Hamiltonian
     ``sum_b [p_b^2 / 2m + V(q_b)] + sum_b 1/2 m omega^2 |q_b - q_{b+1}|^2`` (``total_energy``).
@@ -922,7 +1302,7 @@ class RPMDSimulation(NVESimulation):
     can share one device in a test)."""
 
     def __init__(self, model, inputs, masses, time_step, n_beads, cutoff, temperature=300.0, omega=None,
-                 cutoff_shell=1.0, use_graph=True, thermostat: Optional["PILELocalThermostat"] = None, complete_list="auto",
+                 cutoff_shell=1.0, use_graph=True, thermostat=None, complete_list="auto",
                  group=None, exchange: str = "state"):
         from . import properties as P
         if exchange not in ("state", "forces"):
@@ -940,6 +1320,7 @@ class RPMDSimulation(NVESimulation):
         N = int(inputs[P.R].shape[0])
         rep = fold_replicas(inputs, B)
         self._n1 = N
+        self._idx_m1, self._n_atoms1 = inputs[P.idx_m].long().contiguous(), inputs[P.n_atoms].long().contiguous()   # layout of ONE bead
         super().__init__(model, rep, masses, time_step, cutoff, cutoff_shell, use_graph, complete_list=complete_list)
 
     # -- state ---------------------------------------------------------------------------------
@@ -973,10 +1354,15 @@ class RPMDSimulation(NVESimulation):
             self._pack = torch.empty(2, Bl, N, 3, device=dev)                    # (q, p) of the rank, one message
             self._gath = torch.empty(self._world, 2, Bl, N, 3, device=dev)
             self._pgath = torch.empty(self._world, Bl, N, 3, device=dev)
-        if self.thermostat is not None:          # NVT: PILE-L at step begin and end (md/simulator.py:126-150)
-            self.thermostat.init(self._rp)
-            self._M = self.thermostat.M.to(dev)
+        self._meter = None                       # centroid observables: built by the first call that asks for one
+        if self.thermostat is not None:          # NVT: the thermostat at step begin and end (md/simulator.py:126-150)
+            if not getattr(self.thermostat, "ring_polymer", False) or not hasattr(self.thermostat, "apply_beads"):
+                raise ValueError("RPMDSimulation needs a ring-polymer thermostat (PILELocalThermostat, PILEGlobalThermostat, TRPMDThermostat, "
+                                 "NHCRingPolymerThermostat), got %s" % type(self.thermostat).__name__)
+            self.thermostat.init(self._rp, self._idx_m1, self._n_atoms1)
             self._stepc = torch.zeros(1, dtype=torch.int64, device=dev)      # step counter on the device: fresh noise per graph replay
+            # chain state and workspaces once, before the first capture; re-captured graphs point at the same tensors
+            self.thermostat.prepare(torch.empty(self.n_beads, N, 3, device=dev), m)
 
     def _force_buffer(self, f):
         if not self._replicated:
@@ -1001,17 +1387,15 @@ class RPMDSimulation(NVESimulation):
     # -- pieces of a step --------------------------------------------------------------------------
     def _thermostat(self, which):
         th = self.thermostat
-        if self._replicated:                       # all beads, every rank, same counter-based noise: no exchange
-            st = self.full
-            _pile_hip(st.momenta, st.masses, self._M, th.noise_scale, th.seed, 0, self._stepc, which, 0, self.n_beads, self._pt)
+        if self._replicated:                       # all beads, every rank, same counter-based noise / chain arithmetic: no exchange
+            st, p_all, lo, n_local = self.full, self.full.momenta, 0, self.n_beads
         elif self._dist:                      # the rank's beads from everybody's momenta: ONE all-gather
             st = self.state
             self._all_gather(self._pgath, st.momenta)
-            _pile_hip(self._pgath.view(self.n_beads, self._n1, 3), st.masses, self._M, th.noise_scale, th.seed, 0, self._stepc, which,
-                      self._lo, self.n_local, self._pt)
+            p_all, lo, n_local = self._pgath.view(self.n_beads, self._n1, 3), self._lo, self.n_local
         else:
-            st = self.state
-            _pile_hip(st.momenta, st.masses, self._M, th.noise_scale, th.seed, 0, self._stepc, which, 0, self.n_beads, self._pt)
+            st, p_all, lo, n_local = self.state, self.state.momenta, 0, self.n_beads
+        th.apply_beads(p_all, st.masses, lo, n_local, 0, self._stepc, which, self._pt)
         with torch.no_grad():
             st.momenta.copy_(self._pt)
 
@@ -1093,6 +1477,33 @@ class RPMDSimulation(NVESimulation):
         if self._replicated:
             return 1
         return 1 + (2 if self.thermostat is not None else 0)
+
+    def _all_momenta(self):
+        if self._replicated:
+            return self.full.momenta
+        if self._dist:
+            raise NotImplementedError("centroid observables of exchange='state' over several ranks need the other ranks' beads")
+        return self.state.momenta
+
+    def _centroid_meter(self):
+        if self._meter is None:
+            kb = getattr(self.thermostat, "kb", KB_MD)
+            self._meter = _RingPolymerThermostat(0.0, 1.0, kb=kb).init(self._rp, self._idx_m1, self._n_atoms1)
+        return self._meter
+
+    def centroid_kinetic_energy(self) -> torch.Tensor:
+        """Kinetic energy of the centroid per molecule, [n_molecules] (``System.centroid_kinetic_energy``, md/system.py:523-537):
+        the centroid momentum is the bead mean, p_c / sqrt(n_beads) of the normal-mode centroid ``spk_md_rp_centroid_f32`` writes.
+        Needs the momenta of all beads on this process: single process or ``exchange="forces"``; with ``exchange="state"`` over
+        several ranks it raises NotImplementedError (no collective is spent on an observable)."""
+        return 0.5 * self._centroid_meter().centroid_kinetic2(self._all_momenta(), self.state.masses) / self.n_beads
+
+    def centroid_temperature(self) -> torch.Tensor:
+        """Instantaneous centroid temperature per molecule, [n_molecules] (md/system.py:539-555); 0 for a molecule without atoms.
+        Same limit as ``centroid_kinetic_energy``."""
+        ke = self.centroid_kinetic_energy()
+        n = self._meter._n_atoms_mol.to(ke.dtype)
+        return torch.where(n > 0, 2.0 * ke / (3.0 * n.clamp_min(1.0) * self._meter.kb), torch.zeros_like(ke))
 
     def spring_energy(self):
         """Spring energy of the beads this process holds (all of them unless ``exchange="state"`` over several ranks, where
