@@ -618,6 +618,11 @@ int spk_filter_table_drop_if_stale(const float* key, uint64_t stamp);
  * of workgroup 0 at the phase boundaries; [128 + 4 b, 128 + 4 b + 4): start / end of workgroup b of the backward launch (real time and
  * shader clock) -- so it must hold 128 + 4 * (number of groups) entries; NULL disables it (default). */
 void spk_schnet_mol_set_debug_buffer(void* device_buffer);
+/* Derivative tasks per 32-pair tile in the backward of those kernels (phase E of k_schnet_mol_bwd): 1 = one task per tile -- the hidden
+ * layer of the filter network once, then both channel-tile pairs; every per-pair sum is then built in one fixed order -- 2 = one task
+ * per (tile, channel-tile pair), the hidden layer twice; 0 = automatic (default; the rule is written at the task queue).  Read at
+ * launch.  For tuning and tests. */
+void spk_schnet_mol_set_bwd_task_split(int split);
 /* The same for the molecule-resident PaiNN kernels (spk_painn_mol.hip; representation/painn.py:207-256 with q / mu / context rows
  * of a <= 32-atom block in LDS, all interactions in one launch): >= 256 int64; entry 0 = group start, 1 + 8 l .. 8 + 8 l = phase
  * boundaries of interaction l of the forward (thread 0 of workgroup 0); entries 64.. the backward, 128 + 16 w .. the message phase

@@ -784,6 +784,9 @@ static long long* g_mol_dbg = nullptr;
 // [0, 128): phases of thread 0 of workgroup 0; [128 + 4 b, 128 + 4 b + 4): real-time and cycle stamps at the start / end of workgroup b
 // of the backward launch, so the buffer must hold 128 + 4 * (number of groups) entries.  NULL: off (production)
 extern "C" void spk_schnet_mol_set_debug_buffer(void* p) { g_mol_dbg = (long long*)p; }
+// derivative tasks per pair tile in phase E of the backward: 0 = automatic (the rule at the task queue of k_schnet_mol_bwd), 1, 2
+static int g_mol_bwd_task_split = 0;
+extern "C" void spk_schnet_mol_set_bwd_task_split(int split) { g_mol_bwd_task_split = (split == 1 || split == 2) ? split : 0; }
 
 static size_t mol_w1_floats(int kpb, bool sp) {      // LDS floats of the staged W1 image(s): MlW1Image<KPB>::BYTES twice in the split form
   return sp ? (size_t)2 * (4096 + (kpb > 2 ? (kpb == 4 ? 4096 : 2048) : 0)) / 4 : (size_t)128 * kpb * 8;
@@ -882,11 +885,14 @@ int spk_schnet_mol_forward_ex(const spk_schnet_t* m, const spk_graph_t* g, const
 //
 // Per interaction, last to first (notation of SURVEY.md Appendix B; everything below is local to the group):
 //   D1. gt = (gx W4) * ssp'(pre3)          D2. gy = gt W3                                (two T-GEMM phases)
-//   E.  task queue:  (pair tile, channel-tile pair) derivative tasks  +  row-sum tasks  +  the four tiles of G
-//         derivative task: phi, phi' -> GEMM 1 value and derivative (a, a') -> z' = sigmoid(a) a' -> GEMM 2' (rows =
+//   E.  task queue:  derivative tasks (one per pair tile)  +  row-sum tasks  +  the four tiles of G
+//         derivative task: phi, phi' -> GEMM 1 value and derivative (a, a') -> z' = sigmoid(a) a' -- the hidden layer, once per
+//           pair tile: it does not depend on the channel tile -- then a loop over the two channel-tile pairs tp: GEMM 2' (rows =
 //           channels, columns = pairs: lane = pair) -> D = g' f_c + g f_c' with the SAVED raw filter outputs g ->
 //           s1 = sum_c gy_i h_j D,  s2 = sum_c gy_j h_i D  (in-lane sums over the 16 channels a lane owns, one LDS add per
-//           pair and task); the per-pair sums are kept in LDS across all interactions and become dL/dr once, at the end
+//           pair and tp, in the order tp = 0, 1: one wave builds a pair's sum in one fixed order); the per-pair sums are kept in
+//           LDS across all interactions and become dL/dr once, at the end.  (spk_schnet_mol_set_bwd_task_split(2): one task
+//           per (pair tile, tp), the hidden layer twice per tile -- the form before; the rule of the automatic choice is at the queue)
 //         row-sum task:    gh[a] = sum_{b in row(a)} gy[b] * g[pair(a,b)] * f_c           (the transpose of the forward row sum)
 //         G task (channel tile t): gx[:, 32 t : 32 t + 32] += gh W_in -- waits for the row sums only (LDS counter)
 // ==========================================================================================================
@@ -916,6 +922,7 @@ struct MolBwdArgs {
   int64_t gsz, N;
   RadialDev rb;
   int compact;              // as in the forward
+  int task_split;           // derivative tasks per pair tile in phase E: 0 = automatic, 1, 2 (spk_schnet_mol_set_bwd_task_split)
   long long* dbg;
 };
 
@@ -1116,8 +1123,16 @@ __global__ __launch_bounds__(512) void k_schnet_mol_bwd(MolBwdArgs a) {
       // ================= E: derivative tasks (pair tile, pair of channel tiles) + row-sum tasks (one atom, all channels)
       // The queue hands out the derivative tasks first, then the row sums, then -- unless nothing below consumes dL/dx -- the four
       // channel tiles of G (gx += gh W_in): G only waits for the row sums (a counter in LDS), not for the derivative tasks, so it
-      // runs on the waves that the second round of derivative tasks leaves idle instead of being a phase of its own.
-      const int nder = 2 * ntile;
+      // runs on the waves that the derivative tasks leave idle instead of being a phase of its own.
+      // A derivative task covers pair tile `tile` and the channel-tile pairs [tp0, tp1): the hidden layer of the filter network does
+      // not depend on the channel tile, so a task computes it once and loops over its channel-tile pairs behind it.  `split` tasks
+      // per tile (uniform over the group): 1 = one task does both pairs (hidden layer once per tile), 2 = one pair each (twice).
+      // Automatic = 1 for every group.  The candidate exception -- two tasks per tile while they fit one round, 2 ntile <= 8 -- lost
+      // where it would apply (profiles/r07_mol_bwd_task_split.md; backward launch, 1 against 2 tasks per tile): 256 ethanol frames,
+      // groups of 2 ... 4 tiles, 61.7 against 65.9 us; 16-atom blobs, 8 tiles, 76.5 against 92.1 us; aspirin, 5 tiles, 63.6 against
+      // 73.0 us -- spread of the call times 0.2 ... 0.4 us.
+      const int split = a.task_split ? a.task_split : 1;
+      const int nder = split * ntile;
       const int nrow = (last || np == 0) ? 0 : na;
       const int ng = last ? 0 : NT;
       if (np == 0 && !last) {    // no pair inside the cutoff: dL/dh = 0 (the buffer still holds the hidden gradient of f2out)
@@ -1162,7 +1177,8 @@ __global__ __launch_bounds__(512) void k_schnet_mol_bwd(MolBwdArgs a) {
           if (lane == 0) atomicAdd(&sCnt[1], 1);
           continue;
         }
-        const int tile = k >> 1, tp = k & 1;
+        const int tile = split == 2 ? k >> 1 : k;
+        const int tp0 = split == 2 ? (k & 1) : 0, tp1 = split == 2 ? tp0 + 1 : 2;
         const int pfirst = 32 * tile;
         const int nvalid = (np - pfirst) < 32 ? (np - pfirst) : 32;
         const bool valid = el < nvalid;
@@ -1171,13 +1187,7 @@ __global__ __launch_bounds__(512) void k_schnet_mol_bwd(MolBwdArgs a) {
         const float fc = valid ? pr.fc : 0.f, dfc = valid ? pr.dfc : 0.f;
         const int pi = pr.ij & 255, pj = (pr.ij >> 8) & 255;
         const int grow = pr.ij >> 16;                       // row of this pair in the saved filter tensor
-        // the saved raw filter outputs of this lane's pair for both channel tiles of the task: requested first, used last
-        f32x4 gl[2][4];
-#pragma unroll
-        for (int tt = 0; tt < 2; ++tt)
-#pragma unroll
-          for (int q = 0; q < 4; ++q) gl[tt][q] = ml_ld<f32x4>(g_g + 64 * tp, (unsigned)((grow * NF + 4 * hi + 32 * tt + 8 * q) * 4));
-        float s1 = 0.f, s2 = 0.f;
+        float* const sums = sS + 2 * pl;                    // this pair's (s1, s2)
         if constexpr (SP) {
           // ---- split form (spk_split.h).  GEMM 1, value and derivative, for the four hidden tiles: A = the W1 images, B = this pair's
           // basis values / slopes in the lane's k-slots; z' = sigmoid(a) a' goes from the accumulator registers into the B operand
@@ -1220,35 +1230,51 @@ __global__ __launch_bounds__(512) void k_schnet_mol_bwd(MolBwdArgs a) {
           const float* gyj_p = sGy + pj * ML_LD + 4 * hi_o;
           const float* hi_p = sH + pi * ML_LD + 4 * hi_o;
           const float* hj_p = sH + pj * ML_LD + 4 * hi_o;
+#pragma unroll 1
+          for (int tp = tp0; tp < tp1; ++tp) {
+            // the saved raw filter outputs of this lane's pair for both channel tiles of the pair: requested in front of the
+            // matrix instructions of this iteration, used behind them
+            f32x4 gl[2][4];
 #pragma unroll
-          for (int tt = 0; tt < 2; ++tt) {
-            const int t = 2 * tp + tt;
-            f32x16 gp, gpx;
+            for (int tt = 0; tt < 2; ++tt)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) { gp[r] = 0.f; gpx[r] = 0.f; }
-            const h16x8* wbh = sW2h + (t * 8) * 64 + lane_o;
-            const h16x8* wbl = sW2l + (t * 8) * 64 + lane_o;
-            h16x8 wh[8], wl[8];
+              for (int q = 0; q < 4; ++q) gl[tt][q] = ml_ld<f32x4>(g_g + 64 * tp, (unsigned)((grow * NF + 4 * hi + 32 * tt + 8 * q) * 4));
+            float s1 = 0.f, s2 = 0.f;
 #pragma unroll
-            for (int s = 0; s < 2; ++s) { wh[s] = wbh[s * 64]; wl[s] = wbl[s * 64]; }
-            ML_PIN();
+            for (int tt = 0; tt < 2; ++tt) {
+              const int t = 2 * tp + tt;
+              f32x16 gp, gpx;
 #pragma unroll
-            for (int s = 0; s < 8; ++s) {
-              if (s + 2 < 8) { wh[s + 2] = wbh[(s + 2) * 64]; wl[s + 2] = wbl[(s + 2) * 64]; ML_PIN(); }
-              SP_STEP(wh[s], wl[s], zph[s >> 1][s & 1], zpl[s >> 1][s & 1], gp, gpx);
+              for (int r = 0; r < 16; ++r) { gp[r] = 0.f; gpx[r] = 0.f; }
+              const h16x8* wbh = sW2h + (t * 8) * 64 + lane_o;
+              const h16x8* wbl = sW2l + (t * 8) * 64 + lane_o;
+              h16x8 wh[8], wl[8];
+#pragma unroll
+              for (int s = 0; s < 2; ++s) { wh[s] = wbh[s * 64]; wl[s] = wbl[s * 64]; }
+              ML_PIN();
+#pragma unroll
+              for (int s = 0; s < 8; ++s) {
+                if (s + 2 < 8) { wh[s + 2] = wbh[(s + 2) * 64]; wl[s + 2] = wbl[(s + 2) * 64]; ML_PIN(); }
+                SP_STEP(wh[s], wl[s], zph[s >> 1][s & 1], zpl[s >> 1][s & 1], gp, gpx);
+              }
+              SP_FOLD(gp, gpx);
+#pragma unroll
+              for (int q = 0; q < 4; ++q) {
+                const int col = 32 * t + 8 * q;
+                const f32x4 gyi = *(const f32x4*)(gyi_p + col), gyj = *(const f32x4*)(gyj_p + col);
+                const f32x4 hvi = *(const f32x4*)(hi_p + col), hvj = *(const f32x4*)(hj_p + col);
+                const f32x4 gq = gl[tt][q];
+                const float D0 = gp[4 * q] * fc + gq.x * dfc, D1 = gp[4 * q + 1] * fc + gq.y * dfc;
+                const float D2 = gp[4 * q + 2] * fc + gq.z * dfc, D3 = gp[4 * q + 3] * fc + gq.w * dfc;
+                s1 += gyi.x * hvj.x * D0 + gyi.y * hvj.y * D1 + gyi.z * hvj.z * D2 + gyi.w * hvj.w * D3;
+                s2 += gyj.x * hvi.x * D0 + gyj.y * hvi.y * D1 + gyj.z * hvi.z * D2 + gyj.w * hvi.w * D3;
+              }
             }
-            SP_FOLD(gp, gpx);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-              const int col = 32 * t + 8 * q;
-              const f32x4 gyi = *(const f32x4*)(gyi_p + col), gyj = *(const f32x4*)(gyj_p + col);
-              const f32x4 hvi = *(const f32x4*)(hi_p + col), hvj = *(const f32x4*)(hj_p + col);
-              const f32x4 gq = gl[tt][q];
-              const float D0 = gp[4 * q] * fc + gq.x * dfc, D1 = gp[4 * q + 1] * fc + gq.y * dfc;
-              const float D2 = gp[4 * q + 2] * fc + gq.z * dfc, D3 = gp[4 * q + 3] * fc + gq.w * dfc;
-              s1 += gyi.x * hvj.x * D0 + gyi.y * hvj.y * D1 + gyi.z * hvj.z * D2 + gyi.w * hvj.w * D3;
-              s2 += gyj.x * hvi.x * D0 + gyj.y * hvi.y * D1 + gyj.z * hvi.z * D2 + gyj.w * hvi.w * D3;
-            }
+            // one partial per channel-tile pair, added in the order tp = 0, 1 (the LDS operations of a wave stay in order): with one
+            // task per tile the sum of a pair is built by one wave in one order
+            s1 += __shfl_xor(s1, 32, 64);
+            s2 += __shfl_xor(s2, 32, 64);
+            if (hi == 0 && valid) { atomicAdd(sums, s1); atomicAdd(sums + 1, s2); }
           }
         } else {
         float phi[KPB][4], dphi[KPB][4];
@@ -1320,46 +1346,59 @@ __global__ __launch_bounds__(512) void k_schnet_mol_bwd(MolBwdArgs a) {
         const float* gyj_p = sGy + pj * ML_LD + 4 * hi;
         const float* hi_p = sH + pi * ML_LD + 4 * hi;
         const float* hj_p = sH + pj * ML_LD + 4 * hi;
+#pragma unroll 1
+        for (int tp = tp0; tp < tp1; ++tp) {
+          // the saved raw filter outputs of this lane's pair for both channel tiles of the pair: requested in front of the
+          // matrix instructions of this iteration, used behind them
+          f32x4 gl[2][4];
 #pragma unroll
-        for (int tt = 0; tt < 2; ++tt) {
-          const int t = 2 * tp + tt;
-          f32x16 gp;
+          for (int tt = 0; tt < 2; ++tt)
 #pragma unroll
-          for (int r = 0; r < 16; ++r) gp[r] = 0.f;
-          {
-            // weights from LDS, requested three k-blocks ahead and pinned there (the one-ahead form was collapsed by the compiler
-            // to "ds_read, wait, four MFMAs": a derivative task alone on its SIMD then waits out the LDS round trip of every k-block)
-            const float* wbase = sW2 + ((int64_t)t * KB2 * 64 + lane) * 4;
-            f32x4 wb[KB2];
+            for (int q = 0; q < 4; ++q) gl[tt][q] = ml_ld<f32x4>(g_g + 64 * tp, (unsigned)((grow * NF + 4 * hi + 32 * tt + 8 * q) * 4));
+          float s1 = 0.f, s2 = 0.f;
 #pragma unroll
-            for (int ug = 0; ug < 3; ++ug) wb[ug] = *(const f32x4*)(wbase + ug * 256);
-            ML_PIN();
+          for (int tt = 0; tt < 2; ++tt) {
+            const int t = 2 * tp + tt;
+            f32x16 gp;
 #pragma unroll
-            for (int ug = 0; ug < KB2; ++ug) {
-              const int c = ug >> 2, q = ug & 3;
-              if (ug + 3 < KB2) { wb[ug + 3] = *(const f32x4*)(wbase + (ug + 3) * 256); ML_PIN(); }
-              gp = ML_MFMA(wb[ug].x, zp[c][4 * q + 0], gp);
-              gp = ML_MFMA(wb[ug].y, zp[c][4 * q + 1], gp);
-              gp = ML_MFMA(wb[ug].z, zp[c][4 * q + 2], gp);
-              gp = ML_MFMA(wb[ug].w, zp[c][4 * q + 3], gp);
+            for (int r = 0; r < 16; ++r) gp[r] = 0.f;
+            {
+              // weights from LDS, requested three k-blocks ahead and pinned there (the one-ahead form was collapsed by the compiler
+              // to "ds_read, wait, four MFMAs": a derivative task alone on its SIMD then waits out the LDS round trip of every k-block)
+              const float* wbase = sW2 + ((int64_t)t * KB2 * 64 + lane) * 4;
+              f32x4 wb[KB2];
+#pragma unroll
+              for (int ug = 0; ug < 3; ++ug) wb[ug] = *(const f32x4*)(wbase + ug * 256);
+              ML_PIN();
+#pragma unroll
+              for (int ug = 0; ug < KB2; ++ug) {
+                const int c = ug >> 2, q = ug & 3;
+                if (ug + 3 < KB2) { wb[ug + 3] = *(const f32x4*)(wbase + (ug + 3) * 256); ML_PIN(); }
+                gp = ML_MFMA(wb[ug].x, zp[c][4 * q + 0], gp);
+                gp = ML_MFMA(wb[ug].y, zp[c][4 * q + 1], gp);
+                gp = ML_MFMA(wb[ug].z, zp[c][4 * q + 2], gp);
+                gp = ML_MFMA(wb[ug].w, zp[c][4 * q + 3], gp);
+              }
+            }
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+              const int col = 32 * t + 8 * q;
+              const f32x4 gyi = *(const f32x4*)(gyi_p + col), gyj = *(const f32x4*)(gyj_p + col);
+              const f32x4 hvi = *(const f32x4*)(hi_p + col), hvj = *(const f32x4*)(hj_p + col);
+              const f32x4 gq = gl[tt][q];
+              const float D0 = gp[4 * q] * fc + gq.x * dfc, D1 = gp[4 * q + 1] * fc + gq.y * dfc;
+              const float D2 = gp[4 * q + 2] * fc + gq.z * dfc, D3 = gp[4 * q + 3] * fc + gq.w * dfc;
+              s1 += gyi.x * hvj.x * D0 + gyi.y * hvj.y * D1 + gyi.z * hvj.z * D2 + gyi.w * hvj.w * D3;
+              s2 += gyj.x * hvi.x * D0 + gyj.y * hvi.y * D1 + gyj.z * hvi.z * D2 + gyj.w * hvi.w * D3;
             }
           }
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const int col = 32 * t + 8 * q;
-            const f32x4 gyi = *(const f32x4*)(gyi_p + col), gyj = *(const f32x4*)(gyj_p + col);
-            const f32x4 hvi = *(const f32x4*)(hi_p + col), hvj = *(const f32x4*)(hj_p + col);
-            const f32x4 gq = gl[tt][q];
-            const float D0 = gp[4 * q] * fc + gq.x * dfc, D1 = gp[4 * q + 1] * fc + gq.y * dfc;
-            const float D2 = gp[4 * q + 2] * fc + gq.z * dfc, D3 = gp[4 * q + 3] * fc + gq.w * dfc;
-            s1 += gyi.x * hvj.x * D0 + gyi.y * hvj.y * D1 + gyi.z * hvj.z * D2 + gyi.w * hvj.w * D3;
-            s2 += gyj.x * hvi.x * D0 + gyj.y * hvi.y * D1 + gyj.z * hvi.z * D2 + gyj.w * hvi.w * D3;
-          }
+          // one partial per channel-tile pair, added in the order tp = 0, 1 (the LDS operations of a wave stay in order): with one
+          // task per tile the sum of a pair is built by one wave in one order
+          s1 += __shfl_xor(s1, 32, 64);
+          s2 += __shfl_xor(s2, 32, 64);
+          if (hi == 0 && valid) { atomicAdd(sums, s1); atomicAdd(sums + 1, s2); }
         }
         }
-        s1 += __shfl_xor(s1, 32, 64);
-        s2 += __shfl_xor(s2, 32, 64);
-        if (hi == 0 && valid) { atomicAdd(&sS[2 * pl], s1); atomicAdd(&sS[2 * pl + 1], s2); }
       }
       ML_STAMP(35 + 6 * (Ltop - l));
       __syncthreads();
@@ -1488,6 +1527,7 @@ int spk_schnet_mol_backward_ex(const spk_schnet_t* m, const spk_graph_t* g, cons
   a.rb = spk_radial_dev(rb);
   a.compact = 1;
   a.dbg = g_mol_dbg;
+  a.task_split = g_mol_bwd_task_split;
   switch ((rb->n_rbf + 7) / 8) {
     case 1: return launch_mol_bwd<1>(a, stream);
     case 2: return launch_mol_bwd<2>(a, stream);
