@@ -233,6 +233,29 @@ int64_t spk_edge_virial_workspace_bytes(const spk_graph_t* g, int64_t n_mol, int
 int spk_edge_virial_f32(const float* gr, const float* R, const float* offsets, const spk_graph_t* g, const int64_t* idx_m, int64_t n_mol,
                         float* W, float* W_atom, void* workspace, void* stream);
 
+/* ------------------------------------------------------------------ atomistic/nuclear_repulsion.py:70-108 (ZBLRepulsionEnergy)
+ *   a_z = z^p,  a_ij = (a_zi + a_zj) s,  phi(d) = sum_k c_k exp(-a_ij alpha_k d),  e(d) = z_i z_j phi(d) f_c(d) / d,
+ *   E_atom[i] = 1/2 ke sum_{j in row i} e(d_ij),  E[m] = sum_{i in m} E_atom[i].
+ * params: 12 floats in DEVICE memory -- ke, cutoff (0: no cutoff function, f_c = 1), p, s, alpha[4], c[4] -- the effective values (after
+ * softplus; c L1-normalised).  f_c is the cosine cutoff at the term's own radius; pairs at or beyond it contribute exact zeros.  Z in [0, 128):
+ * an atomic number outside gives NaN in that atom's outputs (never an out-of-bounds read); Z = 0 contributes exact zeros.  idx_m ascending.
+ * No float atomics on lists sorted by idx_i, no host synchronisation.  workspace: spk_zbl_workspace_bytes(g, n_mol) bytes.
+ * spk_zbl_fwd_f32: E [n_mol] and E_atom [N] from the pair vectors r_ij [E, 3] (both overwritten; lists that are not sorted land the per-edge
+ * energies with spk_scatter_add_f32).
+ * spk_zbl_bwd_f32: gr [E, 3] = gE[idx_m[idx_i[e]]] 1/2 ke e'(d_e) r_e / d_e, the gradient w.r.t. r_ij that spk_pairwise_bwd_graph_f32 lands on
+ * the atoms and spk_edge_virial_f32 on the virial.
+ * spk_zbl_forces_f32: the fused eval form on a sorted AND symmetric list (others are refused: use the two calls above): E_zbl [n_mol] is
+ * overwritten, F [N, 3] += ke sum_{j in row i} e'(d_ij) r_ij / d_ij and, if W != NULL, W [n_mol, 3, 3] += the virial (as spk_edge_virial_f32
+ * would form it from gr).  Pair vectors are recomputed from R, idx_j and offsets (may be NULL) as spk_pairwise_f32 does.  A row pass: the same
+ * list gives the same bits on every call; an atom without pairs leaves its F untouched. */
+int64_t spk_zbl_workspace_bytes(const spk_graph_t* g, int64_t n_mol);
+int spk_zbl_fwd_f32(const float* r_ij, const int64_t* Z, const spk_graph_t* g, const int64_t* idx_m, int64_t n_mol, const float* params,
+                    float* E, float* E_atom, void* workspace, void* stream);
+int spk_zbl_bwd_f32(const float* gE, const float* r_ij, const int64_t* Z, const spk_graph_t* g, const int64_t* idx_m, int64_t n_mol,
+                    const float* params, float* gr, void* stream);
+int spk_zbl_forces_f32(const float* R, const float* offsets, const int64_t* Z, const spk_graph_t* g, const int64_t* idx_m, int64_t n_mol,
+                       const float* params, float* E_zbl, float* F, float* W, void* workspace, void* stream);
+
 /* ------------------------------------------------------------------ transform/neighborlist.py:438-507
  * (TorchNeighborList) and md/neighborlist_md.py:100-159 -- cell-list neighbour list on the device for
  * a batch of independent systems (molecules / MD replicas).  Result: every DIRECTED pair (i, j, S)
@@ -774,6 +797,9 @@ int spk_painn_potential_gr_f32(const spk_painn_t* m, const spk_head_t* head, con
  *     idx_m change.  host_stats (may be NULL): [0] pairs in the list, [1] 1 if the list was rebuilt by this call.
  * Errors: SPK_ERR_ARG (bad file / unsupported head or shape / atomic number outside the embedding),
  * SPK_ERR_INDEX (neighbour index out of range), SPK_ERR_HIP. */
+/* A file may carry the optional tensor "zbl" (12 floats, the params of spk_zbl_fwd_f32: a model whose energy is the sum of the head and a ZBL
+ * repulsion with a cosine cutoff no wider than the representation's).  Every compute entry point then adds the term's energies to the energy and
+ * its per-edge gradient (spk_zbl_bwd_f32) to dE/dr before forces, virial and per-atom virial are formed. */
 typedef struct spk_potential spk_potential_t;
 int spk_potential_load(const char* path, spk_potential_t** out);
 int spk_potential_from_memory(const void* host_blob, int64_t n_bytes, spk_potential_t** out);

@@ -153,6 +153,10 @@ _PROTOS = {
     "spk_pairwise_bwd_graph_f32": (ctypes.c_int, [c_f, P(GraphT), c_f, c_f]),
     "spk_edge_virial_workspace_bytes": (c_i64, [P(GraphT), c_i64, c_i32]),
     "spk_edge_virial_f32": (ctypes.c_int, [c_f, c_f, c_f, P(GraphT), c_f, c_i64, c_f, c_f, c_f, c_f]),
+    "spk_zbl_workspace_bytes": (c_i64, [P(GraphT), c_i64]),
+    "spk_zbl_fwd_f32": (ctypes.c_int, [c_f, c_f, P(GraphT), c_f, c_i64, c_f, c_f, c_f, c_f, c_f]),
+    "spk_zbl_bwd_f32": (ctypes.c_int, [c_f, c_f, c_f, P(GraphT), c_f, c_i64, c_f, c_f, c_f]),
+    "spk_zbl_forces_f32": (ctypes.c_int, [c_f, c_f, c_f, P(GraphT), c_f, c_i64, c_f, c_f, c_f, c_f, c_f, c_f]),
     "spk_radial_cutoff_f32": (ctypes.c_int, [c_f, c_i64, P(RadialT), c_f, c_f, c_f]),
     "spk_radial_cutoff_bwd_f32": (ctypes.c_int, [c_f, c_i64, P(RadialT), c_f, c_f, c_f, c_f]),
     "spk_edge_norm_f32": (ctypes.c_int, [c_f, c_i64, c_f, c_f, c_f]),

@@ -3,7 +3,8 @@ assembled (and scripted) without the reference package: ``Strain`` (atomistic/re
 (atomistic/distances.py:9-26), ``Atomwise`` (atomistic/atomwise.py:14-88) and ``Forces`` (atomistic/response.py:18-92).  In an integration the
 reference's own modules run unchanged on top of the HIP classes (tests/test_gpu_reference_callers.py) -- they only see
 ``schnetpack.nn.scatter_add`` / ``Dense`` / the representation classes; ``install(fused_head=True)`` swaps in this
-``Atomwise`` for its one-kernel energy head.
+``Atomwise`` for its one-kernel energy head.  ``ZBLRepulsionEnergy`` (atomistic/nuclear_repulsion.py:13-108) and ``Aggregation``
+(atomistic/aggregation.py:9-28) add the short-range nuclear repulsion production potentials carry next to the learned energy.
 """
 from typing import Callable, Dict, Final, List, Optional, Sequence, Union
 
@@ -12,12 +13,13 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib, properties
+from . import units as spk_units
 from . import torchops  # noqa: F401  (registers torch.ops.spk_hip)
-from .nn import Dense, build_mlp, scatter_add
+from .nn import CosineCutoff, Dense, build_mlp, scatter_add
 from .nn.base import activation_id
 from .nn.fallback import note_fallback, use_aten
 
-__all__ = ["Strain", "PairwiseDistances", "Atomwise", "Forces"]
+__all__ = ["Strain", "PairwiseDistances", "Atomwise", "Forces", "ZBLRepulsionEnergy", "Aggregation"]
 
 
 class Strain(nn.Module):
@@ -188,4 +190,158 @@ class Forces(nn.Module):
             cell = inputs[properties.cell]
             volume = torch.sum(cell[:, 0, :] * torch.cross(cell[:, 1, :], cell[:, 2, :], dim=1), dim=1, keepdim=True)[:, :, None]
             inputs[self.stress_key] = stress / volume
+        return inputs
+
+
+def _softplus_inverse(x: torch.Tensor) -> torch.Tensor:
+    """y with softplus(y) = x (nn/activations.py:25-35)."""
+    return x + torch.log(-torch.expm1(-x))
+
+
+class ZBLRepulsionEnergy(nn.Module):
+    """Ziegler-Biersack-Littmark style nuclear repulsion, the reference's formula (atomistic/nuclear_repulsion.py:70-108):
+    ``a_z = z^p``, ``a_ij = (a_zi + a_zj) s``, ``phi = sum_k c_k exp(-a_ij alpha_k d)``, ``E = 1/2 ke sum_pairs z_i z_j phi f_c / d``.
+    Constructor, parameters (``a_pow``, ``a_div``, ``coefficients``, ``exponents``, stored through the inverse softplus) and the buffer
+    ``ke`` are the reference's, so its ``state_dict``s and pickles load.
+
+    In eval mode, on float32 device tensors and with ``cutoff_fn`` None or the mirror ``CosineCutoff``, the energy is ONE operator,
+    ``torch.ops.spk_hip.zbl`` (csrc/spk_zbl.hip), whose backward returns dE/dr_ij -- what ``Forces`` asks for.  Everything else runs
+    the reference's formula on ATen, on whatever device the tensors are on: training mode (gradients w.r.t. the four parameters and
+    the second order ``Forces(create_graph=True)`` needs), host tensors, float64, any other cutoff callable.  Gradients w.r.t. the
+    parameters from the HIP operator are deliberately not provided: a trainable ZBL term trains on the ATen route.
+
+    The operator reads the effective parameters (after softplus / L1 normalisation) from a 12-float device buffer.  ``op_params()`` --
+    host code, run by every eager call of the module or of the fused model route -- rewrites that buffer IN PLACE when a parameter, ``ke``
+    or the radius has changed, so a captured HIP graph, which keeps pointing at the buffer, replays with the new values after ONE such
+    eager call; a bare ``graph.replay()`` straight after a parameter update still reads the old ones.  Moving the module to another device
+    makes a new buffer: capture again.  Under TorchScript the 12 floats are computed in every call, with the cutoff radius the module had
+    when it was scripted (``load_state_dict`` before scripting is seen; a change of ``cutoff_fn.cutoff`` afterwards is not)."""
+
+    _zbl_op: Final[bool]
+
+    def __init__(self, energy_unit: Union[str, float], position_unit: Union[str, float], output_key: str, trainable: bool = True,
+                 cutoff_fn: Optional[Callable] = None, n_molecules_key: str = "_n_molecules"):
+        super().__init__()
+        energy_units = spk_units.convert_units("Ha", energy_unit)
+        position_units = spk_units.convert_units("Bohr", position_unit)
+        ke = energy_units * position_units
+        self.register_buffer("ke", torch.tensor(ke))
+        self.cutoff_fn = cutoff_fn
+        self.output_key = output_key
+        # all quantities have a fixed sign: stored as the inverse softplus, a softplus in forward() restores them
+        a_div = _softplus_inverse(torch.tensor([1.0 / (position_units * 0.8854)]))      # distances can then be used directly
+        a_pow = _softplus_inverse(torch.tensor([0.23]))
+        exponents = _softplus_inverse(torch.tensor([3.19980, 0.94229, 0.40290, 0.20162]))
+        coefficients = _softplus_inverse(torch.tensor([0.18175, 0.50986, 0.28022, 0.02817]))
+        self.a_pow = nn.Parameter(a_pow, requires_grad=trainable)
+        self.a_div = nn.Parameter(a_div, requires_grad=trainable)
+        self.coefficients = nn.Parameter(coefficients, requires_grad=trainable)
+        self.exponents = nn.Parameter(exponents, requires_grad=trainable)
+        self.n_molecules_key = n_molecules_key
+        self._init_operator()
+
+    def _init_operator(self):
+        self._zbl_op = self.cutoff_fn is None or type(self.cutoff_fn) is CosineCutoff
+        self._zbl_rc = float(self.cutoff_fn.cutoff_value()) if type(self.cutoff_fn) is CosineCutoff else 0.0
+        self.register_buffer("_zbl_params", torch.zeros(12), persistent=False)
+        self._zbl_key = None
+
+    def __setstate__(self, state):
+        # a pickle made by the REFERENCE class (torch.save(model)) unpickled onto this one after install() never ran __init__
+        super().__setstate__(state)
+        if "n_molecules_key" not in self.__dict__:
+            self.n_molecules_key = "_n_molecules"
+        if "_zbl_op" not in self.__dict__ or "_zbl_params" not in self._buffers:
+            self._init_operator()
+
+    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
+        super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
+        rc = state_dict.get(prefix + "cutoff_fn.cutoff")          # (children load after this module: read the radius the scripted path uses here)
+        if rc is not None and type(self.cutoff_fn) is CosineCutoff and not rc.is_meta:
+            self._zbl_rc = float(rc.reshape(-1)[0])
+
+    def cutoff_radius(self) -> float:
+        """Radius of the term's own cosine cutoff; 0.0 without a cutoff function."""
+        return self._zbl_rc
+
+    def _params12(self, like: torch.Tensor) -> torch.Tensor:
+        """ke, cutoff (0: none), p, s, alpha[4], c[4] -- the effective values, float32 on the device of ``like``."""
+        c = F.normalize(F.softplus(self.coefficients)[None, :], p=1.0, dim=1)[0]
+        ke = self.ke.reshape(1).to(self.a_pow.dtype)
+        rc = torch.zeros_like(self.a_pow) + self._zbl_rc
+        prm = torch.cat([ke, rc, F.softplus(self.a_pow), F.softplus(self.a_div), F.softplus(self.exponents), c])
+        return prm.detach().to(device=like.device, dtype=torch.float32)
+
+    @torch.jit.unused
+    def op_params(self, like: torch.Tensor) -> torch.Tensor:
+        """The operator's parameter buffer, recomputed (in place: captured graphs keep pointing at it) only when a parameter, ``ke`` or the
+        cutoff radius has changed since the last call."""
+        if type(self.cutoff_fn) is CosineCutoff:
+            self._zbl_rc = float(self.cutoff_fn.cutoff_value())
+        ps = (self.ke, self.a_pow, self.a_div, self.exponents, self.coefficients)
+        key = (self._zbl_rc, str(like.device)) + tuple((t.data_ptr(), t._version) for t in ps)
+        if key != self._zbl_key or self._zbl_params.device != like.device:
+            with torch.no_grad():
+                prm = self._params12(like)
+                if self._zbl_params.device != like.device or self._zbl_params.dtype != torch.float32:
+                    self._zbl_params = prm.clone()
+                else:
+                    self._zbl_params.copy_(prm)
+            self._zbl_key = key
+        return self._zbl_params
+
+    def _n_molecules(self, inputs: Dict[str, torch.Tensor], idx_m: torch.Tensor) -> int:
+        # like Atomwise: a host-side molecule count in the batch avoids the reference's int(idx_m[-1]) + 1 (a device sync)
+        if self.n_molecules_key in inputs:
+            return int(inputs[self.n_molecules_key])
+        return int(idx_m[-1]) + 1
+
+    def forward(self, inputs: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+        z = inputs[properties.Z]
+        r_ij = inputs[properties.Rij]
+        idx_i = inputs[properties.idx_i]
+        idx_j = inputs[properties.idx_j]
+        idx_m = inputs[properties.idx_m]
+        n_molecules = self._n_molecules(inputs, idx_m)
+        if self._zbl_op and not self.training and not use_aten(r_ij):
+            if torch.jit.is_scripting():
+                prm = self._params12(r_ij)
+            else:
+                prm = self.op_params(r_ij)
+            inputs[self.output_key] = torch.ops.spk_hip.zbl(r_ij, z, idx_i, idx_j, idx_m, n_molecules, prm)[0]
+            return inputs
+        if use_aten(r_ij):
+            note_fallback()
+        # the reference's formula (atomistic/nuclear_repulsion.py:70-106), differentiable to any order in positions and parameters
+        d_ij = torch.norm(r_ij, dim=1)
+        n_atoms = z.shape[0]
+        a = z ** F.softplus(self.a_pow)
+        a_ij = (a[idx_i] + a[idx_j]) * F.softplus(self.a_div)
+        exponents = a_ij[..., None] * F.softplus(self.exponents)[None, ...]
+        coefficients = F.softplus(self.coefficients)[None, ...]
+        coefficients = F.normalize(coefficients, p=1.0, dim=1)
+        screening = torch.sum(coefficients * torch.exp(-exponents * d_ij[:, None]), dim=1)
+        repulsion = (z[idx_i] * z[idx_j]) / d_ij
+        if self.cutoff_fn is not None:
+            f_cut = self.cutoff_fn(d_ij)
+            repulsion = repulsion * f_cut
+        y_zbl = scatter_add(repulsion * screening, idx_i, dim_size=n_atoms)
+        y_zbl = scatter_add(y_zbl, idx_m, dim_size=n_molecules)
+        y_zbl = 0.5 * self.ke * y_zbl
+        inputs[self.output_key] = y_zbl
+        return inputs
+
+
+class Aggregation(nn.Module):
+    """Sum of several predictions under one key (atomistic/aggregation.py:9-28), e.g. learned energy + ZBL repulsion -> ``energy``."""
+
+    def __init__(self, keys: List[str], output_key: str = "y"):
+        super().__init__()
+        self.keys: List[str] = list(keys)
+        self.output_key = output_key
+        self.model_outputs = [output_key]
+
+    def forward(self, inputs: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+        energy = torch.stack([inputs[key] for key in self.keys]).sum(0)
+        inputs[self.output_key] = energy
         return inputs

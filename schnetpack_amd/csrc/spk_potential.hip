@@ -39,6 +39,9 @@ struct FileEntry { char name[32]; int64_t n_floats, offset; };
 __global__ void k_fill_f32(float* __restrict__ p, float v, int64_t n) {
   for (int64_t k = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; k < n; k += (int64_t)gridDim.x * blockDim.x) p[k] = v;
 }
+__global__ void k_accumulate_f32(float* __restrict__ y, const float* __restrict__ x, int64_t n) {
+  for (int64_t k = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; k < n; k += (int64_t)gridDim.x * blockDim.x) y[k] += x[k];
+}
 __global__ void k_half_flags(const int32_t* __restrict__ rev, int64_t n, unsigned char* __restrict__ flags) {
   for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x)
     flags[e] = rev[e] > (int32_t)e ? 1 : 0;
@@ -60,7 +63,8 @@ struct spk_potential {
   spk_radial_t rb;
   // per-call device buffers
   DevBuf z, R, ii, jj, off, idxm, rij, rowptr, rev, half, scr, x0, xo, mu, saved, scratch, pre, gx, gE, gr, gR, E, flags, tmp,
-      cell, pbc, nblws, nblrow, shifts, W, Wa, vws;
+      cell, pbc, nblws, nblrow, shifts, W, Wa, vws, zgr, zE, zEa, zws;
+  const float* zbl = nullptr;                            // optional tensor "zbl": the 12 effective ZBL parameters (spk_zbl.hip), NULL: no such term
   // current list
   spk_graph_t g;
   bool cell_list = false;
@@ -157,6 +161,15 @@ int parse_and_upload(spk_potential* p, const unsigned char* blob, int64_t n) {
     p->atomref.resize(h.n_atomref);
     memcpy(p->atomref.data(), blob + data0 + 4 * it->second->offset, 4 * (size_t)h.n_atomref);
   }
+  const bool has_zbl = by_name.find("zbl") != by_name.end();
+  if (has_zbl) {
+    const FileEntry* ze = by_name["zbl"];
+    SPK_CHECK_ARG(ze->n_floats == 12, "spk_potential: tensor zbl has %lld floats, expected 12", (long long)ze->n_floats);
+    float zp[12];
+    memcpy(zp, blob + data0 + 4 * ze->offset, sizeof(zp));
+    // the runtime builds its list at the representation's cutoff: the term needs a cutoff function whose radius lies inside it
+    SPK_CHECK_ARG(zp[1] > 0.f && zp[1] <= h.cutoff, "spk_potential: ZBL radius %g outside (0, %g] (the cutoff of the list)", (double)zp[1], (double)h.cutoff);
+  }
   SPK_CHECK_ARG(spk_atomwise_supported(h.F, h.head_hidden, h.head_act), "spk_potential: head %d -> %d (activation %d) has no fused kernel",
                 h.F, h.head_hidden, h.head_act);
   // host image = file data + transposed copies, one upload
@@ -176,6 +189,7 @@ int parse_and_upload(spk_potential* p, const unsigned char* blob, int64_t n) {
     cur += (nd.n + 15) / 16 * 16;
   }
   SPK_HIP_TRY(hipMemcpy(p->d_w, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice));
+  if (has_zbl) p->zbl = p->t.at("zbl");
   // parameter blocks
   auto T = [&](const std::string& s) { return p->t.at(s); };
   p->rb.kind = h.rbf_kind; p->rb.n_rbf = h.n_rbf; p->rb.p0 = T("rbf_p0"); p->rb.p1 = T("rbf_p1"); p->rb.cutoff = h.cutoff;
@@ -333,6 +347,27 @@ int run_model(spk_potential* p, int64_t N, int64_t E, int64_t M, bool new_list, 
     rc = spk_painn_backward_f32(&p->pm, g, &p->rb, p->gx.as<float>(), nullptr, p->rij.as<float>(), p->saved.as<float>(), p->scratch.as<float>(),
                                 p->gr.as<float>(), nullptr, s);
   if (rc) return rc;
+  if (p->zbl) {
+    // ZBL repulsion aggregated into the energy: its energies into E and its per-edge gradient into dE/dr, which the landing kernels below
+    // put on the atoms, the virial and the per-atom virial like the learned part (any list: sorted or not, with or without a skin)
+    const int64_t zb = spk_zbl_workspace_bytes(g, M);
+    SPK_CHECK_ARG(zb >= 0, "spk_potential: bad list for the ZBL term");
+    if ((rc = p->zws.ensure((size_t)std::max<int64_t>(zb, 1)))) return rc;
+    if ((rc = p->zE.ensure((size_t)M * 4))) return rc;
+    if ((rc = p->zEa.ensure((size_t)N * 4))) return rc;
+    if ((rc = spk_zbl_fwd_f32(E > 0 ? p->rij.as<float>() : nullptr, p->z.as<int64_t>(), g, p->idxm.as<int64_t>(), M, p->zbl, p->zE.as<float>(),
+                              p->zEa.as<float>(), p->zws.p, s)))
+      return rc;
+    hipLaunchKernelGGL(k_accumulate_f32, dim3(spk_grid_for(M, 256, 1024)), dim3(256), 0, s, p->E.as<float>(), p->zE.as<float>(), M);
+    SPK_LAUNCH_CHECK();
+    if (E > 0) {
+      if ((rc = p->zgr.ensure((size_t)E * 12))) return rc;
+      if ((rc = spk_zbl_bwd_f32(p->gE.as<float>(), p->rij.as<float>(), p->z.as<int64_t>(), g, p->idxm.as<int64_t>(), M, p->zbl, p->zgr.as<float>(), s)))
+        return rc;
+      hipLaunchKernelGGL(k_accumulate_f32, dim3(spk_grid_for(3 * E, 256, spk_num_cus() * 16)), dim3(256), 0, s, p->gr.as<float>(), p->zgr.as<float>(), 3 * E);
+      SPK_LAUNCH_CHECK();
+    }
+  }
   if ((rc = spk_pairwise_bwd_graph_f32(p->gr.as<float>(), g, p->gR.as<float>(), s))) return rc;
   if (host_virial || host_atom_virial) {
     const int64_t vb = spk_edge_virial_workspace_bytes(g, M, host_atom_virial ? 1 : 0);
@@ -429,7 +464,7 @@ extern "C" void spk_potential_free(spk_potential_t* p) {
   if (p->stream) (void)hipStreamSynchronize(p->stream);
   DevBuf* bufs[] = {&p->z, &p->R, &p->ii, &p->jj, &p->off, &p->idxm, &p->rij, &p->rowptr, &p->rev, &p->half, &p->scr, &p->x0, &p->xo, &p->mu,
                     &p->saved, &p->scratch, &p->pre, &p->gx, &p->gE, &p->gr, &p->gR, &p->E, &p->flags, &p->tmp, &p->cell, &p->pbc, &p->W, &p->Wa, &p->vws, &p->nblws,
-                    &p->nblrow, &p->shifts};
+                    &p->nblrow, &p->shifts, &p->zgr, &p->zE, &p->zEa, &p->zws};
   for (DevBuf* b : bufs) b->release();
   if (p->wpack) (void)hipFree(p->wpack);
   if (p->d_w) (void)hipFree(p->d_w);

@@ -977,6 +977,86 @@ Tensor edge_virial_raw(const Tensor& gr, const Tensor& R, const Tensor& off, con
   return W;
 }
 
+// ZBL nuclear repulsion (atomistic/nuclear_repulsion.py:70-108; csrc/spk_zbl.hip).  params: the 12 effective parameters as a float32 DEVICE
+// tensor (ke, cutoff or 0, p, s, alpha[4], c[4]): a replayed graph reads what the host last wrote there.
+Tensor zbl_params(const Tensor& params, const char* who) {
+  Tensor p = f32(params.detach(), who);
+  TORCH_CHECK(p.numel() == 12, who, ": params = [ke, cutoff (0: none), a_pow, a_div, exponents[4], coefficients[4]] (12 floats), got ", p.sizes());
+  return p;
+}
+Tensor zbl_workspace(const spk_graph_t& g, int64_t n_mol, const Tensor& like) {
+  const int64_t bytes = spk_zbl_workspace_bytes(&g, n_mol);
+  TORCH_CHECK(bytes >= 0, "zbl: bad list");
+  return at::empty({std::max<int64_t>(1, bytes)}, like.options().dtype(at::kByte));
+}
+std::tuple<Tensor, Tensor> zbl_forward_raw(const Tensor& r_in, const Tensor& Z_in, const Tensor& idx_i, const Tensor& idx_j, const Tensor& idx_m_in,
+                                           int64_t n_mol, const Tensor& params) {
+  const char* who = "zbl";
+  Tensor r = f32(r_in.detach(), who), Z = i64(Z_in, who), idx_m = i64(idx_m_in, who), prm = zbl_params(params, who);
+  const int64_t N = Z.size(0);
+  TORCH_CHECK(r.dim() == 2 && r.size(1) == 3 && r.size(0) == idx_i.size(0) && idx_m.size(0) == N && n_mol >= 0, who, ": r_ij [E, 3], Z / idx_m [N]");
+  c10::DeviceGuard guard(r.device());
+  Tensor E = at::empty({n_mol}, r.options()), Ea = at::empty({N}, r.options());
+  auto plan = get_plan(idx_i, idx_j, N, r);
+  spk_graph_t g = plan->graph();
+  Tensor ws = zbl_workspace(g, n_mol, r);
+  check(spk_zbl_fwd_f32(r.numel() ? fp(r) : nullptr, N ? Z.data_ptr<int64_t>() : nullptr, &g, N ? idx_m.data_ptr<int64_t>() : nullptr, n_mol, fp(prm),
+                        n_mol ? fpm(E) : nullptr, N ? fpm(Ea) : nullptr, ws.data_ptr(), stream_of(r)));
+  return {E, Ea};
+}
+Tensor zbl_backward_raw(const Tensor& gE_in, const Tensor& r_in, const Tensor& Z_in, const Tensor& idx_i, const Tensor& idx_j, const Tensor& idx_m_in,
+                        int64_t n_mol, const Tensor& params) {
+  const char* who = "zbl_backward";
+  Tensor gE = f32(gE_in, who), r = f32(r_in.detach(), who), Z = i64(Z_in, who), idx_m = i64(idx_m_in, who), prm = zbl_params(params, who);
+  const int64_t N = Z.size(0);
+  TORCH_CHECK(gE.numel() == n_mol && r.dim() == 2 && r.size(1) == 3 && r.size(0) == idx_i.size(0) && idx_m.size(0) == N, who, ": gE [n_mol], r_ij [E, 3]");
+  c10::DeviceGuard guard(r.device());
+  Tensor gr = at::empty_like(r);
+  if (r.size(0) == 0) return gr;
+  auto plan = get_plan(idx_i, idx_j, N, r);
+  spk_graph_t g = plan->graph();
+  check(spk_zbl_bwd_f32(fp(gE), fp(r), Z.data_ptr<int64_t>(), &g, idx_m.data_ptr<int64_t>(), n_mol, fp(prm), fpm(gr), stream_of(r)));
+  return gr;
+}
+// Eval-only accumulate form: E_zbl [n_mol]; F [N, 3] and (if given) W [n_mol, 3, 3] are ADDED to in place.  Sorted symmetric lists: one row pass
+// (spk_zbl_forces_f32); every other list: spk_zbl_fwd_f32 / spk_zbl_bwd_f32 and the general landing kernels.
+Tensor zbl_forces_raw(const Tensor& R_in, const c10::optional<Tensor>& offsets_in, const Tensor& Z_in, const Tensor& idx_i, const Tensor& idx_j,
+                      const Tensor& idx_m_in, int64_t n_mol, const Tensor& params, Tensor F, c10::optional<Tensor> W_in) {
+  const char* who = "zbl_forces";
+  Tensor R = f32(R_in.detach(), who), off = opt_f32(offsets_in, who), Z = i64(Z_in, who), idx_m = i64(idx_m_in, who), prm = zbl_params(params, who);
+  const int64_t N = R.size(0);
+  Tensor W = (W_in.has_value() && W_in->defined()) ? *W_in : Tensor();
+  require_device(F, who);
+  TORCH_CHECK(F.scalar_type() == at::kFloat && F.is_contiguous() && F.dim() == 2 && F.size(0) == N && F.size(1) == 3, who, ": F must be a contiguous float32 [N, 3] tensor");
+  if (W.defined()) {
+    require_device(W, who);
+    TORCH_CHECK(W.scalar_type() == at::kFloat && W.is_contiguous() && W.numel() == n_mol * 9, who, ": W must be a contiguous float32 [n_mol, 3, 3] tensor");
+  }
+  TORCH_CHECK(Z.size(0) == N && idx_m.size(0) == N && n_mol >= 0, who, ": Z / idx_m [N]");
+  c10::DeviceGuard guard(R.device());
+  c10::optional<Tensor> off_d = off.defined() ? c10::optional<Tensor>(off) : c10::optional<Tensor>();
+  auto plan = find_plan(idx_i, idx_j, N);
+  Tensor r;
+  if (!plan) {
+    r = pairwise_raw(R, idx_i, idx_j, off_d);
+    plan = get_plan(idx_i, idx_j, N, r);
+  }
+  spk_graph_t g = plan->graph();
+  Tensor E = at::empty({n_mol}, R.options());
+  if (plan->n_edges == 0 || (plan->sorted && plan->symmetric)) {
+    Tensor ws = zbl_workspace(g, n_mol, R);
+    check(spk_zbl_forces_f32(fp(R), fp(off), N ? Z.data_ptr<int64_t>() : nullptr, &g, N ? idx_m.data_ptr<int64_t>() : nullptr, n_mol, fp(prm),
+                             n_mol ? fpm(E) : nullptr, fpm(F), W.defined() ? fpm(W) : nullptr, ws.data_ptr(), stream_of(R)));
+    return E;
+  }
+  if (!r.defined()) r = pairwise_raw(R, idx_i, idx_j, off_d);
+  E = std::get<0>(zbl_forward_raw(r, Z, idx_i, idx_j, idx_m, n_mol, prm));
+  Tensor gr = zbl_backward_raw(at::ones({n_mol}, R.options()), r, Z, idx_i, idx_j, idx_m, n_mol, prm);
+  F.sub_(pairwise_bwd_raw(gr, idx_i, idx_j, N));
+  if (W.defined()) W.add_(edge_virial_raw(gr, R, off, *plan, idx_m, n_mol).view(W.sizes()));
+  return E;
+}
+
 // Energies, forces AND the virial W = dE/dS of the strain (Strain -> ... -> Forces(calc_stress=True), atomistic/response.py:434-464) for eval:
 // (E, F = -dE/dR, W [n_mol, 3, 3], scalar_representation), no autograd node.  E and F are those of schnet_potential_forces bit for bit: the same
 // two launches (the backward also writes dE/dr of every edge) or the same three stages (whose dE/dr is kept), plus the virial launches.
@@ -1458,10 +1538,48 @@ struct AtomwiseFn : public torch::autograd::Function<AtomwiseFn> {
   }
 };
 
+// ZBL repulsion: first-order gradient w.r.t. the pair vectors (what Forces asks for in eval mode); the parameters get none
+std::tuple<Tensor, Tensor> call_zbl(const Tensor& r, const Tensor& Z, const Tensor& ii, const Tensor& jj, const Tensor& idx_m, int64_t n_mol, const Tensor& prm) {
+  static auto op = op_handle<std::tuple<Tensor, Tensor>(const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, int64_t, const Tensor&)>("spk_hip::zbl");
+  return op.call(r, Z, ii, jj, idx_m, n_mol, prm);
+}
+Tensor call_zbl_backward(const Tensor& gE, const Tensor& r, const Tensor& Z, const Tensor& ii, const Tensor& jj, const Tensor& idx_m, int64_t n_mol, const Tensor& prm) {
+  static auto op = op_handle<Tensor(const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, int64_t, const Tensor&)>("spk_hip::zbl_backward");
+  return op.call(gE, r, Z, ii, jj, idx_m, n_mol, prm);
+}
+const char* kZblFirstOrder =
+    "spk_hip::zbl: the operator returns first-order gradients w.r.t. the pair vectors only -- a recorded backward (create_graph=True) or a gradient "
+    "w.r.t. the per-atom energies was requested.  Put the module in training mode (module.train()): ZBLRepulsionEnergy then runs the reference's "
+    "formula on ATen, differentiable to any order in the positions and in its parameters.";
+struct ZblFn : public torch::autograd::Function<ZblFn> {
+  static variable_list forward(AutogradContext* ctx, const Tensor& r, const Tensor& Z, const Tensor& ii, const Tensor& jj, const Tensor& idx_m,
+                               int64_t n_mol, const Tensor& prm) {
+    at::AutoDispatchBelowADInplaceOrView guard;
+    ctx->set_materialize_grads(false);       // an unused E_atom must arrive undefined, not as zeros
+    auto out = call_zbl(r, Z, ii, jj, idx_m, n_mol, prm);
+    ctx->save_for_backward({r, Z, ii, jj, idx_m, prm});
+    ctx->saved_data["n_mol"] = n_mol;
+    return {std::get<0>(out), std::get<1>(out)};
+  }
+  static variable_list backward(AutogradContext* ctx, variable_list grads) {
+    TORCH_CHECK(!at::GradMode::is_enabled(), kZblFirstOrder);
+    TORCH_CHECK(!grads[1].defined(), kZblFirstOrder);
+    auto sv = ctx->get_saved_variables();
+    Tensor gr;
+    if (ctx->needs_input_grad(0) && grads[0].defined())
+      gr = call_zbl_backward(grads[0], sv[0], sv[1], sv[2], sv[3], sv[4], ctx->saved_data["n_mol"].toInt(), sv[5]);
+    return {gr, Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
+  }
+};
+
 // ------------------------------------------------------------------------------------------------ operator entry points
 // --- Autograd key
 Tensor scatter_add_ad(const Tensor& x, const Tensor& idx, int64_t dim_size, int64_t dim) { return ScatterAddFn::apply(x, idx, dim_size, dim); }
 Tensor gather_ad(const Tensor& x, const Tensor& idx, int64_t dim) { return GatherFn::apply(x, idx, dim); }
+std::tuple<Tensor, Tensor> zbl_ad(const Tensor& r, const Tensor& Z, const Tensor& ii, const Tensor& jj, const Tensor& idx_m, int64_t n_mol, const Tensor& prm) {
+  auto o = ZblFn::apply(r, Z, ii, jj, idx_m, n_mol, prm);
+  return {o[0], o[1]};
+}
 Tensor pairwise_ad(const Tensor& R, const Tensor& ii, const Tensor& jj, const c10::optional<Tensor>& off) { return PairwiseFn::apply(R, ii, jj, off); }
 Tensor pairwise_backward_ad(const Tensor& gr, const Tensor& ii, const Tensor& jj, int64_t n) { return PairwiseBwdFn::apply(gr, ii, jj, n); }
 Tensor dense_ad(const Tensor& x, const Tensor& w, const c10::optional<Tensor>& b, int64_t act) { return DenseFn::apply(x, w, b, act)[0]; }
@@ -1797,6 +1915,14 @@ Tensor gather_meta(const Tensor& x, const Tensor& idx, int64_t dim) {
   shape[at::maybe_wrap_dim(dim, x.dim())] = idx.size(0);
   return at::empty(shape, x.options());
 }
+std::tuple<Tensor, Tensor> zbl_meta(const Tensor& r, const Tensor& Z, const Tensor&, const Tensor&, const Tensor&, int64_t n_mol, const Tensor&) {
+  return {at::empty({n_mol}, r.options()), at::empty({Z.size(0)}, r.options())};
+}
+Tensor zbl_backward_meta(const Tensor&, const Tensor& r, const Tensor&, const Tensor&, const Tensor&, const Tensor&, int64_t, const Tensor&) { return at::empty_like(r); }
+Tensor zbl_forces_meta(const Tensor& R, const c10::optional<Tensor>&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, int64_t n_mol, const Tensor&, Tensor,
+                       c10::optional<Tensor>) {
+  return at::empty({n_mol}, R.options());
+}
 Tensor pairwise_meta(const Tensor& R, const Tensor& ii, const Tensor&, const c10::optional<Tensor>&) { return at::empty({ii.size(0), 3}, R.options()); }
 Tensor pairwise_backward_meta(const Tensor& gr, const Tensor&, const Tensor&, int64_t n) { return at::empty({n, 3}, gr.options()); }
 Tensor dense_meta(const Tensor& x, const Tensor& w, const c10::optional<Tensor>&, int64_t) {
@@ -1875,6 +2001,10 @@ TORCH_LIBRARY(spk_hip, m) {
   m.def("painn_potential_forces(Tensor? q0, Tensor? embedding, Tensor Z, Tensor R, Tensor? offsets, Tensor idx_i, Tensor idx_j, Tensor idx_m, int n_mol, Tensor[] weights, Tensor[] head, bool shared_filters, float epsilon, int rbf_kind, Tensor rbf_p0, Tensor? rbf_p1, float cutoff, int head_act) -> (Tensor, Tensor, Tensor, Tensor)");  // eval: (E, forces, scalar_representation, vector_representation), no autograd
   m.def("schnet_potential_stress(Tensor? x0, Tensor? embedding, Tensor Z, Tensor R, Tensor? offsets, Tensor idx_i, Tensor idx_j, Tensor idx_m, int n_mol, Tensor[] weights, Tensor[] head, int n_filters, int rbf_kind, Tensor rbf_p0, Tensor? rbf_p1, float cutoff, int head_act) -> (Tensor, Tensor, Tensor, Tensor)");  // eval: (E, forces, virial [n_mol, 3, 3], scalar_representation), no autograd
   m.def("painn_potential_stress(Tensor? q0, Tensor? embedding, Tensor Z, Tensor R, Tensor? offsets, Tensor idx_i, Tensor idx_j, Tensor idx_m, int n_mol, Tensor[] weights, Tensor[] head, bool shared_filters, float epsilon, int rbf_kind, Tensor rbf_p0, Tensor? rbf_p1, float cutoff, int head_act) -> (Tensor, Tensor, Tensor, Tensor, Tensor)");  // eval: (E, forces, virial, scalar_representation, vector_representation)
+  // atomistic/nuclear_repulsion.py:70-108: (E [n_mol], E_atom [N]); params = 12 effective floats on the device (csrc/spk_zbl.hip)
+  m.def("zbl(Tensor r_ij, Tensor Z, Tensor idx_i, Tensor idx_j, Tensor idx_m, int n_mol, Tensor params) -> (Tensor, Tensor)");
+  m.def("zbl_backward(Tensor gE, Tensor r_ij, Tensor Z, Tensor idx_i, Tensor idx_j, Tensor idx_m, int n_mol, Tensor params) -> Tensor");
+  m.def("zbl_forces(Tensor R, Tensor? offsets, Tensor Z, Tensor idx_i, Tensor idx_j, Tensor idx_m, int n_mol, Tensor params, Tensor(a!) F, Tensor(b!)? W) -> Tensor");  // eval: E_zbl; F, W += in place
   m.def("potential_plan(Tensor idx_i, Tensor idx_j, int n_atoms, Tensor idx_m, int n_mol) -> int");
   m.def("eval_guard(Tensor(a) y, Tensor[] params) -> Tensor(a)");      // alias of y whose backward raises the eval-only message
   m.def("schnet_potential_forward(Tensor x0, Tensor R, Tensor? offsets, Tensor idx_i, Tensor idx_j, Tensor idx_m, int n_mol, Tensor[] weights, Tensor[] head, int n_filters, int rbf_kind, Tensor rbf_p0, Tensor? rbf_p1, float cutoff, int head_act) -> (Tensor, Tensor, Tensor, Tensor)");
@@ -1925,6 +2055,9 @@ TORCH_LIBRARY_IMPL(spk_hip, CUDA, m) {   // "CUDA" is the dispatch key of ROCm d
   m.impl("schnet_potential_stress", schnet_potential_stress_raw);
   m.impl("painn_potential_stress", painn_potential_stress_raw);
   m.impl("eval_guard", eval_guard_dev);
+  m.impl("zbl", zbl_forward_raw);
+  m.impl("zbl_backward", zbl_backward_raw);
+  m.impl("zbl_forces", zbl_forces_raw);
   m.impl("potential_plan", potential_plan_op);
   m.impl("schnet_potential_backward", schnet_potential_backward_raw);
   m.impl("dense_forward", dense_raw);
@@ -1957,6 +2090,7 @@ TORCH_LIBRARY_IMPL(spk_hip, Autograd, m) {
   m.impl("atomwise", atomwise_ad);
   m.impl("schnet_potential", schnet_potential_ad);
   m.impl("eval_guard", eval_guard_ad);
+  m.impl("zbl", zbl_ad);
   train_impl_autograd(m);
   fm_impl_autograd(m);
 }
@@ -1966,7 +2100,7 @@ TORCH_LIBRARY_IMPL(spk_hip, CPU, m) {
                            "dense_forward", "dense_backward_input", "radial_cutoff_backward", "schnet_forward", "schnet_backward", "painn_forward",
                            "painn_backward", "atomwise_forward", "atomwise_backward", "edge_plan", "static_declare", "static_declare_range", "schnet_potential",
                            "schnet_potential_forward", "schnet_potential_backward", "schnet_potential_forces", "painn_potential_forces", "potential_plan",
-                           "schnet_potential_stress", "painn_potential_stress"})
+                           "schnet_potential_stress", "painn_potential_stress", "zbl", "zbl_backward", "zbl_forces"})
     m.impl(name, torch::CppFunction::makeFromBoxedFunction<&no_cpu_boxed>());
   for (const char* name : kTrainOps) m.impl(name, torch::CppFunction::makeFromBoxedFunction<&no_cpu_boxed>());
   for (const char* name : kFmOps) m.impl(name, torch::CppFunction::makeFromBoxedFunction<&no_cpu_boxed>());
@@ -1999,6 +2133,9 @@ TORCH_LIBRARY_IMPL(spk_hip, Meta, m) {
   m.impl("painn_potential_stress", painn_potential_stress_meta);
   m.impl("eval_guard", eval_guard_dev);
   m.impl("schnet_potential_backward", schnet_potential_backward_meta);
+  m.impl("zbl", zbl_meta);
+  m.impl("zbl_backward", zbl_backward_meta);
+  m.impl("zbl_forces", zbl_forces_meta);
   train_impl_meta(m);
   fm_impl_meta(m);
 }

@@ -17,7 +17,9 @@ atomref rows, n_tensors, 3 reserved); 4 float32 (cutoff, epsilon, energy mean, r
 (32-byte zero padded name, int64 n_floats, int64 offset in floats from the data start); padding to a multiple of
 64 bytes; the fp32 data.  Tensor names are the field names of ``spk_schnet_layer_t`` / ``spk_painn_layer_t``
 prefixed with ``l<k>.``, plus ``embedding``, ``rbf_p0``, ``rbf_p1``, ``filt_w``, ``filt_b`` (PaiNN),
-``head_w1``, ``head_b1``, ``head_w2``, ``head_b2`` and ``atomref``.
+``head_w1``, ``head_b1``, ``head_w2``, ``head_b2``, ``atomref`` and, for a model whose energy is the ``Aggregation`` of the head and a
+``ZBLRepulsionEnergy``, the optional ``zbl`` (12 floats: ke, cutoff, a_pow, a_div, exponents[4], coefficients[4], effective values); the runtime
+adds the term's energies and its per-edge gradient before forces and virial are formed.
 """
 import ctypes
 import struct
@@ -45,7 +47,7 @@ def _find_head(model):
     head, frc = heads[0], forces[0]
     if getattr(head, "aggregation_mode", "sum") != "sum" or getattr(head, "n_out", 1) != 1:
         raise ValueError("deploy: only a summed scalar Atomwise head is supported")
-    if getattr(frc, "energy_key", "energy") != getattr(head, "output_key", "energy"):
+    if getattr(frc, "energy_key", "energy") != getattr(head, "output_key", "energy") and _find_zbl(model, head) is None:
         raise ValueError("deploy: Forces must differentiate the Atomwise output")
     if getattr(frc, "calc_stress", False):
         # Strain -> ... -> Forces(calc_stress=True): the virial comes from the same per-edge gradient (spk_potential_compute*_virial), the
@@ -53,6 +55,46 @@ def _find_head(model):
         if not getattr(frc, "calc_forces", True) or not any(type(m).__name__ == "Strain" for m in getattr(model, "input_modules", [])):
             raise ValueError("deploy: stress needs forces and a Strain input module")
     return head
+
+
+def _find_zbl(model, head):
+    """The ``ZBLRepulsionEnergy`` of the composition head + ZBL -> ``Aggregation`` of exactly their two keys -> ``Forces`` of the aggregated
+    key (``model.classify_potential`` 4 / 5), or None when ``Forces`` differentiates the head's own output."""
+    outs = list(model.output_modules)
+    zbls = [m for m in outs if type(m).__name__ == "ZBLRepulsionEnergy"]
+    aggs = [m for m in outs if type(m).__name__ == "Aggregation"]
+    forces = [m for m in outs if type(m).__name__ == "Forces"]
+    if len(zbls) != 1 or len(aggs) != 1 or len(forces) != 1 or len(outs) != 4:
+        return None
+    zbl, agg, frc = zbls[0], aggs[0], forces[0]
+    keys = sorted([getattr(head, "output_key", "energy"), zbl.output_key])
+    if keys[0] == keys[1] or sorted(agg.keys) != keys or frc.energy_key != agg.output_key or agg.output_key in keys:
+        return None
+    if outs.index(agg) != 2 or outs.index(frc) != 3:
+        return None
+    return zbl
+
+
+def _zbl_params(zbl, rep_cutoff):
+    """The 12 floats of the optional tensor ``zbl``: ke, cutoff, a_pow, a_div, exponents[4], coefficients[4] -- the effective values (after
+    softplus, coefficients L1-normalised; csrc/spk_zbl.hip).  The runtime builds its neighbour list at the representation's cutoff, so the
+    term must carry a cosine cutoff whose radius lies inside it."""
+    import torch
+    import torch.nn.functional as F
+    cut = getattr(zbl, "cutoff_fn", None)
+    if cut is None:
+        raise ValueError("deploy: a ZBL term without a cutoff function counts every delivered pair; the runtime's list ends at the "
+                         "representation's cutoff -- give ZBLRepulsionEnergy a CosineCutoff")
+    if type(cut).__name__ != "CosineCutoff" or not hasattr(cut, "cutoff"):
+        raise ValueError("deploy: the ZBL term's cutoff function %s is not CosineCutoff (the only one the kernels evaluate)" % type(cut).__name__)
+    rc = float(cut.cutoff.detach().reshape(-1)[0])
+    if not (0.0 < rc <= float(rep_cutoff)):
+        raise ValueError("deploy: the ZBL radius %g exceeds the representation's cutoff %g, where the runtime's neighbour list ends" % (rc, rep_cutoff))
+    with torch.no_grad():
+        c = F.softplus(zbl.coefficients.detach().double())
+        vals = [zbl.ke.detach().double().reshape(1), torch.tensor([rc], dtype=torch.float64), F.softplus(zbl.a_pow.detach().double()).reshape(1),
+                F.softplus(zbl.a_div.detach().double()).reshape(1), F.softplus(zbl.exponents.detach().double()).reshape(4), (c / c.abs().sum()).reshape(4)]
+        return torch.cat([v.cpu() for v in vals]).float().numpy()
 
 
 def _offsets_of(model, energy_key):
@@ -135,11 +177,15 @@ def export_potential(model, path: Optional[str] = None) -> bytes:
     tensors["head_b1"] = _np(net[0].bias) if net[0].bias is not None else np.zeros(H, np.float32)
     tensors["head_w2"] = _np(net[1].weight).reshape(-1)
     tensors["head_b2"] = _np(net[1].bias).reshape(-1) if net[1].bias is not None else np.zeros(1, np.float32)
-    mean, ext, atomref = _offsets_of(model, head.output_key)
+    zbl = _find_zbl(model, head)
+    frc = [m for m in model.output_modules if type(m).__name__ == "Forces"][0]
+    mean, ext, atomref = _offsets_of(model, frc.energy_key if zbl is not None else head.output_key)
     n_atomref = 0
     if atomref is not None:
         tensors["atomref"] = atomref.astype(np.float32)
         n_atomref = int(atomref.shape[0])
+    if zbl is not None:       # optional tensor: a file of a model without the term is what it always was
+        tensors["zbl"] = _zbl_params(zbl, cutoff)
     names = list(tensors)
     ints = [VERSION, kind, F, nf, L, int(n_rbf), int(rbk), H, int(head_act), int(tensors["embedding"].shape[0]),
             ext, n_atomref, len(names), 0, 0, 0]

@@ -6,7 +6,8 @@
 Patches, inside the already imported ``schnetpack`` package, exactly the names of SURVEY.md
 section 8(b): ``nn.scatter_add`` (+ ``nn.scatter.scatter_add``), ``nn.Dense``, ``nn.GaussianRBF``,
 ``nn.BesselRBF``, ``nn.CosineCutoff``, ``representation.{SchNet, SchNetInteraction, PaiNN,
-PaiNNInteraction, PaiNNMixing}`` and ``atomistic.PairwiseDistances``.  Classes are replaced both on
+PaiNNInteraction, PaiNNMixing}``, ``atomistic.PairwiseDistances``, ``atomistic.ZBLRepulsionEnergy`` and
+``atomistic.Aggregation``.  Classes are replaced both on
 the package and on the defining sub-module, so Hydra ``_target_`` paths and pickled models
 (``torch.load`` resolves ``schnetpack.representation.painn.PaiNN`` by attribute) pick up the
 mirrors; parameter names and shapes are identical, so existing ``state_dict``s and whole-model
@@ -76,6 +77,12 @@ def _fused_potential_call(orig_call):
             inputs = M.potential_forces_forward(self, inputs)
         elif mode == 3:
             inputs = M.potential_stress_forward(self, inputs)
+        elif mode in (4, 5):      # ... with a ZBL repulsion aggregated into the energy: one more launch
+            lay = self.__dict__.get("_spk_hip_zbl")
+            if lay is None:
+                lay = M.zbl_layout(list(self.output_modules))
+                self.__dict__["_spk_hip_zbl"] = lay
+            inputs = M.potential_stress_forward(self, inputs, lay) if mode == 5 else M.potential_forces_forward(self, inputs, lay)
         else:
             inputs = M.potential_forward(self, inputs)
             for i, m in enumerate(self.output_modules):
@@ -97,7 +104,9 @@ def install(spk=None, verbose=False, fused_head=True, neighbor_lists=False, fuse
     an eval-mode call of a model that is the standard potential (PairwiseDistances -> SchNet / PaiNN -> default Atomwise ->
     Forces) runs as the two-launch operator exactly like the mirror model -- 1.3-2 x the module-by-module route; any other
     model, training, and ``torch.jit.script`` (the class ``forward`` is untouched) keep the reference's code.
-    ``install(fused_head=False, fused_potential=False)`` is the minimal patch of rounds 1-3.
+    ``install(fused_head=False, fused_potential=False)`` is the minimal patch of rounds 1-3 -- plus, since the ZBL kernels exist,
+    ``atomistic.ZBLRepulsionEnergy`` and ``atomistic.Aggregation`` (same constructors, ``state_dict`` keys and ATen formulas; patched in every
+    configuration, when the reference has loaded those modules).
     ``neighbor_lists=True`` adds ``transform.HipNeighborList`` and replaces ``md.neighborlist_md.NeighborListMD``
     by the device-side batched version (same constructor and ``get_neighbors``)."""
     from . import atomistic as A
@@ -137,6 +146,11 @@ def install(spk=None, verbose=False, fused_head=True, neighbor_lists=False, fuse
     if fused_head:
         for mod in (getattr(spk, "atomistic", None), sub("atomistic.atomwise")):
             _set(mod, "Atomwise", A.Atomwise, log)
+    # the ZBL repulsion and the sum of energies (when the reference has loaded them): same constructors and state_dict keys
+    for mod in (getattr(spk, "atomistic", None), sub("atomistic.nuclear_repulsion")):
+        _set(mod, "ZBLRepulsionEnergy", A.ZBLRepulsionEnergy, log)
+    for mod in (getattr(spk, "atomistic", None), sub("atomistic.aggregation")):
+        _set(mod, "Aggregation", A.Aggregation, log)
     if fused_potential and fused_head:
         mb = sub("model.base")
         cls = getattr(mb, "NeuralNetworkPotential", None) if mb is not None else None

@@ -1,12 +1,12 @@
 """Mirror of ``NeuralNetworkPotential`` (model/base.py:132-190) -- the one caller of the hot
 path -- plus helpers to assemble the benchmark models and to move batches to the device."""
-from typing import Dict, Final, List, Optional
+from typing import Dict, Final, List, Optional, Tuple
 
 import torch
 import torch.nn as nn
 
 from . import properties
-from .atomistic import Atomwise, Forces, PairwiseDistances, Strain
+from .atomistic import Aggregation, Atomwise, Forces, PairwiseDistances, Strain, ZBLRepulsionEnergy
 from .nn import CosineCutoff, GaussianRBF, BesselRBF
 from .representation import PaiNN, SchNet
 
@@ -29,12 +29,47 @@ def _is_strain(m) -> bool:
     return t is Strain or (t.__name__ == "Strain" and t.__module__ == "schnetpack.atomistic.response")
 
 
+def _is_aggregation(m) -> bool:
+    """The mirror's ``Aggregation`` or the reference's own (atomistic/aggregation.py:9-28), not a subclass."""
+    t = type(m)
+    if t is Aggregation:
+        return True
+    return (t.__name__ == "Aggregation" and t.__module__ == "schnetpack.atomistic.aggregation"
+            and all(hasattr(m, a) for a in ("keys", "output_key")))
+
+
+def zbl_layout(outs) -> Optional[Tuple[int, int, int, int]]:
+    """Positions (head, zbl, aggregation, forces) in ``output_modules`` when they are: the learned ``Atomwise`` energy and ONE
+    ``ZBLRepulsionEnergy`` on its operator path (either order), one ``Aggregation`` over exactly their two keys, ``Forces`` of the aggregated
+    key.  None for every other composition."""
+    if len(outs) != 4:
+        return None
+    if isinstance(outs[0], Atomwise) and type(outs[1]) is ZBLRepulsionEnergy:
+        ih, iz = 0, 1
+    elif type(outs[0]) is ZBLRepulsionEnergy and isinstance(outs[1], Atomwise):
+        ih, iz = 1, 0
+    else:
+        return None
+    head, zbl, agg, frc = outs[ih], outs[iz], outs[2], outs[3]
+    if not (zbl._zbl_op and _is_aggregation(agg) and _is_forces(frc)):
+        return None
+    keys = list(agg.keys)
+    if head.output_key == zbl.output_key or len(keys) != 2 or sorted(keys) != sorted([head.output_key, zbl.output_key]):
+        return None
+    if frc.energy_key != agg.output_key or agg.output_key in keys:
+        return None
+    return ih, iz, 2, 3
+
+
 def classify_potential(model) -> int:
     """0: module-by-module.  1: the standard potential -- ``PairwiseDistances`` -> fused ``SchNet`` -> ``Atomwise`` (default
     head, summed or averaged over the molecule) -> ``Forces`` without stress: representation + head are ONE operator.
     2: ... and the only other output is Forces' -dE/dR of a summed energy: energies AND forces from the two launches.
     3: ``Strain`` -> ``PairwiseDistances`` -> ... -> ``Forces(calc_forces=True, calc_stress=True)`` of the summed energy: energies,
     forces and the virial dE/dstrain from the same operators (``*_potential_stress``).
+    4 / 5: forms 2 / 3 with a ``ZBLRepulsionEnergy`` next to the head, an ``Aggregation`` of the two energies and ``Forces`` of the sum
+    (:func:`zbl_layout`): the same operators, then one ``zbl_forces`` operator (a row pass, two reductions, a row-pointer kernel) that adds the
+    repulsion into their forces and virial, and one add of the two energies.
     Works on any model with the reference's ``NeuralNetworkPotential`` layout (model/base.py:132-190), i.e. also on the
     reference's own class around the HIP modules."""
     rep, ins, outs = model.representation, list(model.input_modules), list(model.output_modules)
@@ -44,6 +79,14 @@ def classify_potential(model) -> int:
     strained = len(ins) == 2 and _is_strain(ins[0]) and type(ins[1]) is PairwiseDistances
     if not ((strained or (len(ins) == 1 and type(ins[0]) is PairwiseDistances)) and len(outs) >= 1):
         return 0
+    lay = zbl_layout(outs)
+    if lay is not None:
+        head, frc = outs[lay[0]], outs[lay[3]]
+        if not (head._fused_head and head.per_atom_output_key is None and head.aggregation_mode == "sum" and frc.calc_forces):
+            return 0
+        if strained:
+            return 5 if frc.calc_stress else 0
+        return 0 if frc.calc_stress else 4
     head = outs[0]
     if not (isinstance(head, Atomwise) and head._fused_head and head.per_atom_output_key is None
             and head.aggregation_mode in ("sum", "avg")):
@@ -79,10 +122,23 @@ def potential_forward(model, inputs: Dict[str, torch.Tensor]) -> Dict[str, torch
     return inputs
 
 
-def potential_forces_forward(model, inputs: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+def _zbl_add(zbl, inputs: Dict[str, torch.Tensor], n_mol: int, F: torch.Tensor, W: Optional[torch.Tensor]) -> torch.Tensor:
+    """One operator (four short launches: row pass, chunk and molecule reductions, row pointers of ``idx_m``): the repulsion's forces (and
+    virial) added into ``F`` (``W``) in place; returns its energies."""
+    R = inputs[properties.R]
+    return torch.ops.spk_hip.zbl_forces(R, inputs.get(properties.offsets), inputs[properties.Z], inputs[properties.idx_i], inputs[properties.idx_j],
+                                        inputs[properties.idx_m], n_mol, zbl.op_params(R), F, W)
+
+
+def potential_forces_forward(model, inputs: Dict[str, torch.Tensor], layout: Optional[Tuple[int, int, int, int]] = None) -> Dict[str, torch.Tensor]:
     """Energies and forces straight from the two launches (no autograd node: eval only; the embedding rows are looked up
-    inside the forward launch when the nuclear embedding is a plain table)."""
-    rep, head, frc = model.representation, model.output_modules[0], model.output_modules[1]
+    inside the forward launch when the nuclear embedding is a plain table).  With a ``layout`` (:func:`zbl_layout`, mode 4) the ZBL
+    repulsion is added by one more operator and the learned, the repulsion and the aggregated energies are all set."""
+    outs = model.output_modules
+    rep, head, frc = model.representation, outs[0], outs[1]
+    zbl, agg = None, None
+    if layout is not None:
+        head, zbl, agg, frc = outs[layout[0]], outs[layout[1]], outs[layout[2]], outs[layout[3]]
     idx_m = inputs[properties.idx_m]
     kind, p0, p1 = rep.radial_basis.kernel_params()
     l0, l1 = head.outnet[0], head.outnet[1]
@@ -94,13 +150,21 @@ def potential_forces_forward(model, inputs: Dict[str, torch.Tensor]) -> Dict[str
                 inputs.get(properties.offsets), inputs[properties.idx_i], inputs[properties.idx_j], idx_m, head._n_molecules(inputs, idx_m),
                 rep.interaction_weights(), [l0.weight, l0.bias, l1.weight, l1.bias], rep.share_filters, rep.epsilon, kind, p0, p1,
                 rep.cutoff_fn.cutoff_value(), head._head_act)
+            if zbl is not None:
+                Ez = _zbl_add(zbl, inputs, head._n_molecules(inputs, idx_m), F, None)
+                Et = E + Ez
         if torch.is_grad_enabled():
             guard = [l0.weight]
             E, F = torch.ops.spk_hip.eval_guard(E, guard), torch.ops.spk_hip.eval_guard(F, guard)
+            if zbl is not None:
+                Ez, Et = torch.ops.spk_hip.eval_guard(Ez, guard), torch.ops.spk_hip.eval_guard(Et, guard)
         inputs["scalar_representation"] = x
         inputs["vector_representation"] = mu
         inputs[head.output_key] = E
         inputs[frc.force_key] = F
+        if zbl is not None:
+            inputs[zbl.output_key] = Ez
+            inputs[agg.output_key] = Et
         return inputs
     with torch.no_grad():
         x0 = None if plain else rep.embed(inputs)
@@ -108,20 +172,33 @@ def potential_forces_forward(model, inputs: Dict[str, torch.Tensor]) -> Dict[str
             x0, rep.embedding.weight if plain else None, inputs[properties.Z], inputs[properties.R], inputs.get(properties.offsets),
             inputs[properties.idx_i], inputs[properties.idx_j], idx_m, head._n_molecules(inputs, idx_m), rep.interaction_weights(),
             [l0.weight, l0.bias, l1.weight, l1.bias], rep.n_filters, kind, p0, p1, rep.cutoff_fn.cutoff_value(), head._head_act)
+        if zbl is not None:
+            Ez = _zbl_add(zbl, inputs, head._n_molecules(inputs, idx_m), F, None)
+            Et = E + Ez
     if torch.is_grad_enabled():      # a backward pass into this eval-mode model gets the eval-only message, not silence
         guard = [l0.weight]
         E, F = torch.ops.spk_hip.eval_guard(E, guard), torch.ops.spk_hip.eval_guard(F, guard)
+        if zbl is not None:
+            Ez, Et = torch.ops.spk_hip.eval_guard(Ez, guard), torch.ops.spk_hip.eval_guard(Et, guard)
     inputs["scalar_representation"] = x
     inputs[head.output_key] = E
     inputs[frc.force_key] = F
+    if zbl is not None:
+        inputs[zbl.output_key] = Ez
+        inputs[agg.output_key] = Et
     return inputs
 
 
-def potential_stress_forward(model, inputs: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+def potential_stress_forward(model, inputs: Dict[str, torch.Tensor], layout: Optional[Tuple[int, int, int, int]] = None) -> Dict[str, torch.Tensor]:
     """Energies, forces and stress straight from the operators (eval only, like :func:`potential_forces_forward`): the operator returns the
     virial W = dE/dstrain [n_mol, 3, 3]; stress = W / V with the signed cell volume, as ``Forces`` computes it (atomistic/response.py:81-90).
-    ``Strain`` itself does not run: at zero strain it leaves positions, offsets and cell as they are."""
-    rep, head, frc = model.representation, model.output_modules[0], model.output_modules[1]
+    ``Strain`` itself does not run: at zero strain it leaves positions, offsets and cell as they are.  With a ``layout`` (mode 5) the ZBL
+    repulsion is added into forces and virial by one more operator, as in :func:`potential_forces_forward`."""
+    outs = model.output_modules
+    rep, head, frc = model.representation, outs[0], outs[1]
+    zbl, agg = None, None
+    if layout is not None:
+        head, zbl, agg, frc = outs[layout[0]], outs[layout[1]], outs[layout[2]], outs[layout[3]]
     idx_m = inputs[properties.idx_m]
     kind, p0, p1 = rep.radial_basis.kernel_params()
     l0, l1 = head.outnet[0], head.outnet[1]
@@ -138,16 +215,24 @@ def potential_stress_forward(model, inputs: Dict[str, torch.Tensor]) -> Dict[str
             E, F, W, x = torch.ops.spk_hip.schnet_potential_stress(
                 None if plain else rep.embed(inputs), rep.embedding.weight if plain else None, *common, rep.n_filters, kind, p0, p1,
                 rep.cutoff_fn.cutoff_value(), head._head_act)
+        if zbl is not None:
+            Ez = _zbl_add(zbl, inputs, head._n_molecules(inputs, idx_m), F, W)
+            Et = E + Ez
         cell = inputs[properties.cell]
         volume = torch.sum(cell[:, 0, :] * torch.cross(cell[:, 1, :], cell[:, 2, :], dim=1), dim=1, keepdim=True)[:, :, None]
         S = W / volume
     if torch.is_grad_enabled():
         guard = [l0.weight]
         E, F, S = torch.ops.spk_hip.eval_guard(E, guard), torch.ops.spk_hip.eval_guard(F, guard), torch.ops.spk_hip.eval_guard(S, guard)
+        if zbl is not None:
+            Ez, Et = torch.ops.spk_hip.eval_guard(Ez, guard), torch.ops.spk_hip.eval_guard(Et, guard)
     inputs["scalar_representation"] = x
     inputs[head.output_key] = E
     inputs[frc.force_key] = F
     inputs[frc.stress_key] = S
+    if zbl is not None:
+        inputs[zbl.output_key] = Ez
+        inputs[agg.output_key] = Et
     return inputs
 
 
@@ -228,6 +313,11 @@ class NeuralNetworkPotential(nn.Module):
     #: gradients of a loss(E, F) by forward-over-reverse).  Set to False for the operator-by-operator path (any-order autograd).
     fm_engine: bool
     _fm_head_act: int
+    #: eval mode of the standard potential with a ZBL repulsion aggregated into the energy (classify_potential 4 / 5): the fused operators
+    #: plus one ``zbl_forces`` operator; ``_zbl_layout`` = positions of (head, zbl, aggregation, forces) in ``output_modules``
+    _potential_zbl: bool
+    _zbl_stress: bool
+    _zbl_layout: List[int]
 
     def __init__(self, representation: nn.Module, input_modules: List[nn.Module] = None,
                  output_modules: List[nn.Module] = None):
@@ -251,8 +341,17 @@ class NeuralNetworkPotential(nn.Module):
         # ... and when the only other output is Forces' -dE/dR, energies AND forces come from the two launches directly
         self._potential_forces = mode == 2
         self._potential_stress = mode == 3
+        self._potential_zbl = mode in (4, 5)
+        self._zbl_stress = mode == 5
+        self._zbl_layout = list(zbl_layout(list(self.output_modules)) or []) if mode in (4, 5) else []
         self._fm_head_act = classify_fm(self)
         self.fm_engine = self._fm_head_act > 0
+
+    def __setstate__(self, state):
+        # a model pickled before the ZBL routes existed: it has no such composition
+        super().__setstate__(state)
+        if "_potential_zbl" not in self.__dict__:
+            self._potential_zbl, self._zbl_stress, self._zbl_layout = False, False, []
 
     @torch.jit.unused
     def _potential_fm_forward(self, inputs: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
@@ -265,6 +364,11 @@ class NeuralNetworkPotential(nn.Module):
     @torch.jit.unused
     def _potential_forces_forward(self, inputs: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
         return potential_forces_forward(self, inputs)
+
+    @torch.jit.unused
+    def _potential_zbl_forward(self, inputs: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+        lay = (self._zbl_layout[0], self._zbl_layout[1], self._zbl_layout[2], self._zbl_layout[3])
+        return potential_stress_forward(self, inputs, lay) if self._zbl_stress else potential_forces_forward(self, inputs, lay)
 
     @torch.jit.unused
     def _potential_stress_forward(self, inputs: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
@@ -287,6 +391,9 @@ class NeuralNetworkPotential(nn.Module):
             return {k: inputs[k] for k in self.model_outputs}
         if self._potential_stress and not self.training and not torch.jit.is_scripting():
             inputs = self._potential_stress_forward(inputs)
+            return {k: inputs[k] for k in self.model_outputs}
+        if self._potential_zbl and not self.training and not torch.jit.is_scripting():
+            inputs = self._potential_zbl_forward(inputs)
             return {k: inputs[k] for k in self.model_outputs}
         if self.training and self.fm_engine and not torch.jit.is_scripting():
             pos = inputs[properties.R]
