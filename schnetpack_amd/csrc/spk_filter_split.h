@@ -117,3 +117,82 @@ __device__ __forceinline__ void ml_basis_split(int kind, int n_rbf, const float*
   }
 }
 
+// The same basis in straight-line form, from a table of what the slot loop needs instead of the raw parameters.
+// Table [2][32] in LDS, made by one workgroup on every launch (nothing is cached: trainable basis parameters keep working):
+//   gaussian:  row 0 = offset_k,           row 1 = -0.5 log2(e) / width_k^2   (a true division, once per launch and workgroup)
+//   bessel:    row 0 = omega_k / (2 pi),   row 1 = omega_k
+// Padding slots (k >= n_rbf) hold zeros: a Gaussian slot then evaluates to exp2(0) = 1 and a Bessel slot to sin(0) / d = 0 -- finite,
+// and without effect on the product, because ml_stage_w1_split() zeroes the columns k >= n_rbf of both W1 images (and the upper
+// half of k-step 1 when KPB = 3), so no branch on k is needed.
+__device__ __forceinline__ void ml_basis_table(float* __restrict__ tab, const RadialDev& rb, int tid) {
+  if (tid < 32) {
+    float t0 = 0.f, t1 = 0.f;
+    if (tid < rb.n_rbf) {
+      if (rb.kind == SPK_RBF_GAUSSIAN) {
+        const float w = rb.p1 ? rb.p1[tid] : 1.0f;
+        t0 = rb.p0 ? rb.p0[tid] : 1.0f;
+        t1 = (-0.5f * 1.4426950408889634f) / (w * w);
+      } else {
+        t1 = rb.p0 ? rb.p0[tid] : 1.0f;
+        t0 = t1 * 0.15915494309189535f;
+      }
+    }
+    tab[tid] = t0; tab[32 + tid] = t1;
+  }
+}
+// The lane's slots are runs of four consecutive k in ml_w1_k() order (k-step 0: 8 hi + 0..7; k-step 1: 16 + 4 hi + 0..3 and, KPB = 4,
+// 24 + 4 hi + 0..3), so each run is one 16-byte read per table row.  `kind` is wave-uniform: decided once, outside the slot loop.
+// A Gaussian value is sub, mul, mul, exp2; the slope follows from the same products (d phi / d d = 2 c t phi).
+template <int KPB, bool DERIV>
+__device__ __forceinline__ void ml_basis_split_lin(int kind, const float* __restrict__ tab, int hi, float d,
+                                                   h16x8 (&ph)[2], h16x8 (&pl)[2], h16x8 (&dh)[2], h16x8 (&dl)[2]) {
+  constexpr int NRUN = KPB > 2 ? (KPB == 4 ? 4 : 3) : 2;
+  f32x4 p0[NRUN], p1[NRUN];
+#pragma unroll
+  for (int q = 0; q < NRUN; ++q) {
+    const int k0 = q < 2 ? 8 * hi + 4 * q : 16 + 8 * (q - 2) + 4 * hi;
+    p0[q] = *(const f32x4*)(tab + k0);
+    p1[q] = *(const f32x4*)(tab + 32 + k0);
+  }
+  float v[16], dv[16];
+#pragma unroll
+  for (int e = 0; e < 16; ++e) { v[e] = 0.f; dv[e] = 0.f; }
+  if (kind == SPK_RBF_GAUSSIAN) {
+#pragma unroll
+    for (int q = 0; q < NRUN; ++q)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float t = d - p0[q][j];
+        const float ct = p1[q][j] * t;
+        const float phi = __builtin_amdgcn_exp2f(ct * t);
+        v[4 * q + j] = phi;
+        if (DERIV) dv[4 * q + j] = (1.3862943611198906f * ct) * phi;        // 2 ln 2: the coefficient carries log2(e)
+      }
+  } else {
+    const float inv = __builtin_amdgcn_rcpf(d);
+    const bool zero = d == 0.0f;
+#pragma unroll
+    for (int q = 0; q < NRUN; ++q)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float rev = p0[q][j] * d;
+        const float s = __builtin_amdgcn_sinf(rev);
+        const float phi = zero ? s : s * inv;
+        v[4 * q + j] = phi;
+        if (DERIV) dv[4 * q + j] = zero ? 0.f : (p1[q][j] * __builtin_amdgcn_cosf(rev) - phi) * inv;
+      }
+  }
+#pragma unroll
+  for (int s = 0; s < (KPB > 2 ? 2 : 1); ++s) {
+    float x[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) x[e] = v[8 * s + e];
+    sp_split8(x, ph[s], pl[s]);
+    if (DERIV) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) x[e] = dv[8 * s + e];
+      sp_split8(x, dh[s], dl[s]);
+    }
+  }
+}
+

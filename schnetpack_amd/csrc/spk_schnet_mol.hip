@@ -7,17 +7,21 @@
 // of the general driver (spk_schnet.hip), the float atomics of the pair kernels and their memsets; configs[1] of
 // BASELINE.json (256 aspirin frames) maps one molecule onto each of the 256 compute units.
 //
-// Workgroup = 8 wavefronts, one group of atoms (a block, or several small blocks, <= 32 atoms).  Per interaction:
-//   A. task queue over  (pair tile, channel tile) filter tasks  +  4 in2f tasks:
-//        filter task: 32 undirected pairs -> phi -> GEMM 1 (hidden = ssp(W1 phi + b1), rows = hidden channels) ->
-//                     GEMM 2 with swapped operands (rows = pairs, columns = the 32 channels of the task) -> raw filter
-//                     outputs g to memory (the tensor the backward reads anyway; L2-resident, 78 KB per aspirin frame)
-//        in2f task:   h[:, 32t:32t+32] = x W_in^T   (T-GEMM, weights streamed from their packed image)
-//   B. y[a] = sum_{b in row(a)} h[b] * g[pair(a,b)] * f_c   -- a per-atom row sum over the directed CSR of the block,
-//        thread = (channel, atom quarter): no atomics, no scatter, deterministic
-//   C. t = ssp(y W3^T + b3);  x += t W4^T + b4      (two T-GEMM phases; the idle half of the workgroup stages the
-//        filter weights of the next interaction into LDS meanwhile)
-// fp32 MFMA (v_mfma_f32_32x32x2_f32) throughout: 1e-5 parity with the reference rules out bf16.
+// Workgroup = 8 wavefronts, one group of atoms (a block, or several small blocks, <= 32 atoms).  Set-up once per group: atom
+// features and per-pair records (atoms, distance, f_c) in LDS, shared by every interaction.  The waves are two teams of four, wave t
+// of a team owns channel tile t.  Per interaction:
+//   A. pair tiles of 32 undirected pairs, alternating between the teams (team 1 runs in2f, h = x W_in^T, first):
+//        hidden layer ONCE per tile and team: radial basis from a table staged per launch (ml_basis_split_lin) -> GEMM 1 ->
+//          ssp -> one LDS tile, wave t its 32 hidden channels;
+//        per wave: GEMM 2 with swapped operands (rows = pairs, columns = its 32 channels) -> raw filter outputs g to memory (the
+//          tensor the backward reads; L2-resident) -> modulation W = g f_c, products W h[j], W h[i] -> accumulated into
+//          y[atom, channel] by the 0/1 incidence of the tile ON THE MATRIX CORE; branch-free: padding rows of the last tile
+//          repeat its last pair with weight zero.  No atomics, no scatter pass, deterministic
+//   C. t = ssp((y_team0 + y_team1) W3^T + b3);  x += t W4^T + b4      (two T-GEMM phases; the idle team stages the filter
+//        weights of the next interaction into LDS meanwhile)
+// then the energy head on the atom tile that is still in LDS.  Matrix products run on the split-precision path (spk_split.h: fp32
+// operands as two fp16 images on v_mfma_f32_32x32x16_f16; 1e-5 parity with the reference rules out plain bf16 / fp16), or, with
+// spk_set_split(0), on v_mfma_f32_32x32x2_f32 (the <KPB, false> instances).
 #include "spk_common.h"
 #include "spk_pack.h"
 #include "spk_split.h"
@@ -88,6 +92,13 @@ struct MolFwdArgs {
 
 // per pair of a group: local atoms i | j << 8, distance, f_c(d), f_c'(d) -- computed once per group, used by every interaction
 struct __attribute__((aligned(16))) MolPair { int ij; float d; float fc; float dfc; };
+// the record as the split forward keeps it (rewritten in place once per group; it never needs f_c'): what a row of the modulation
+// loop would otherwise derive from `ij` in every tile visit of every interaction --
+// ij = byte offset of atom i's row of an [32][ML_LD] LDS tile | that of atom j << 16, dfc = the BITS of the byte offset of the
+// pair's row of the saved filter outputs
+__device__ __forceinline__ MolPair ml_fwd_pair(const MolPair p) {
+  return MolPair{(p.ij & 255) * (ML_LD * 4) | (((p.ij >> 8) & 255) * (ML_LD * 4)) << 16, p.d, p.fc, __int_as_float((p.ij >> 16) * (128 * 4))};
+}
 
 // pair records of a group: geometry is the same for every interaction.  ij = local i | local j << 8 | position of the pair in the
 // group's pair list << 16.  With `compact` (lists with a skin: MD) only the pairs INSIDE the cutoff get a record -- the others
@@ -426,7 +437,8 @@ __global__ __launch_bounds__(512) void k_schnet_mol_fwd(MolFwdArgs a) {
   const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);   // wv: SGPR
   const int hi = lane >> 5, el = lane & 31;
   const int team = wv >> 2, t = wv & 3;
-  if (tid < 64) {
+  if constexpr (SP) ml_basis_table(sRb, a.rb, tid);          // (offset, exponent coefficient) per slot: ml_basis_split_lin()
+  else if (tid < 64) {
     const int k = tid & 31;
     const float* src = (tid < 32) ? a.rb.p0 : a.rb.p1;
     sRb[tid] = (src && k < a.rb.n_rbf) ? src[k] : 1.0f;
@@ -454,6 +466,9 @@ __global__ __launch_bounds__(512) void k_schnet_mol_fwd(MolFwdArgs a) {
     }
     const int np = ml_pair_records(sP, nullptr, sScan, a.half, a.rij, a.R, a.offsets, a.idx_i, a.idx_j, p0, np_list, a0, a.rb.cutoff, a.compact != 0, tid);
     const int ntile = (np + 31) / 32;
+    if constexpr (SP) {      // (each thread its own record; the barrier at the top of the first interaction publishes them)
+      if (tid < np) sP[tid] = ml_fwd_pair(sP[tid]);
+    }
     // (W2 of the first interaction -- first read by GEMM 2 of the first tile -- is staged by team 0 behind its first hidden tile,
     // while team 1 is still busy with in2f)
     if constexpr (SP) ml_stage_w1_split<KPB>(sW1h, sW1l, a.L[0].w1, a.rb.n_rbf, tid);
@@ -504,7 +519,7 @@ __global__ __launch_bounds__(512) void k_schnet_mol_fwd(MolFwdArgs a) {
             // split form: A = the (high, low) images of W1, B = this pair's basis values in the lane's k-slots; three f16 matrix
             // instructions per k-step, the cross terms in their own accumulator
             h16x8 ph[2], pl[2], dh_[2], dl_[2];
-            ml_basis_split<KPB, false>(a.rb.kind, a.rb.n_rbf, sRb, sRb + 32, hi, d, ph, pl, dh_, dl_);
+            ml_basis_split_lin<KPB, false>(a.rb.kind, sRb, hi, d, ph, pl, dh_, dl_);
             f32x16 zx;
 #pragma unroll
             for (int r = 0; r < 16; ++r) zx[r] = 0.f;
@@ -611,6 +626,12 @@ __global__ __launch_bounds__(512) void k_schnet_mol_fwd(MolFwdArgs a) {
           if constexpr (SP) {
             // incidence product on the f16 matrix instruction: A (0 / 1, exact) carries the weight 2^-11 of the low parts itself, so
             // the accumulator that lives across the tiles stays ONE
+            // Branch-free: a padding row (pr >= nvalid) takes the record of the tile's last pair.  The hidden layer mirrored that pair's
+            // distance into the padded lanes, so the row of g is that pair's row bit for bit and the store below writes the same value
+            // to the same address again (tests/test_gpu_mol_fwd_operands.py); its weight is zero.
+            const MolPair* sQ = sP + pfirst;             // forward-side records: ml_fwd_pair()
+            const char* hcol = (const char*)(sH + c0);
+            const int own = el * (ML_LD * 4);
 #pragma unroll
             for (int s2 = 0; s2 < 2; ++s2) {
               float tI[8], tJ[8];
@@ -620,13 +641,13 @@ __global__ __launch_bounds__(512) void k_schnet_mol_fwd(MolFwdArgs a) {
                 const int r = 8 * s2 + e;
                 const int pr = ml_row(r, hi);
                 const bool ok = pr < nvalid;
-                const MolPair rec = sP[pfirst + (ok ? pr : 0)];
-                const int pi = rec.ij & 255, pj = (rec.ij >> 8) & 255;
-                if (ok) ml_st<float>(gt, (unsigned)(((rec.ij >> 16) * NF + el) * 4), g[r]);
-                const float W = ok ? g[r] * rec.fc : 0.f;
-                tI[e] = W * sH[pj * ML_LD + c0]; tJ[e] = W * sH[pi * ML_LD + c0];
-                ai[e] = pi == el ? (_Float16)1.0f : (_Float16)0.0f;
-                aj[e] = pj == el ? (_Float16)1.0f : (_Float16)0.0f;
+                const MolPair rec = sQ[ok ? pr : nvalid - 1];
+                const int oi = rec.ij & 0xFFFF, oj = rec.ij >> 16;
+                ml_st<float>(gt, (unsigned)(__float_as_int(rec.dfc) + el * 4), g[r]);
+                const float W = g[r] * (ok ? rec.fc : 0.f);
+                tI[e] = W * *(const float*)(hcol + oj); tJ[e] = W * *(const float*)(hcol + oi);
+                ai[e] = oi == own ? (_Float16)1.0f : (_Float16)0.0f;
+                aj[e] = oj == own ? (_Float16)1.0f : (_Float16)0.0f;
               }
               h16x8 ih, il, jh, jl;
               sp_split8(tI, ih, il);
@@ -953,7 +974,8 @@ __global__ __launch_bounds__(512) void k_schnet_mol_bwd(MolBwdArgs a) {
 
   const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);   // wv: SGPR
   const int hi = lane >> 5, el = lane & 31;
-  if (tid < 64) {
+  if constexpr (SP) ml_basis_table(sRb, a.rb, tid);          // as in the forward: ml_basis_split_lin()
+  else if (tid < 64) {
     const int k = tid & 31;
     const float* src = (tid < 32) ? a.rb.p0 : a.rb.p1;
     sRb[tid] = (src && k < a.rb.n_rbf) ? src[k] : 1.0f;
@@ -1198,7 +1220,7 @@ __global__ __launch_bounds__(512) void k_schnet_mol_bwd(MolBwdArgs a) {
           asm volatile("" : "+v"(lane_o));
           const int hi_o = lane_o >> 5;
           h16x8 ph[2], pl[2], dh[2], dl[2];
-          ml_basis_split<KPB, true>(a.rb.kind, a.rb.n_rbf, sRb, sRb + 32, hi_o, pr.d, ph, pl, dh, dl);
+          ml_basis_split_lin<KPB, true>(a.rb.kind, sRb, hi_o, pr.d, ph, pl, dh, dl);
           h16x8 zph[NT][2], zpl[NT][2];
 #pragma unroll
           for (int c = 0; c < NT; ++c) {
