@@ -256,6 +256,30 @@ int spk_zbl_bwd_f32(const float* gE, const float* r_ij, const int64_t* Z, const 
 int spk_zbl_forces_f32(const float* R, const float* offsets, const int64_t* Z, const spk_graph_t* g, const int64_t* idx_m, int64_t n_mol,
                        const float* params, float* E_zbl, float* F, float* W, void* workspace, void* stream);
 
+/* ------------------------------------------------------------------ atomistic/atomwise.py:91-293 (DipoleMoment, Polarizability),
+ * nn/equivariant.py:11-71 (GatedEquivariantBlock), nn/blocks.py:79-156 (build_gated_equivariant_mlp)
+ * spk_gated_mlp_fwd_f32: the whole gated equivariant MLP of a head, build_gated_equivariant_mlp(n_in, n_out = 1, n_hidden = None,
+ * n_gating_hidden = None, n_layers, activation = sactivation = act), in ONE launch: s [N, n_in], v [N, 3, n_in] -> s_out [N] (= [N, 1]),
+ * v_out [N, 3] (= [N, 3, 1]), both overwritten.  host_weights: HOST array of 5 n_layers device pointers, per block mix_vectors.weight
+ * [2 n_vout, n_vin], scalar_net.0.weight [n_hidden, n_sin + n_vout], scalar_net.0.bias, scalar_net.1.weight [n_sout + n_vout, n_hidden],
+ * scalar_net.1.bias, with the pyramidal widths n_in -> n_in / 2 -> 1 and n_hidden = the block's input width.  Covered (spk_gated_mlp_supported):
+ * n_in in {64, 128}, n_layers = 2, SILU; anything else returns SPK_ERR_ARG.  s, v and the block-0 weight matrices must be 16-byte aligned.
+ * The vector norm carries no epsilon (torch.norm): a zero vector row gives finite outputs.  No workspace, no host synchronisation.
+ * spk_moment_reduce_f32: the per-molecule sums, one wave per molecule, idx_m [N] ASCENDING with entries in [0, n_mol) (the atom range of a
+ * molecule is found by bisection; an atom inside it with another index turns that molecule's outputs into NaN).  No float atomics: the same
+ * inputs give the same bits.  A molecule without atoms gives zeros.
+ *   SPK_MOMENT_DIPOLE:         out [n_mol, 3] = sum_i (q_i + c_m) R_i + d_i;  d [N, 3] or NULL;  with `correct` c_m = (total_charge[m] -
+ *                              sum_i q_i) / n_atoms(m) (total_charge NULL: zero), else c_m = 0;  q_out [N] (or NULL) receives q_i + c_m.
+ *   SPK_MOMENT_POLARIZABILITY: out [n_mol, 3, 3] = sum_i q_i 1 + d_i R_i^T + R_i d_i^T, symmetric to the bit;  q = the isotropic part,
+ *                              d [N, 3] required; total_charge, correct and q_out are ignored. */
+#define SPK_MOMENT_DIPOLE 0
+#define SPK_MOMENT_POLARIZABILITY 1
+int spk_gated_mlp_supported(int32_t n_in, int32_t n_layers, int32_t act);
+int spk_gated_mlp_fwd_f32(const float* s, const float* v, int64_t N, int32_t n_in, int32_t n_layers, int32_t act,
+                          const float* const* host_weights, float* s_out, float* v_out, void* stream);
+int spk_moment_reduce_f32(int32_t kind, const float* q, const float* d, const float* R, const int64_t* idx_m, int64_t N, int64_t n_mol,
+                          const float* total_charge, int32_t correct, float* out, float* q_out, void* stream);
+
 /* ------------------------------------------------------------------ transform/neighborlist.py:438-507
  * (TorchNeighborList) and md/neighborlist_md.py:100-159 -- cell-list neighbour list on the device for
  * a batch of independent systems (molecules / MD replicas).  Result: every DIRECTED pair (i, j, S)

@@ -157,6 +157,9 @@ _PROTOS = {
     "spk_zbl_fwd_f32": (ctypes.c_int, [c_f, c_f, P(GraphT), c_f, c_i64, c_f, c_f, c_f, c_f, c_f]),
     "spk_zbl_bwd_f32": (ctypes.c_int, [c_f, c_f, c_f, P(GraphT), c_f, c_i64, c_f, c_f, c_f]),
     "spk_zbl_forces_f32": (ctypes.c_int, [c_f, c_f, c_f, P(GraphT), c_f, c_i64, c_f, c_f, c_f, c_f, c_f, c_f]),
+    "spk_gated_mlp_supported": (ctypes.c_int, [c_i32, c_i32, c_i32]),
+    "spk_gated_mlp_fwd_f32": (ctypes.c_int, [c_f, c_f, c_i64, c_i32, c_i32, c_i32, P(ctypes.c_void_p), c_f, c_f, c_f]),
+    "spk_moment_reduce_f32": (ctypes.c_int, [c_i32, c_f, c_f, c_f, c_f, c_i64, c_i64, c_f, c_i32, c_f, c_f, c_f]),
     "spk_radial_cutoff_f32": (ctypes.c_int, [c_f, c_i64, P(RadialT), c_f, c_f, c_f]),
     "spk_radial_cutoff_bwd_f32": (ctypes.c_int, [c_f, c_i64, P(RadialT), c_f, c_f, c_f, c_f]),
     "spk_edge_norm_f32": (ctypes.c_int, [c_f, c_i64, c_f, c_f, c_f]),

@@ -5,6 +5,7 @@ reference's own modules run unchanged on top of the HIP classes (tests/test_gpu_
 ``schnetpack.nn.scatter_add`` / ``Dense`` / the representation classes; ``install(fused_head=True)`` swaps in this
 ``Atomwise`` for its one-kernel energy head.  ``ZBLRepulsionEnergy`` (atomistic/nuclear_repulsion.py:13-108) and ``Aggregation``
 (atomistic/aggregation.py:9-28) add the short-range nuclear repulsion production potentials carry next to the learned energy.
+``DipoleMoment`` and ``Polarizability`` (atomistic/atomwise.py:91-293) are the tensorial heads on PaiNN's vector representation.
 """
 from typing import Callable, Dict, Final, List, Optional, Sequence, Union
 
@@ -15,11 +16,11 @@ import torch.nn.functional as F
 from . import _lib, properties
 from . import units as spk_units
 from . import torchops  # noqa: F401  (registers torch.ops.spk_hip)
-from .nn import CosineCutoff, Dense, build_mlp, scatter_add
+from .nn import CosineCutoff, Dense, GatedEquivariantBlock, build_gated_equivariant_mlp, build_mlp, scatter_add
 from .nn.base import activation_id
 from .nn.fallback import note_fallback, use_aten
 
-__all__ = ["Strain", "PairwiseDistances", "Atomwise", "Forces", "ZBLRepulsionEnergy", "Aggregation"]
+__all__ = ["Strain", "PairwiseDistances", "Atomwise", "Forces", "ZBLRepulsionEnergy", "Aggregation", "DipoleMoment", "Polarizability"]
 
 
 class Strain(nn.Module):
@@ -344,4 +345,263 @@ class Aggregation(nn.Module):
     def forward(self, inputs: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
         energy = torch.stack([inputs[key] for key in self.keys]).sum(0)
         inputs[self.output_key] = energy
+        return inputs
+
+
+def _gated_head_act(net, n_in: int) -> int:
+    """Activation id (> 0) when ``net`` is the gated equivariant MLP the one-launch kernel covers -- ``build_gated_equivariant_mlp(n_in, 1)``
+    with the pyramidal default widths, the gating networks as wide as their block's input, one fusable activation inside and on the scalars
+    of every block but the last -- else 0."""
+    if not (isinstance(net, nn.Sequential) and len(net) >= 1 and all(type(b) is GatedEquivariantBlock for b in net)):
+        return 0
+    act0 = activation_id(net[0].scalar_net[0].activation)
+    if act0 is None or act0 == _lib.SPK_ACT_NONE:
+        return 0
+    n = int(n_in)
+    for i, b in enumerate(net):
+        last = i == len(net) - 1
+        m = 1 if last else n // 2
+        if (b.n_sin, b.n_vin, b.n_sout, b.n_vout, b.n_hidden) != (n, n, m, m, n):
+            return 0
+        sn = b.scalar_net
+        if not (type(b.mix_vectors) is Dense and b.mix_vectors.bias is None and len(sn) == 2 and all(type(l) is Dense for l in sn)):
+            return 0
+        if sn[0].bias is None or sn[1].bias is None or activation_id(sn[0].activation) != act0 or activation_id(sn[1].activation) != _lib.SPK_ACT_NONE:
+            return 0
+        sact = _lib.SPK_ACT_NONE if b.sactivation is None else activation_id(b.sactivation)
+        if sact != (_lib.SPK_ACT_NONE if last else act0):
+            return 0
+        n = m
+    if not bool(_lib.lib().spk_gated_mlp_supported(int(n_in), len(net), int(act0))):
+        return 0
+    return int(act0)
+
+
+def _scalar_head_act(net) -> int:
+    """Activation id (> 0) when ``net`` is the 2-layer / width-1 ``build_mlp`` head that ``spk_atomwise_fwd_f32`` covers, else 0."""
+    if not (isinstance(net, nn.Sequential) and len(net) == 2 and all(type(l) is Dense for l in net)):
+        return 0
+    act = activation_id(net[0].activation)
+    if act is None or act == _lib.SPK_ACT_NONE or activation_id(net[1].activation) != _lib.SPK_ACT_NONE:
+        return 0
+    if net[1].out_features != 1 or net[0].bias is None or net[1].bias is None:
+        return 0
+    if not bool(_lib.lib().spk_atomwise_supported(int(net[0].in_features), int(net[0].out_features), int(act))):
+        return 0
+    return int(act)
+
+
+class DipoleMoment(nn.Module):
+    """Dipole moment from latent partial charges and, with ``use_vector_representation``, local atomic dipoles (atomistic/atomwise.py:91-213):
+    ``mu = sum_i q_i R_i + d_i``; ``correct_charges`` shifts the charges of every molecule so that they sum to ``inputs["total_charge"]`` (zero when
+    absent).  Constructor, attributes and ``state_dict`` keys are the reference's.
+
+    Eval mode on float32 device tensors is two launches: the whole gated equivariant MLP (``torch.ops.spk_hip.gated_mlp``; scalar route: the
+    ``atomwise`` operator's per-atom output) and the per-molecule part (``torch.ops.spk_hip.dipole_moment``: charge sum, correction, moment; no float
+    atomics, ``idx_m`` ascending).  No autograd graph is built there: with autograd enabled the outputs pass through ``eval_guard``, whose backward
+    raises.  Training mode, float64, host tensors and heads without a fused kernel (any ``n_hidden`` / ``n_layers`` but the default two pyramidal
+    layers of width 64 or 128, other activations) run the reference's formula on the ``Dense`` / ``scatter_add`` mirrors -- the route with parameter
+    gradients and derivatives w.r.t. the positions.  A molecule without atoms gets a zero moment on both routes (the reference's 0 / 0 correction of
+    such a molecule is never gathered by an atom).  ``_n_atoms`` is read on the ATen route only, and counted from ``idx_m`` when absent."""
+
+    use_vector_representation: Final[bool]
+    _gated_act: Final[int]
+    _scalar_act: Final[int]
+
+    def __init__(self, n_in: int, n_hidden: Optional[Union[int, Sequence[int]]] = None, n_layers: int = 2, activation: Callable = F.silu,
+                 predict_magnitude: bool = False, return_charges: bool = False, dipole_key: str = properties.dipole_moment,
+                 charges_key: str = properties.partial_charges, correct_charges: bool = True, use_vector_representation: bool = False,
+                 n_molecules_key: str = "_n_molecules"):
+        super().__init__()
+        self.dipole_key = dipole_key
+        self.charges_key = charges_key
+        self.return_charges = return_charges
+        self.model_outputs = [dipole_key]
+        if self.return_charges:
+            self.model_outputs.append(charges_key)
+        self.predict_magnitude = predict_magnitude
+        self.use_vector_representation = use_vector_representation
+        self.correct_charges = correct_charges
+        if use_vector_representation:
+            self.outnet = build_gated_equivariant_mlp(n_in=n_in, n_out=1, n_hidden=n_hidden, n_layers=n_layers, activation=activation,
+                                                      sactivation=activation)
+        else:
+            self.outnet = build_mlp(n_in=n_in, n_out=1, n_hidden=n_hidden, n_layers=n_layers, activation=activation)
+        self.n_molecules_key = n_molecules_key
+        self._init_operator()
+
+    def _init_operator(self):
+        self._gated_act = _gated_head_act(self.outnet, self.outnet[0].n_sin) if self.use_vector_representation else 0
+        self._scalar_act = 0 if self.use_vector_representation else _scalar_head_act(self.outnet)
+
+    def __setstate__(self, state):
+        # a pickle made by the REFERENCE class unpickled onto this one after install() never ran __init__
+        super().__setstate__(state)
+        if "n_molecules_key" not in self.__dict__:
+            self.n_molecules_key = "_n_molecules"
+        if "_gated_act" not in self.__dict__ or "_scalar_act" not in self.__dict__:
+            self._init_operator()
+
+    def _n_molecules(self, inputs: Dict[str, torch.Tensor], idx_m: torch.Tensor) -> int:
+        # like Atomwise: a host-side molecule count in the batch avoids the reference's int(idx_m[-1]) + 1 (a device sync)
+        if self.n_molecules_key in inputs:
+            return int(inputs[self.n_molecules_key])
+        return int(idx_m[-1]) + 1
+
+    def _head_weights(self) -> List[torch.Tensor]:
+        ws: List[torch.Tensor] = []
+        for b in self.outnet:
+            ws.append(b.mix_vectors.weight)
+            ws.append(b.scalar_net[0].weight)
+            ws.append(b.scalar_net[0].bias)
+            ws.append(b.scalar_net[1].weight)
+            ws.append(b.scalar_net[1].bias)
+        return ws
+
+    def forward(self, inputs: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+        positions = inputs[properties.R]
+        l0 = inputs["scalar_representation"]
+        idx_m = inputs[properties.idx_m]
+        maxm = self._n_molecules(inputs, idx_m)
+        total: Optional[torch.Tensor] = None
+        if properties.total_charge in inputs:
+            total = inputs[properties.total_charge]
+        device_ok = not self.training and l0.dim() == 2 and not use_aten(l0) and not use_aten(positions)
+        if self.use_vector_representation:
+            l1 = inputs["vector_representation"]
+            if self._gated_act > 0 and device_ok and l1.dim() == 3:
+                q, d = torch.ops.spk_hip.gated_mlp(l0.detach(), l1.detach(), self._head_weights(), self._gated_act)
+                return self._moment(inputs, q, d, positions, idx_m, maxm, total, self.outnet[0].mix_vectors.weight)
+            charges, dip = self.outnet((l0, l1))
+            return self._aten(inputs, charges, torch.squeeze(dip, -1), positions, idx_m, maxm, total)
+        else:
+            if self._scalar_act > 0 and device_ok:
+                n0 = self.outnet[0]
+                n1 = self.outnet[1]
+                q = torch.ops.spk_hip.atomwise(l0.detach(), n0.weight.detach(), n0.bias.detach(), n1.weight.detach(), n1.bias.detach(), idx_m, maxm,
+                                               self._scalar_act)[1]
+                return self._moment(inputs, q, None, positions, idx_m, maxm, total, n0.weight)
+            charges = self.outnet(l0)
+            return self._aten(inputs, charges, None, positions, idx_m, maxm, total)
+
+    def _moment(self, inputs: Dict[str, torch.Tensor], q: torch.Tensor, d: Optional[torch.Tensor], positions: torch.Tensor, idx_m: torch.Tensor,
+                maxm: int, total: Optional[torch.Tensor], guard: torch.Tensor) -> Dict[str, torch.Tensor]:
+        y, charges = torch.ops.spk_hip.dipole_moment(q, d, positions.detach(), idx_m, maxm, total, self.correct_charges)
+        if self.predict_magnitude:
+            y = torch.norm(y, dim=1, keepdim=False)
+        if torch.is_grad_enabled():      # a backward pass into the eval-mode head gets the eval-only message, not silence
+            y = torch.ops.spk_hip.eval_guard(y, [guard])
+            charges = torch.ops.spk_hip.eval_guard(charges, [guard])
+        if self.return_charges:
+            inputs[self.charges_key] = charges
+        inputs[self.dipole_key] = y
+        return inputs
+
+    def _aten(self, inputs: Dict[str, torch.Tensor], charges: torch.Tensor, dip: Optional[torch.Tensor], positions: torch.Tensor,
+              idx_m: torch.Tensor, maxm: int, total: Optional[torch.Tensor]) -> Dict[str, torch.Tensor]:
+        # the reference's formula (atomistic/atomwise.py:187-212)
+        if use_aten(charges):
+            note_fallback()
+        if self.correct_charges:
+            sum_charge = scatter_add(charges, idx_m, dim_size=maxm)
+            if total is not None:
+                total_charge = total[:, None]
+            else:
+                total_charge = torch.zeros_like(sum_charge)
+            if properties.n_atoms in inputs:
+                natoms = inputs[properties.n_atoms].to(charges.dtype).unsqueeze(-1)
+            else:
+                natoms = scatter_add(torch.ones_like(charges), idx_m, dim_size=maxm)
+            charge_correction = (total_charge - sum_charge) / natoms
+            charge_correction = charge_correction[idx_m]
+            charges = charges + charge_correction
+        if self.return_charges:
+            inputs[self.charges_key] = charges
+        y = positions * charges
+        if dip is not None:
+            y = y + dip
+        y = scatter_add(y, idx_m, dim_size=maxm)
+        if self.predict_magnitude:
+            y = torch.norm(y, dim=1, keepdim=False)
+        inputs[self.dipole_key] = y
+        return inputs
+
+
+class Polarizability(nn.Module):
+    """Polarizability tensor by rank factorisation (atomistic/atomwise.py:216-293): ``alpha = sum_i a_i 1 + d_i R_i^T + R_i d_i^T`` with the scalar
+    ``a_i`` and the vector ``d_i`` from a gated equivariant MLP on the scalar and vector representation.  Constructor, attributes and
+    ``state_dict`` keys are the reference's.
+
+    Routing as :class:`DipoleMoment`: eval mode on float32 device tensors is ``torch.ops.spk_hip.gated_mlp`` +
+    ``torch.ops.spk_hip.polarizability`` (two launches; ``alpha`` equals its transpose to the bit; ``idx_m`` ascending), everything else the
+    reference's formula on the mirrors."""
+
+    _gated_act: Final[int]
+
+    def __init__(self, n_in: int, n_hidden: Optional[Union[int, Sequence[int]]] = None, n_layers: int = 2, activation: Callable = F.silu,
+                 polarizability_key: str = properties.polarizability, n_molecules_key: str = "_n_molecules"):
+        super().__init__()
+        self.n_in = n_in
+        self.n_layers = n_layers
+        self.n_hidden = n_hidden
+        self.polarizability_key = polarizability_key
+        self.model_outputs = [polarizability_key]
+        self.outnet = build_gated_equivariant_mlp(n_in=n_in, n_out=1, n_hidden=n_hidden, n_layers=n_layers, activation=activation,
+                                                  sactivation=activation)
+        self.requires_dr = False
+        self.requires_stress = False
+        self.n_molecules_key = n_molecules_key
+        self._gated_act = _gated_head_act(self.outnet, n_in)
+
+    def __setstate__(self, state):
+        super().__setstate__(state)
+        if "n_molecules_key" not in self.__dict__:
+            self.n_molecules_key = "_n_molecules"
+        if "_gated_act" not in self.__dict__:
+            self._gated_act = _gated_head_act(self.outnet, self.outnet[0].n_sin)
+
+    def _n_molecules(self, inputs: Dict[str, torch.Tensor], idx_m: torch.Tensor) -> int:
+        if self.n_molecules_key in inputs:
+            return int(inputs[self.n_molecules_key])
+        return int(idx_m[-1]) + 1
+
+    def _head_weights(self) -> List[torch.Tensor]:
+        ws: List[torch.Tensor] = []
+        for b in self.outnet:
+            ws.append(b.mix_vectors.weight)
+            ws.append(b.scalar_net[0].weight)
+            ws.append(b.scalar_net[0].bias)
+            ws.append(b.scalar_net[1].weight)
+            ws.append(b.scalar_net[1].bias)
+        return ws
+
+    def forward(self, inputs: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+        positions = inputs[properties.R]
+        l0 = inputs["scalar_representation"]
+        l1 = inputs["vector_representation"]
+        idx_m = inputs[properties.idx_m]
+        maxm = self._n_molecules(inputs, idx_m)
+        if (self._gated_act > 0 and not self.training and l0.dim() == 2 and l1.dim() == 3 and l1.shape[-2] == 3 and not use_aten(l0)
+                and not use_aten(positions)):
+            a0, d = torch.ops.spk_hip.gated_mlp(l0.detach(), l1.detach(), self._head_weights(), self._gated_act)
+            alpha = torch.ops.spk_hip.polarizability(a0, d, positions.detach(), idx_m, maxm)
+            if torch.is_grad_enabled():
+                alpha = torch.ops.spk_hip.eval_guard(alpha, [self.outnet[0].mix_vectors.weight])
+            inputs[self.polarizability_key] = alpha
+            return inputs
+        if use_aten(l0):
+            note_fallback()
+        # the reference's formula (atomistic/atomwise.py:267-292)
+        dim = l1.shape[-2]
+        l0, l1 = self.outnet((l0, l1))
+        alpha = l0[..., 0:1]
+        size = list(alpha.shape)
+        size[-1] = dim
+        alpha = alpha.expand(size)
+        alpha = torch.diag_embed(alpha)
+        mur = l1[..., None, 0] * positions[..., None, :]
+        alpha_c = mur + mur.transpose(-2, -1)
+        alpha = alpha + alpha_c
+        alpha = scatter_add(alpha, idx_m, dim_size=maxm)
+        inputs[self.polarizability_key] = alpha
         return inputs

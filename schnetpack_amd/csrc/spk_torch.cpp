@@ -1057,6 +1057,76 @@ Tensor zbl_forces_raw(const Tensor& R_in, const c10::optional<Tensor>& offsets_i
   return E;
 }
 
+// Tensorial heads (atomistic/atomwise.py:91-293; csrc/spk_tensorial.hip), eval only, no autograd node: the mirrors hand in detached tensors and
+// pass the outputs through eval_guard.
+// gated_mlp: the gated equivariant MLP of a head in one launch.  weights = per block [mix_vectors.weight, scalar_net.0.weight, scalar_net.0.bias,
+// scalar_net.1.weight, scalar_net.1.bias]; the pyramidal default widths (n_in -> n_in / 2 -> 1, gating width = block input) are checked here.
+std::tuple<Tensor, Tensor> gated_mlp_raw(const Tensor& s_in, const Tensor& v_in, at::TensorList weights, int64_t act) {
+  const char* who = "gated_mlp";
+  Tensor s = f32(s_in.detach(), who), v = f32(v_in.detach(), who);
+  TORCH_CHECK(s.dim() == 2 && v.dim() == 3 && v.size(0) == s.size(0) && v.size(1) == 3 && v.size(2) == s.size(1), who, ": s [N, F], v [N, 3, F]");
+  const int64_t N = s.size(0), F = s.size(1);
+  TORCH_CHECK(weights.size() % 5 == 0 && weights.size() > 0, who, ": five weight tensors per block");
+  const int64_t n_layers = (int64_t)weights.size() / 5;
+  TORCH_CHECK(spk_gated_mlp_supported((int32_t)F, (int32_t)n_layers, (int32_t)act), who, ": no fused kernel for n_in = ", F, ", n_layers = ", n_layers,
+              ", act = ", act, " (spk_gated_mlp_supported); the module mirror takes its ATen route for such heads");
+  std::vector<Tensor> w;
+  std::vector<const float*> ptr;
+  int64_t n = F;
+  for (int64_t b = 0; b < n_layers; ++b) {
+    const int64_t m = b + 1 == n_layers ? 1 : n / 2;
+    const int64_t shape[5][2] = {{2 * m, n}, {n, n + m}, {n, -1}, {2 * m, n}, {2 * m, -1}};
+    for (int k = 0; k < 5; ++k) {
+      Tensor t = f32(weights[5 * b + k].detach(), who);
+      const bool ok = shape[k][1] < 0 ? (t.dim() == 1 && t.size(0) == shape[k][0]) : (t.dim() == 2 && t.size(0) == shape[k][0] && t.size(1) == shape[k][1]);
+      TORCH_CHECK(ok, who, ": weight ", 5 * b + k, " has shape ", t.sizes(), ", not that of the pyramidal head (block ", b, ": ", n, " -> ", m, ")");
+      if (((uintptr_t)t.data_ptr() & 15) != 0) t = t.clone();
+      w.push_back(t);
+      ptr.push_back(fp(t));
+    }
+    n = m;
+  }
+  if (N && (((uintptr_t)s.data_ptr() & 15) != 0)) s = s.clone();
+  if (N && (((uintptr_t)v.data_ptr() & 15) != 0)) v = v.clone();
+  c10::DeviceGuard guard(s.device());
+  Tensor so = at::empty({N, 1}, s.options()), vo = at::empty({N, 3, 1}, s.options());
+  check(spk_gated_mlp_fwd_f32(N ? fp(s) : nullptr, N ? fp(v) : nullptr, N, (int32_t)F, (int32_t)n_layers, (int32_t)act, ptr.data(), N ? fpm(so) : nullptr,
+                              N ? fpm(vo) : nullptr, stream_of(s)));
+  return {so, vo};
+}
+// dipole_moment: (mu [n_mol, 3], charges [N, 1]) from the latent charges q [N, 1], the atomic dipoles d [N, 3(, 1)] (None: scalar route) and the
+// positions; with `correct` the charges are shifted so that they sum to total_charge [n_mol] (None: zero) per molecule.  idx_m ascending.
+std::tuple<Tensor, Tensor> dipole_moment_raw(const Tensor& q_in, const c10::optional<Tensor>& d_in, const Tensor& R_in, const Tensor& idx_m_in, int64_t n_mol,
+                                             const c10::optional<Tensor>& total_in, bool correct) {
+  const char* who = "dipole_moment";
+  Tensor q = f32(q_in.detach(), who), R = f32(R_in.detach(), who), idx_m = i64(idx_m_in, who);
+  Tensor d = (d_in.has_value() && d_in->defined()) ? f32(d_in->detach(), who) : Tensor();
+  Tensor tot = (total_in.has_value() && total_in->defined()) ? f32(total_in->detach(), who) : Tensor();
+  const int64_t N = R.size(0);
+  TORCH_CHECK(R.dim() == 2 && R.size(1) == 3 && q.numel() == N && idx_m.dim() == 1 && idx_m.size(0) == N && n_mol >= 0, who, ": q [N(, 1)], R [N, 3], idx_m [N]");
+  TORCH_CHECK(!d.defined() || d.numel() == 3 * N, who, ": d [N, 3(, 1)]");
+  TORCH_CHECK(!tot.defined() || tot.numel() == n_mol, who, ": total_charge [n_mol]");
+  c10::DeviceGuard guard(R.device());
+  Tensor mu = at::empty({n_mol, 3}, R.options()), qo = at::empty({N, 1}, R.options());
+  check(spk_moment_reduce_f32(SPK_MOMENT_DIPOLE, N ? fp(q) : nullptr, (N && d.defined()) ? fp(d) : nullptr, N ? fp(R) : nullptr,
+                              N ? idx_m.data_ptr<int64_t>() : nullptr, N, n_mol, tot.defined() && n_mol ? fp(tot) : nullptr, correct ? 1 : 0,
+                              n_mol ? fpm(mu) : nullptr, N ? fpm(qo) : nullptr, stream_of(R)));
+  return {mu, qo};
+}
+// polarizability: alpha [n_mol, 3, 3] = sum_i a0_i 1 + d_i R_i^T + R_i d_i^T, symmetric to the bit.  idx_m ascending.
+Tensor polarizability_raw(const Tensor& a0_in, const Tensor& d_in, const Tensor& R_in, const Tensor& idx_m_in, int64_t n_mol) {
+  const char* who = "polarizability";
+  Tensor a0 = f32(a0_in.detach(), who), d = f32(d_in.detach(), who), R = f32(R_in.detach(), who), idx_m = i64(idx_m_in, who);
+  const int64_t N = R.size(0);
+  TORCH_CHECK(R.dim() == 2 && R.size(1) == 3 && a0.numel() == N && d.numel() == 3 * N && idx_m.dim() == 1 && idx_m.size(0) == N && n_mol >= 0, who,
+              ": a0 [N(, 1)], d [N, 3(, 1)], R [N, 3], idx_m [N]");
+  c10::DeviceGuard guard(R.device());
+  Tensor al = at::empty({n_mol, 3, 3}, R.options());
+  check(spk_moment_reduce_f32(SPK_MOMENT_POLARIZABILITY, N ? fp(a0) : nullptr, N ? fp(d) : nullptr, N ? fp(R) : nullptr, N ? idx_m.data_ptr<int64_t>() : nullptr,
+                              N, n_mol, nullptr, 0, n_mol ? fpm(al) : nullptr, nullptr, stream_of(R)));
+  return al;
+}
+
 // Energies, forces AND the virial W = dE/dS of the strain (Strain -> ... -> Forces(calc_stress=True), atomistic/response.py:434-464) for eval:
 // (E, F = -dE/dR, W [n_mol, 3, 3], scalar_representation), no autograd node.  E and F are those of schnet_potential_forces bit for bit: the same
 // two launches (the backward also writes dE/dr of every edge) or the same three stages (whose dE/dr is kept), plus the virial launches.
@@ -1923,6 +1993,13 @@ Tensor zbl_forces_meta(const Tensor& R, const c10::optional<Tensor>&, const Tens
                        c10::optional<Tensor>) {
   return at::empty({n_mol}, R.options());
 }
+std::tuple<Tensor, Tensor> gated_mlp_meta(const Tensor& s, const Tensor&, at::TensorList, int64_t) {
+  return {at::empty({s.size(0), 1}, s.options()), at::empty({s.size(0), 3, 1}, s.options())};
+}
+std::tuple<Tensor, Tensor> dipole_moment_meta(const Tensor&, const c10::optional<Tensor>&, const Tensor& R, const Tensor&, int64_t n_mol, const c10::optional<Tensor>&, bool) {
+  return {at::empty({n_mol, 3}, R.options()), at::empty({R.size(0), 1}, R.options())};
+}
+Tensor polarizability_meta(const Tensor&, const Tensor&, const Tensor& R, const Tensor&, int64_t n_mol) { return at::empty({n_mol, 3, 3}, R.options()); }
 Tensor pairwise_meta(const Tensor& R, const Tensor& ii, const Tensor&, const c10::optional<Tensor>&) { return at::empty({ii.size(0), 3}, R.options()); }
 Tensor pairwise_backward_meta(const Tensor& gr, const Tensor&, const Tensor&, int64_t n) { return at::empty({n, 3}, gr.options()); }
 Tensor dense_meta(const Tensor& x, const Tensor& w, const c10::optional<Tensor>&, int64_t) {
@@ -2005,6 +2082,10 @@ TORCH_LIBRARY(spk_hip, m) {
   m.def("zbl(Tensor r_ij, Tensor Z, Tensor idx_i, Tensor idx_j, Tensor idx_m, int n_mol, Tensor params) -> (Tensor, Tensor)");
   m.def("zbl_backward(Tensor gE, Tensor r_ij, Tensor Z, Tensor idx_i, Tensor idx_j, Tensor idx_m, int n_mol, Tensor params) -> Tensor");
   m.def("zbl_forces(Tensor R, Tensor? offsets, Tensor Z, Tensor idx_i, Tensor idx_j, Tensor idx_m, int n_mol, Tensor params, Tensor(a!) F, Tensor(b!)? W) -> Tensor");  // eval: E_zbl; F, W += in place
+  // tensorial heads (atomistic/atomwise.py:91-293; csrc/spk_tensorial.hip), eval only: the gated equivariant MLP in one launch, the moments in one more
+  m.def("gated_mlp(Tensor s, Tensor v, Tensor[] weights, int act) -> (Tensor, Tensor)");
+  m.def("dipole_moment(Tensor q, Tensor? d, Tensor R, Tensor idx_m, int n_mol, Tensor? total_charge, bool correct) -> (Tensor, Tensor)");
+  m.def("polarizability(Tensor a0, Tensor d, Tensor R, Tensor idx_m, int n_mol) -> Tensor");
   m.def("potential_plan(Tensor idx_i, Tensor idx_j, int n_atoms, Tensor idx_m, int n_mol) -> int");
   m.def("eval_guard(Tensor(a) y, Tensor[] params) -> Tensor(a)");      // alias of y whose backward raises the eval-only message
   m.def("schnet_potential_forward(Tensor x0, Tensor R, Tensor? offsets, Tensor idx_i, Tensor idx_j, Tensor idx_m, int n_mol, Tensor[] weights, Tensor[] head, int n_filters, int rbf_kind, Tensor rbf_p0, Tensor? rbf_p1, float cutoff, int head_act) -> (Tensor, Tensor, Tensor, Tensor)");
@@ -2058,6 +2139,9 @@ TORCH_LIBRARY_IMPL(spk_hip, CUDA, m) {   // "CUDA" is the dispatch key of ROCm d
   m.impl("zbl", zbl_forward_raw);
   m.impl("zbl_backward", zbl_backward_raw);
   m.impl("zbl_forces", zbl_forces_raw);
+  m.impl("gated_mlp", gated_mlp_raw);
+  m.impl("dipole_moment", dipole_moment_raw);
+  m.impl("polarizability", polarizability_raw);
   m.impl("potential_plan", potential_plan_op);
   m.impl("schnet_potential_backward", schnet_potential_backward_raw);
   m.impl("dense_forward", dense_raw);
@@ -2100,7 +2184,8 @@ TORCH_LIBRARY_IMPL(spk_hip, CPU, m) {
                            "dense_forward", "dense_backward_input", "radial_cutoff_backward", "schnet_forward", "schnet_backward", "painn_forward",
                            "painn_backward", "atomwise_forward", "atomwise_backward", "edge_plan", "static_declare", "static_declare_range", "schnet_potential",
                            "schnet_potential_forward", "schnet_potential_backward", "schnet_potential_forces", "painn_potential_forces", "potential_plan",
-                           "schnet_potential_stress", "painn_potential_stress", "zbl", "zbl_backward", "zbl_forces"})
+                           "schnet_potential_stress", "painn_potential_stress", "zbl", "zbl_backward", "zbl_forces", "gated_mlp",
+                           "dipole_moment", "polarizability"})
     m.impl(name, torch::CppFunction::makeFromBoxedFunction<&no_cpu_boxed>());
   for (const char* name : kTrainOps) m.impl(name, torch::CppFunction::makeFromBoxedFunction<&no_cpu_boxed>());
   for (const char* name : kFmOps) m.impl(name, torch::CppFunction::makeFromBoxedFunction<&no_cpu_boxed>());
@@ -2136,6 +2221,9 @@ TORCH_LIBRARY_IMPL(spk_hip, Meta, m) {
   m.impl("zbl", zbl_meta);
   m.impl("zbl_backward", zbl_backward_meta);
   m.impl("zbl_forces", zbl_forces_meta);
+  m.impl("gated_mlp", gated_mlp_meta);
+  m.impl("dipole_moment", dipole_moment_meta);
+  m.impl("polarizability", polarizability_meta);
   train_impl_meta(m);
   fm_impl_meta(m);
 }

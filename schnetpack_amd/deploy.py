@@ -39,6 +39,10 @@ def _np(t):
 
 
 def _find_head(model):
+    for m in model.output_modules:
+        if type(m).__name__ in ("DipoleMoment", "Polarizability"):
+            raise ValueError("deploy: the model has a tensorial head (%s); the .spkm file and the runtime carry energies, forces and the virial only "
+                             "-- export the model without it" % type(m).__name__)
     heads = [m for m in model.output_modules if hasattr(m, "outnet")]
     forces = [m for m in model.output_modules if type(m).__name__ == "Forces"]
     if len(heads) != 1 or len(forces) != 1:

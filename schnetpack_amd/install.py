@@ -6,8 +6,9 @@
 Patches, inside the already imported ``schnetpack`` package, exactly the names of SURVEY.md
 section 8(b): ``nn.scatter_add`` (+ ``nn.scatter.scatter_add``), ``nn.Dense``, ``nn.GaussianRBF``,
 ``nn.BesselRBF``, ``nn.CosineCutoff``, ``representation.{SchNet, SchNetInteraction, PaiNN,
-PaiNNInteraction, PaiNNMixing}``, ``atomistic.PairwiseDistances``, ``atomistic.ZBLRepulsionEnergy`` and
-``atomistic.Aggregation``.  Classes are replaced both on
+PaiNNInteraction, PaiNNMixing}``, ``atomistic.PairwiseDistances``, ``atomistic.ZBLRepulsionEnergy``,
+``atomistic.Aggregation``, ``nn.GatedEquivariantBlock``, ``nn.build_gated_equivariant_mlp`` and
+``atomistic.{DipoleMoment, Polarizability}``.  Classes are replaced both on
 the package and on the defining sub-module, so Hydra ``_target_`` paths and pickled models
 (``torch.load`` resolves ``schnetpack.representation.painn.PaiNN`` by attribute) pick up the
 mirrors; parameter names and shapes are identical, so existing ``state_dict``s and whole-model
@@ -73,6 +74,10 @@ def _fused_potential_call(orig_call):
         if mode == 0:
             return orig_call(self, *args, **kwargs)
         inputs = self.initialize_derivatives(args[0])
+        n_tail = self.__dict__.get("_spk_hip_tail")
+        if n_tail is None:      # DipoleMoment / Polarizability mirrors at the end of output_modules: they run behind the fused call
+            n_tail = M.tensorial_tail(list(self.output_modules))
+            self.__dict__["_spk_hip_tail"] = n_tail
         if mode == 2:
             inputs = M.potential_forces_forward(self, inputs)
         elif mode == 3:
@@ -80,7 +85,7 @@ def _fused_potential_call(orig_call):
         elif mode in (4, 5):      # ... with a ZBL repulsion aggregated into the energy: one more launch
             lay = self.__dict__.get("_spk_hip_zbl")
             if lay is None:
-                lay = M.zbl_layout(list(self.output_modules))
+                lay = M.zbl_layout(list(self.output_modules)[:len(self.output_modules) - n_tail])
                 self.__dict__["_spk_hip_zbl"] = lay
             inputs = M.potential_stress_forward(self, inputs, lay) if mode == 5 else M.potential_forces_forward(self, inputs, lay)
         else:
@@ -88,6 +93,8 @@ def _fused_potential_call(orig_call):
             for i, m in enumerate(self.output_modules):
                 if i > 0:
                     inputs = m(inputs)
+            n_tail = 0          # (the loop above has run them)
+        inputs = M.run_tail(self, inputs, n_tail)
         inputs = self.postprocess(inputs)
         return self.extract_outputs(inputs)
 
@@ -151,6 +158,14 @@ def install(spk=None, verbose=False, fused_head=True, neighbor_lists=False, fuse
         _set(mod, "ZBLRepulsionEnergy", A.ZBLRepulsionEnergy, log)
     for mod in (getattr(spk, "atomistic", None), sub("atomistic.aggregation")):
         _set(mod, "Aggregation", A.Aggregation, log)
+    # the tensorial heads and the gated equivariant blocks they are made of (when the reference has loaded them)
+    for mod in (getattr(spk, "nn", None), sub("nn.equivariant")):
+        _set(mod, "GatedEquivariantBlock", N.GatedEquivariantBlock, log)
+    for mod in (getattr(spk, "nn", None), sub("nn.blocks")):
+        _set(mod, "build_gated_equivariant_mlp", N.build_gated_equivariant_mlp, log)
+    for mod in (getattr(spk, "atomistic", None), sub("atomistic.atomwise")):
+        _set(mod, "DipoleMoment", A.DipoleMoment, log)
+        _set(mod, "Polarizability", A.Polarizability, log)
     if fused_potential and fused_head:
         mb = sub("model.base")
         cls = getattr(mb, "NeuralNetworkPotential", None) if mb is not None else None

@@ -6,7 +6,7 @@ import torch
 import torch.nn as nn
 
 from . import properties
-from .atomistic import Aggregation, Atomwise, Forces, PairwiseDistances, Strain, ZBLRepulsionEnergy
+from .atomistic import Aggregation, Atomwise, DipoleMoment, Forces, PairwiseDistances, Polarizability, Strain, ZBLRepulsionEnergy
 from .nn import CosineCutoff, GaussianRBF, BesselRBF
 from .representation import PaiNN, SchNet
 
@@ -61,6 +61,26 @@ def zbl_layout(outs) -> Optional[Tuple[int, int, int, int]]:
     return ih, iz, 2, 3
 
 
+def tensorial_tail(outs) -> int:
+    """Number of ``DipoleMoment`` / ``Polarizability`` mirror instances at the END of ``output_modules``.  They read the representation and the
+    positions only, so the modules before them classify as if the tail were not there (:func:`classify_potential`) and the tail runs on the
+    dict the fused route returns (:func:`run_tail`)."""
+    n = 0
+    while n < len(outs) and type(outs[len(outs) - 1 - n]) in (DipoleMoment, Polarizability):
+        n += 1
+    return n
+
+
+def run_tail(model, inputs: Dict[str, torch.Tensor], n_tail: int) -> Dict[str, torch.Tensor]:
+    """The last ``n_tail`` output modules on the dict of a fused force call (``scalar_representation``, ``vector_representation`` and the positions
+    are in it)."""
+    if n_tail > 0:
+        outs = list(model.output_modules)
+        for m in outs[len(outs) - n_tail:]:
+            inputs = m(inputs)
+    return inputs
+
+
 def classify_potential(model) -> int:
     """0: module-by-module.  1: the standard potential -- ``PairwiseDistances`` -> fused ``SchNet`` -> ``Atomwise`` (default
     head, summed or averaged over the molecule) -> ``Forces`` without stress: representation + head are ONE operator.
@@ -70,9 +90,12 @@ def classify_potential(model) -> int:
     4 / 5: forms 2 / 3 with a ``ZBLRepulsionEnergy`` next to the head, an ``Aggregation`` of the two energies and ``Forces`` of the sum
     (:func:`zbl_layout`): the same operators, then one ``zbl_forces`` operator (a row pass, two reductions, a row-pointer kernel) that adds the
     repulsion into their forces and virial, and one add of the two energies.
+    A tail of ``DipoleMoment`` / ``Polarizability`` mirrors (:func:`tensorial_tail`) is set aside first: the rest classifies as above and the
+    tail runs module by module behind the fused call; such a module anywhere else gives 0.
     Works on any model with the reference's ``NeuralNetworkPotential`` layout (model/base.py:132-190), i.e. also on the
     reference's own class around the HIP modules."""
     rep, ins, outs = model.representation, list(model.input_modules), list(model.output_modules)
+    outs = outs[:len(outs) - tensorial_tail(outs)]
     is_painn = isinstance(rep, PaiNN)
     if not (isinstance(rep, (SchNet, PaiNN)) and rep._fused and len(rep.interactions) > 0):
         return 0
@@ -343,7 +366,9 @@ class NeuralNetworkPotential(nn.Module):
         self._potential_stress = mode == 3
         self._potential_zbl = mode in (4, 5)
         self._zbl_stress = mode == 5
-        self._zbl_layout = list(zbl_layout(list(self.output_modules)) or []) if mode in (4, 5) else []
+        #: ``DipoleMoment`` / ``Polarizability`` modules at the end of ``output_modules``: they run behind the fused force call
+        self._n_tail = tensorial_tail(list(self.output_modules))
+        self._zbl_layout = list(zbl_layout(list(self.output_modules)[:len(self.output_modules) - self._n_tail]) or []) if mode in (4, 5) else []
         self._fm_head_act = classify_fm(self)
         self.fm_engine = self._fm_head_act > 0
 
@@ -352,6 +377,8 @@ class NeuralNetworkPotential(nn.Module):
         super().__setstate__(state)
         if "_potential_zbl" not in self.__dict__:
             self._potential_zbl, self._zbl_stress, self._zbl_layout = False, False, []
+        if "_n_tail" not in self.__dict__:        # ... or before the tensorial heads
+            self._n_tail = 0
 
     @torch.jit.unused
     def _potential_fm_forward(self, inputs: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
@@ -363,16 +390,17 @@ class NeuralNetworkPotential(nn.Module):
 
     @torch.jit.unused
     def _potential_forces_forward(self, inputs: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
-        return potential_forces_forward(self, inputs)
+        return run_tail(self, potential_forces_forward(self, inputs), self._n_tail)
 
     @torch.jit.unused
     def _potential_zbl_forward(self, inputs: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
         lay = (self._zbl_layout[0], self._zbl_layout[1], self._zbl_layout[2], self._zbl_layout[3])
-        return potential_stress_forward(self, inputs, lay) if self._zbl_stress else potential_forces_forward(self, inputs, lay)
+        inputs = potential_stress_forward(self, inputs, lay) if self._zbl_stress else potential_forces_forward(self, inputs, lay)
+        return run_tail(self, inputs, self._n_tail)
 
     @torch.jit.unused
     def _potential_stress_forward(self, inputs: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
-        return potential_stress_forward(self, inputs)
+        return run_tail(self, potential_stress_forward(self, inputs), self._n_tail)
 
     def forward(self, inputs: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
         for p in self.required_derivatives:

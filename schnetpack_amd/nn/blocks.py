@@ -1,13 +1,14 @@
-"""Mirror of ``schnetpack.nn.blocks.build_mlp`` (nn/blocks.py:12-76)."""
-from typing import Callable, Optional, Sequence, Union
+"""Mirrors of ``schnetpack.nn.blocks.build_mlp`` (nn/blocks.py:12-76) and ``build_gated_equivariant_mlp`` (nn/blocks.py:79-156)."""
+from typing import Callable, Optional, Sequence, Tuple, Union
 
 import torch
 import torch.nn.functional as F
 from torch import nn
 
 from .base import Dense
+from .equivariant import GatedEquivariantBlock
 
-__all__ = ["build_mlp"]
+__all__ = ["build_mlp", "build_gated_equivariant_mlp"]
 
 
 def build_mlp(n_in: int, n_out: int, n_hidden: Optional[Union[int, Sequence[int]]] = None,
@@ -29,3 +30,41 @@ def build_mlp(n_in: int, n_out: int, n_hidden: Optional[Union[int, Sequence[int]
     else:
         layers.append(Dense(sizes[-2], sizes[-1], activation=None, bias=last_bias))
     return nn.Sequential(*layers)
+
+
+class _GatedSequential(nn.Sequential):
+    """``nn.Sequential`` over modules that map a (scalars, vectors) pair to such a pair, with the annotation TorchScript needs (the plain
+    container's ``forward`` is inferred to take a tensor); same ``state_dict`` keys."""
+
+    def forward(self, inputs: Tuple[torch.Tensor, torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
+        for module in self:
+            inputs = module(inputs)
+        return inputs
+
+
+def build_gated_equivariant_mlp(n_in: int, n_out: int, n_hidden: Optional[Union[int, Sequence[int]]] = None,
+                                n_gating_hidden: Optional[Union[int, Sequence[int]]] = None, n_layers: int = 2,
+                                activation: Callable = F.silu, sactivation: Callable = F.silu) -> nn.Module:
+    """``n_layers`` ``GatedEquivariantBlock``s with the widths of :func:`build_mlp`; the gating networks are as wide as their block's
+    input unless ``n_gating_hidden`` says otherwise, the last block has no scalar activation."""
+    if n_hidden is None:
+        c = n_in
+        sizes = []
+        for _ in range(n_layers):
+            sizes.append(c)
+            c = max(n_out, c // 2)
+        sizes.append(n_out)
+    else:
+        hidden = [n_hidden] * (n_layers - 1) if type(n_hidden) is int else list(n_hidden)
+        sizes = [n_in] + hidden + [n_out]
+    if n_gating_hidden is None:
+        gating = sizes[:-1]
+    elif type(n_gating_hidden) is int:
+        gating = [n_gating_hidden] * n_layers
+    else:
+        gating = list(n_gating_hidden)
+    layers = [GatedEquivariantBlock(n_sin=sizes[i], n_vin=sizes[i], n_sout=sizes[i + 1], n_vout=sizes[i + 1], n_hidden=gating[i],
+                                    activation=activation, sactivation=sactivation) for i in range(n_layers - 1)]
+    layers.append(GatedEquivariantBlock(n_sin=sizes[-2], n_vin=sizes[-2], n_sout=sizes[-1], n_vout=sizes[-1], n_hidden=gating[-1],
+                                        activation=activation, sactivation=None))
+    return _GatedSequential(*layers)
