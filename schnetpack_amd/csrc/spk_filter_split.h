@@ -68,27 +68,38 @@ struct MlW1Image {
   static constexpr int BYTES = 4096 + (KPB > 2 ? (KPB == 4 ? 4096 : 2048) : 0);     // per image (high or low)
 };
 __device__ __forceinline__ int ml_w1_k(int s, int hi, int e) { return s == 0 ? 8 * hi + e : (e < 4 ? 16 + 4 * hi + e : 20 + 4 * hi + e); }
+// in two parts, so that a caller can have the loads of a slot in flight together with its other staging loads (one round trip to L2
+// instead of one per staged tensor): ml_stage_w1_load() requests the slot's values (x0: k-step 0, x1: k-step 1, used when KPB > 2),
+// ml_stage_w1_store() splits them and writes both images
 template <int KPB>
-__device__ __forceinline__ void ml_stage_w1_split(char* __restrict__ ih, char* __restrict__ il, const float* __restrict__ w1, int n_rbf, int slot) {
-  if (slot >= 256) return;
+__device__ __forceinline__ void ml_stage_w1_load(float (&x0)[8], float (&x1)[8], const float* __restrict__ w1, int n_rbf, int slot) {
   const int lane = slot & 63, t = slot >> 6, hi = lane >> 5;
   const float* src = w1 + (32 * t + (lane & 31)) * n_rbf;
-  float x[8];
 #pragma unroll
-  for (int e = 0; e < 8; ++e) { const int k = ml_w1_k(0, hi, e); x[e] = k < n_rbf ? src[k] : 0.f; }
+  for (int e = 0; e < 8; ++e) { const int k = ml_w1_k(0, hi, e); x0[e] = k < n_rbf ? src[k] : 0.f; }
+#pragma unroll
+  for (int e = 0; e < 8; ++e) { const int k = ml_w1_k(1, hi, e); x1[e] = (KPB > 2 && k < n_rbf && (KPB == 4 || e < 4)) ? src[k] : 0.f; }
+}
+template <int KPB>
+__device__ __forceinline__ void ml_stage_w1_store(char* __restrict__ ih, char* __restrict__ il, const float (&x0)[8], const float (&x1)[8], int slot) {
   h16x8 h, l;
-  sp_split8(x, h, l);
+  sp_split8(x0, h, l);
   ((h16x8*)ih)[slot] = h; ((h16x8*)il)[slot] = l;
   if (KPB > 2) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { const int k = ml_w1_k(1, hi, e); x[e] = (k < n_rbf && (KPB == 4 || e < 4)) ? src[k] : 0.f; }
-    sp_split8(x, h, l);
+    sp_split8(x1, h, l);
     if (KPB == 4) { ((h16x8*)(ih + 4096))[slot] = h; ((h16x8*)(il + 4096))[slot] = l; }
     else {
       ((h16x4*)(ih + 4096))[slot] = h16x4{h[0], h[1], h[2], h[3]};
       ((h16x4*)(il + 4096))[slot] = h16x4{l[0], l[1], l[2], l[3]};
     }
   }
+}
+template <int KPB>
+__device__ __forceinline__ void ml_stage_w1_split(char* __restrict__ ih, char* __restrict__ il, const float* __restrict__ w1, int n_rbf, int slot) {
+  if (slot >= 256) return;
+  float x0[8], x1[8];
+  ml_stage_w1_load<KPB>(x0, x1, w1, n_rbf, slot);
+  ml_stage_w1_store<KPB>(ih, il, x0, x1, slot);
 }
 template <int KPB>
 __device__ __forceinline__ void ml_w1_operand(const char* __restrict__ ih, const char* __restrict__ il, int s, int slot, h16x8& h, h16x8& l) {

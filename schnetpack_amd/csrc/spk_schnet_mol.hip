@@ -18,7 +18,8 @@
 //          y[atom, channel] by the 0/1 incidence of the tile ON THE MATRIX CORE; branch-free: padding rows of the last tile
 //          repeat its last pair with weight zero.  No atomics, no scatter pass, deterministic
 //   C. t = ssp((y_team0 + y_team1) W3^T + b3);  x += t W4^T + b4      (two T-GEMM phases; the idle team stages the filter
-//        weights of the next interaction into LDS meanwhile)
+//        weights of the next interaction into LDS meanwhile, all its loads in flight at once: one round trip to L2.  Split
+//        instances: t is written to LDS as the split image and the second phase reads it as it lies -- split once, at the writer)
 // then the energy head on the atom tile that is still in LDS.  Matrix products run on the split-precision path (spk_split.h: fp32
 // operands as two fp16 images on v_mfma_f32_32x32x16_f16; 1e-5 parity with the reference rules out plain bf16 / fp16), or, with
 // spk_set_split(0), on v_mfma_f32_32x32x2_f32 (the <KPB, false> instances).
@@ -89,6 +90,8 @@ struct MolFwdArgs {
   long long* dbg;           // tuning aid: cycle stamps, see spk_schnet_mol_set_debug_buffer (null in production)
 };
 #define ML_STAMP(n) do { if (a.dbg && blockIdx.x == 0 && threadIdx.x == 0) a.dbg[n] = (long long)__builtin_readcyclecounter(); } while (0)
+// per wave, when its memory operations have landed: entries [n, n + 8) -- which half of a Dense phase the barrier behind it waits for
+#define ML_WSTAMP(n) do { if (a.dbg && blockIdx.x == 0 && lane == 0) { __builtin_amdgcn_s_waitcnt(0); a.dbg[(n) + wv] = (long long)__builtin_readcyclecounter(); } } while (0)
 
 // per pair of a group: local atoms i | j << 8, distance, f_c(d), f_c'(d) -- computed once per group, used by every interaction
 struct __attribute__((aligned(16))) MolPair { int ij; float d; float fc; float dfc; };
@@ -201,6 +204,17 @@ int spk_schnet_mol_pack_w2(const float* w2, float* image, hipStream_t stream) {
   SPK_LAUNCH_CHECK();
   return SPK_OK;
 }
+// the copy by 256 threads with ALL 16 pieces of a thread in flight at once (64 VGPRs), in two parts like ml_stage_w1_load / _store: a
+// team that stages during a Dense phase has nothing else in its registers, and every further round trip to L2 is time the team
+// that runs the GEMM spends waiting at the barrier
+__device__ __forceinline__ void ml_w2_image_load(f32x4 (&v)[16], const float* __restrict__ img, int t2) {
+#pragma unroll
+  for (int p = 0; p < 16; ++p) v[p] = *(const f32x4*)((const char*)img + (unsigned)((t2 + p * 256) * 16));
+}
+__device__ __forceinline__ void ml_w2_image_store(float* __restrict__ dst, const f32x4 (&v)[16], int t2) {
+#pragma unroll
+  for (int p = 0; p < 16; ++p) *(f32x4*)(dst + (t2 + p * 256) * 4) = v[p];
+}
 template <int NTHREADS>
 __device__ __forceinline__ void ml_stage_w2_image(float* __restrict__ dst, const float* __restrict__ img, int tid) {
   constexpr int PER = 4096 / NTHREADS;      // 16-byte pieces per thread (64 KB)
@@ -282,6 +296,10 @@ __device__ __forceinline__ void ml_dense_load(f32x4 (&av)[16], const float* __re
 // Split form of a Dense block (SP; spk_split.h): `av` then holds chunks of the SPLIT weight image (k_pack_weight_split: chunk 2 s = the high
 // parts of k-step s, chunk 2 s + 1 its low parts -- same bytes, same offsets as the fp32 image), the activations are read from LDS
 // as eight consecutive fp32 values per k-step and split in registers; three f16 instructions per 16 k instead of eight f32 ones.
+// This on-the-fly form serves the tiles that must stay fp32 in LDS because something else reads or accumulates into them (x, the two
+// partial sums y, dL/dx, the row sums dL/dh); a tile that is ONLY a B operand is written as the split image instead and read by
+// ml_dense_mma_sp_pre below (phase C2 of the forward).  The Dense phases of the backward stay on this form: their length is set by
+// the half of the workgroup that stages weights, not by the GEMM waves (profiles/r09_mol_dense_operands.md).
 #ifndef SP_AHEAD
 #define SP_AHEAD 1      // k-steps of LDS operands requested ahead of their use in the split Dense blocks
 #endif
@@ -304,6 +322,44 @@ __device__ __forceinline__ f32x16 ml_dense_mma_sp(const f32x4* __restrict__ av, 
   }
   SP_FOLD(acc, cx);
   return acc;
+}
+// Pre-split form: the activation tile lies in LDS as the SPLIT IMAGE its writer made -- row = atom, stride ML_LD * 4 bytes, bytes
+// [0, 256) the 128 high halves, [256, 512) the 128 low halves (the layout of the hidden tile of phase A).  A k-step is two 16-byte
+// reads and SP_STEP: no vector-unit work in the loop, so the operands are requested SP_PRE_AHEAD k-steps ahead (4 = all of a half
+// tile up front; phase C2 of the forward 3.9 k cycles on the fp32 tile, 2.9 k with 2 ahead, 2.5 k with 4:
+// profiles/r09_mol_dense_operands.md).  Same products in the same order as ml_dense_mma_sp on the fp32 tile: the writer splits the
+// same fp32 values with the same sp_split.
+#ifndef SP_PRE_AHEAD
+#define SP_PRE_AHEAD 4
+#endif
+template <int NS>
+__device__ __forceinline__ f32x16 ml_dense_mma_sp_pre(const f32x4* __restrict__ av, const char* __restrict__ brow /* lane's row + 16 hi + first k-step */, f32x16 acc) {
+  f32x16 cx;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) cx[r] = 0.f;
+  h16x8 bh[NS], bl[NS];
+#pragma unroll
+  for (int s = 0; s < SP_PRE_AHEAD && s < NS; ++s) { bh[s] = *(const h16x8*)(brow + 32 * s); bl[s] = *(const h16x8*)(brow + 256 + 32 * s); }
+  ML_PIN();
+#pragma unroll
+  for (int s = 0; s < NS; ++s) {
+    if (s + SP_PRE_AHEAD < NS) { bh[s + SP_PRE_AHEAD] = *(const h16x8*)(brow + 32 * (s + SP_PRE_AHEAD)); bl[s + SP_PRE_AHEAD] = *(const h16x8*)(brow + 256 + 32 * (s + SP_PRE_AHEAD)); ML_PIN(); }
+    SP_STEP(__builtin_bit_cast(h16x8, av[2 * s]), __builtin_bit_cast(h16x8, av[2 * s + 1]), bh[s], bl[s], acc, cx);
+  }
+  SP_FOLD(acc, cx);
+  return acc;
+}
+// half a Dense tile (8 k-blocks = 4 k-steps) on a split image
+__device__ __forceinline__ f32x16 ml_dense_mma8_pre(const f32x4 (&av)[8], const float* __restrict__ sIn, int lane, int half, f32x16 acc) {
+  return ml_dense_mma_sp_pre<4>(av, (const char*)sIn + (lane & 31) * (ML_LD * 4) + 16 * (lane >> 5) + 128 * half, acc);
+}
+// the writer's side: four consecutive K values of row `row` -> their place in the split image (two 8-byte stores)
+__device__ __forceinline__ void ml_store_split4(float* __restrict__ tile, int row, int k0, const f32x4 v) {
+  h16x4 h, l;
+  sp_split4(v, h, l);
+  char* p = (char*)tile + row * (ML_LD * 4) + 2 * k0;
+  *(h16x4*)p = h;
+  *(h16x4*)(p + 256) = l;
 }
 template <bool SP = false>
 __device__ __forceinline__ f32x16 ml_dense_mma(const f32x4 (&av)[16], const float* __restrict__ sIn, int lane, f32x16 acc) {
@@ -683,6 +739,9 @@ __global__ __launch_bounds__(512) void k_schnet_mol_fwd(MolFwdArgs a) {
       ML_STAMP(4 + 5 * l);
 
       // ================= phase C1: pre3 = (y0 + y1) W3^T + b3 (saved), hidden = ssp(pre3) -> sH; the other team stages weights
+      // (split instances: the wave that computes the hidden layer writes it to sH as the SPLIT IMAGE, phase C2 reads it with
+      //  ml_dense_mma8_pre -- activations are split once, by whoever writes them.  The input of C1 stays on the on-the-fly form:
+      //  forming and splitting y0 + y1 once costs a pass of the workgroup and a barrier, and did not shorten the phase)
       f32x4 avC[8];        // team 0: first half of the weight tile of phase C2, requested BEFORE the stores of pre3 -- loads and
                            // stores share one in-order counter, a load issued behind a store cannot be waited for without it
       if (team == 0) {
@@ -699,19 +758,39 @@ __global__ __launch_bounds__(512) void k_schnet_mol_fwd(MolFwdArgs a) {
         for (int q = 0; q < 4; ++q) {
           const f32x4 pv = {acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]};
           if (el < na) ml_st<f32x4>(pre3_g + (size_t)a0 * NF + 32 * t, (unsigned)((el * NF + 8 * q + 4 * hi) * 4), pv);
-          *(f32x4*)(sH + el * ML_LD + 32 * t + 8 * q + 4 * hi) = f32x4{spk_fast_ssp(pv.x), spk_fast_ssp(pv.y), spk_fast_ssp(pv.z), spk_fast_ssp(pv.w)};
+          const f32x4 hv = {spk_fast_ssp(pv.x), spk_fast_ssp(pv.y), spk_fast_ssp(pv.z), spk_fast_ssp(pv.w)};
+          if constexpr (SP) ml_store_split4(sH, el, 32 * t + 8 * q + 4 * hi, hv);
+          else *(f32x4*)(sH + el * ML_LD + 32 * t + 8 * q + 4 * hi) = hv;
         }
       } else if (l + 1 < a.n_layers) {     // the filter GEMMs of this interaction are done: their LDS images can be replaced
         const int t2 = tid - 256;
+        bool staged = false;                // the split instances' one-round-trip form below has written the biases too
         if constexpr (SP) {
-          if (a.L[l + 1].w2_img) ml_stage_w2_image<256>(sW2, a.L[l + 1].w2_img, t2); else ml_stage_w2_split<256>(sW2h, sW2l, a.L[l + 1].w2, t2);
-          ml_stage_w1_split<KPB>(sW1h, sW1l, a.L[l + 1].w1, a.rb.n_rbf, t2);
+          if (a.L[l + 1].w2_img) {
+            // every staging load of this thread is requested before the first one is used: ONE round trip to L2.  In turn -- two
+            // batches of the W2 image, W1, the biases: four round trips -- this team reached the barrier 2 ... 3 k cycles behind the
+            // GEMM waves, and the phase was as long as the staging (ML_WSTAMP below; profiles/r09_mol_dense_operands.md)
+            f32x4 v[16];
+            float x0[8], x1[8], bv1 = 0.f, bv2 = 0.f;
+            ml_w2_image_load(v, a.L[l + 1].w2_img, t2);
+            ml_stage_w1_load<KPB>(x0, x1, a.L[l + 1].w1, a.rb.n_rbf, t2);
+            if (t2 < NF) { bv1 = a.L[l + 1].b1[t2]; bv2 = a.L[l + 1].b2[t2]; }
+            ML_PIN();
+            ml_w2_image_store(sW2, v, t2);
+            ml_stage_w1_store<KPB>(sW1h, sW1l, x0, x1, t2);
+            if (t2 < NF) { sb1[t2] = bv1; sb2[t2] = bv2; }
+            staged = true;
+          } else {
+            ml_stage_w2_split<256>(sW2h, sW2l, a.L[l + 1].w2, t2);
+            ml_stage_w1_split<KPB>(sW1h, sW1l, a.L[l + 1].w1, a.rb.n_rbf, t2);
+          }
         } else {
           ml_stage_packed<256, NF * NF / 4>(sW2, a.L[l + 1].w2, NF, KB2, t2);
           ml_stage_packed<256, NF * KPB * 2>(sW1, a.L[l + 1].w1, a.rb.n_rbf, KPB, t2);
         }
-        if (t2 < NF) { sb1[t2] = a.L[l + 1].b1[t2]; sb2[t2] = a.L[l + 1].b2[t2]; }
+        if (!staged && t2 < NF) { sb1[t2] = a.L[l + 1].b1[t2]; sb2[t2] = a.L[l + 1].b2[t2]; }
       }
+      if constexpr (SP) { if (l == 1) ML_WSTAMP(64); }
       __syncthreads();
       ML_STAMP(5 + 5 * l);
 
@@ -722,8 +801,13 @@ __global__ __launch_bounds__(512) void k_schnet_mol_fwd(MolFwdArgs a) {
         f32x16 acc;
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[r] = P.o2_b[32 * t + ml_row(r, hi)];
-        acc = ml_dense_mma8<SP>(avC, sH, lane, 0, acc);
-        acc = ml_dense_mma8<SP>(avB, sH, lane, 1, acc);
+        if constexpr (SP) {
+          acc = ml_dense_mma8_pre(avC, sH, lane, 0, acc);
+          acc = ml_dense_mma8_pre(avB, sH, lane, 1, acc);
+        } else {
+          acc = ml_dense_mma8(avC, sH, lane, 0, acc);
+          acc = ml_dense_mma8(avB, sH, lane, 1, acc);
+        }
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           float* xp = sX + el * ML_LD + 32 * t + 8 * q + 4 * hi;
@@ -733,6 +817,16 @@ __global__ __launch_bounds__(512) void k_schnet_mol_fwd(MolFwdArgs a) {
           *(f32x4*)xp = xv;
           if (l + 1 == a.n_layers && el < na) ml_st<f32x4>(a.x_out + (size_t)a0 * NF + 32 * t, (unsigned)((el * NF + 8 * q + 4 * hi) * 4), xv);
         }
+      }
+      if constexpr (SP) {
+        if (l == 1) ML_WSTAMP(72);
+        // (the interaction counter re-derived through an opaque asm, like the lane in the backward's derivative task -- DESIGN.md
+        //  section 4.3a.  Found by elimination, not in the listing: the per-wave stamp above alone took k_schnet_mol_fwd<3, true> from
+        //  136 to 92 B per lane of scratch and the group set-up from 10.4 k to 8.6 k cycles, and of what the stamp consists of only
+        //  this -- a counter the compiler cannot follow through the loop -- does the same without it; a scheduling barrier, a memory
+        //  clobber or a wait in its place do not.  Presumably the per-interaction addresses are otherwise formed ahead of the loop and
+        //  parked in scratch by the prologue.  profiles/r09_mol_dense_operands.md, section 2)
+        asm volatile("" : "+s"(l));
       }
       // (the barrier at the top of the next interaction / group closes this phase)
     }

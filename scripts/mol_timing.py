@@ -30,6 +30,10 @@ for base in (0, 32):
     for k in sorted(names):
         if k >= base and k < base + 32 and st[k]:
             print("  %-36s %8d  (+%d)" % (names[k], st[k] - st[base], st[k] - prev)); prev = st[k]
+# interaction 1 of the forward: when each wave was done with its half of a Dense phase (waves 0-3: the GEMM, 4-7: staging), cycles after the phase began
+for label, first, begin in (("fwd L1 C1", 64, 9), ("fwd L1 C2", 72, 10)):
+    if st[first]:
+        print("  %-10s waves 0-7 done after" % label, [st[first + w] - st[begin] for w in range(8)])
 import numpy as np
 print("bwd set-up of block 0 (cycles from the first instruction):", {k: st[k] - st[130] for k in (120, 121, 122, 123, 124, 32) if st[k]})
 blk = np.array(st[128:128 + 4 * 256]).reshape(256, 4)
