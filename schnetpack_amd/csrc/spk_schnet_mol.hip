@@ -20,7 +20,9 @@
 //   C. t = ssp((y_team0 + y_team1) W3^T + b3);  x += t W4^T + b4      (two T-GEMM phases; the idle team stages the filter
 //        weights of the next interaction into LDS meanwhile, all its loads in flight at once: one round trip to L2.  Split
 //        instances: t is written to LDS as the split image and the second phase reads it as it lies -- split once, at the writer)
-// then the energy head on the atom tile that is still in LDS.  Matrix products run on the split-precision path (spk_split.h: fp32
+// then the energy head on the atom tile that is still in LDS (split instances: its weights staged into the dead images of the filter
+// network by the team that idles in the last phase C1, x_L as a split image, the hidden layer on the split path).
+// Matrix products run on the split-precision path (spk_split.h: fp32
 // operands as two fp16 images on v_mfma_f32_32x32x16_f16; 1e-5 parity with the reference rules out plain bf16 / fp16), or, with
 // spk_set_split(0), on v_mfma_f32_32x32x2_f32 (the <KPB, false> instances).
 #include "spk_common.h"
@@ -225,6 +227,35 @@ __device__ __forceinline__ void ml_stage_w2_image(float* __restrict__ dst, const
     for (int p = 0; p < 8; ++p) v[p] = *(const f32x4*)((const char*)img + (unsigned)((tid + (p0 + p) * NTHREADS) * 16));
 #pragma unroll
     for (int p = 0; p < 8; ++p) *(f32x4*)(dst + (tid + (p0 + p) * NTHREADS) * 4) = v[p];
+  }
+}
+// The energy head's first layer, outnet.0.weight [H][128], as the split A-operand image of its H / 32 row tiles: slot (row tile,
+// k-step S, lane) = the eight values W[32 tile + el][16 S + 8 hi + e], high halves in `dh`, low halves in `dl` -- the slot order of
+// the W2 image, with the contraction index in natural order (the B operand is a split activation tile, ml_dense_mma_sp_pre).
+// Staged by 256 threads, in two parts like the W2 image above: eight slots per thread, all requested before the first is used;
+// slot t2 + 256 p lies in row tile p >> 1 (uniform), tiles >= HT are neither read nor written.
+__device__ __forceinline__ void ml_head_w1_load(f32x4 (&v)[16], const float* __restrict__ w1, int HT, int t2) {
+  const unsigned o = (unsigned)((((t2 & 31) * 128) + 16 * ((t2 >> 6) & 3) + 8 * ((t2 >> 5) & 1)) * 4);
+#pragma unroll
+  for (int p = 0; p < 8; ++p) {
+    v[2 * p] = f32x4{0.f, 0.f, 0.f, 0.f}; v[2 * p + 1] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if ((p >> 1) < HT) {
+      const unsigned op = o + (unsigned)((32 * (p >> 1) * 128 + 64 * (p & 1)) * 4);
+      v[2 * p] = *(const f32x4*)((const char*)w1 + op);
+      v[2 * p + 1] = *(const f32x4*)((const char*)w1 + op + 16u);
+    }
+  }
+}
+__device__ __forceinline__ void ml_head_w1_store(h16x8* __restrict__ dh, h16x8* __restrict__ dl, const f32x4 (&v)[16], int HT, int t2) {
+#pragma unroll
+  for (int p = 0; p < 8; ++p) {
+    if ((p >> 1) < HT) {
+      h16x4 ah, al, bh, bl;
+      sp_split4(v[2 * p], ah, al);
+      sp_split4(v[2 * p + 1], bh, bl);
+      dh[t2 + 256 * p] = sp_cat(ah, bh);
+      dl[t2 + 256 * p] = sp_cat(al, bl);
+    }
   }
 }
 // One 32-column output tile of a Dense layer over the 32 atom rows of the group, T-GEMM convention of spk_dense.hip:
@@ -789,8 +820,29 @@ __global__ __launch_bounds__(512) void k_schnet_mol_fwd(MolFwdArgs a) {
           ml_stage_packed<256, NF * KPB * 2>(sW1, a.L[l + 1].w1, a.rb.n_rbf, KPB, t2);
         }
         if (!staged && t2 < NF) { sb1[t2] = a.L[l + 1].b1[t2]; sb2[t2] = a.L[l + 1].b2[t2]; }
+      } else {
+        if constexpr (SP) {
+          if (a.head.w1) {
+            // last interaction: this team stages the energy head into the images of the filter network, which nobody reads after the
+            // last phase A -- outnet.0.weight as split A operand -> sW2, its bias -> sb1, outnet.1.weight -> sb2, its bias -> sW1[0];
+            // one round trip, so that the head below starts from LDS (the next group's set-up overwrites all of it behind the
+            // barrier at the top of the group loop)
+            const MolHeadDev& Hd = a.head;
+            int t2 = tid - 256;
+            asm volatile("" : "+v"(t2));      // opaque: the slot addresses are formed here, not ahead of the interaction loop
+            f32x4 v[16];
+            float hb1 = 0.f, hw2 = 0.f, hb2 = 0.f;
+            ml_head_w1_load(v, Hd.w1, Hd.H / 32, t2);
+            if (t2 < Hd.H) { hb1 = Hd.b1[t2]; hw2 = Hd.w2[t2]; }
+            if (t2 == 0 && Hd.b2) hb2 = Hd.b2[0];
+            ML_PIN();
+            ml_head_w1_store(sW2h, sW2l, v, Hd.H / 32, t2);
+            if (t2 < Hd.H) { sb1[t2] = hb1; sb2[t2] = hw2; }
+            if (t2 == 0) sW1[0] = hb2;
+          }
+        }
       }
-      if constexpr (SP) { if (l == 1) ML_WSTAMP(64); }
+      if constexpr (SP) { if (l == 1) ML_WSTAMP(64); if (l == 2) ML_WSTAMP(80); }
       __syncthreads();
       ML_STAMP(5 + 5 * l);
 
@@ -816,6 +868,9 @@ __global__ __launch_bounds__(512) void k_schnet_mol_fwd(MolFwdArgs a) {
           if (el >= na) xv = f32x4{0.f, 0.f, 0.f, 0.f};       // padding rows stay zero (in2f has no bias: h pads stay zero too)
           *(f32x4*)xp = xv;
           if (l + 1 == a.n_layers && el < na) ml_st<f32x4>(a.x_out + (size_t)a0 * NF + 32 * t, (unsigned)((el * NF + 8 * q + 4 * hi) * 4), xv);
+          if constexpr (SP) {      // x_L once more as the split image, the B operand of the energy head (sY: last read by phase C1)
+            if (l + 1 == a.n_layers) ml_store_split4(sY, el, 32 * t + 8 * q + 4 * hi, xv);
+          }
         }
       }
       if constexpr (SP) {
@@ -834,10 +889,44 @@ __global__ __launch_bounds__(512) void k_schnet_mol_fwd(MolFwdArgs a) {
       // ================= energy head on the atom tile that is still in LDS: y = w2 . act(W1 x + b1) + b2, E[mol] += sum_atoms y
       const MolHeadDev& Hd = a.head;
       const int HT = Hd.H / 32;
+      ML_STAMP(101);
       long long my_mol = -1;
       if (wv == 1 && lane < 32) my_mol = lane < na ? Hd.idx_m[a0 + lane] : -2;      // wave 1: molecule id of atom `lane`
       __syncthreads();                    // x_L is complete
       const int hw = wv;
+      if constexpr (SP) {
+        // split instances: everything the head reads is in LDS -- its weights as staged by team 1 during phase C1 of the last
+        // interaction, x_L as the split image the C2 epilogue wrote to sY.  8 k-steps of three f16 matrix instructions per row tile
+        // in place of 64 dependent fp32 ones behind a round trip for the weights and another for outnet.1.weight.
+        if (hw < HT) {
+          int ln = lane;
+          asm volatile("" : "+v"(ln));      // opaque, as above: nothing of the head is prepared ahead of the group loop
+          const int hi = ln >> 5, el = ln & 31;
+          f32x4 av[16];
+#pragma unroll
+          for (int s = 0; s < 8; ++s) {
+            av[2 * s] = __builtin_bit_cast(f32x4, sW2h[(hw * 8 + s) * 64 + ln]);
+            av[2 * s + 1] = __builtin_bit_cast(f32x4, sW2l[(hw * 8 + s) * 64 + ln]);
+          }
+          f32x16 acc;
+#pragma unroll
+          for (int r = 0; r < 16; ++r) acc[r] = sb1[32 * hw + ml_row(r, hi)];
+          acc = ml_dense_mma_sp_pre<8>(av, (const char*)sY + el * (ML_LD * 4) + 16 * hi, acc);
+          float part = 0.f;
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const f32x4 pv = {acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]};
+            if (el < na) ml_st<f32x4>(Hd.pre_h + (size_t)a0 * Hd.H + 32 * hw, (unsigned)((el * Hd.H + 8 * q + 4 * hi) * 4), pv);
+            const f32x4 wv2 = *(const f32x4*)(sb2 + 32 * hw + 8 * q + 4 * hi);
+            if (Hd.act == SPK_ACT_SILU)
+              part += pv.x * spk_sigmoid(pv.x) * wv2.x + pv.y * spk_sigmoid(pv.y) * wv2.y + pv.z * spk_sigmoid(pv.z) * wv2.z + pv.w * spk_sigmoid(pv.w) * wv2.w;
+            else
+              part += spk_ssp(pv.x) * wv2.x + spk_ssp(pv.y) * wv2.y + spk_ssp(pv.z) * wv2.z + spk_ssp(pv.w) * wv2.w;
+          }
+          part += __shfl_xor(part, 32, 64);
+          if (hi == 0) sH[hw * 32 + el] = part;          // (sH: the hidden tile of the last f2out is no longer needed)
+        }
+      } else
       if (hw < HT) {
         f32x4 av[16];                     // (requested after the barrier: register arrays that live across one get spilled)
 #pragma unroll
@@ -860,12 +949,14 @@ __global__ __launch_bounds__(512) void k_schnet_mol_fwd(MolFwdArgs a) {
         part += __shfl_xor(part, 32, 64);
         if (hi == 0) sH[hw * 32 + el] = part;          // (sH: the hidden tile of the last f2out is no longer needed)
       }
+      ML_STAMP(102);
       __syncthreads();
       // wave 1 holds the molecule id of atom (lane) in my_mol: segment heads add their run, one atomic per (group, molecule)
       if (wv == 1) {
         float y = 0.f;
         if (lane < 32) {
-          y = Hd.b2 ? Hd.b2[0] : 0.f;
+          if constexpr (SP) y = sW1[0];                 // outnet.1.bias as staged with the head's weights (0 when there is none)
+          else y = Hd.b2 ? Hd.b2[0] : 0.f;
           for (int w = 0; w < HT; ++w) y += sH[w * 32 + lane];
           if (lane >= na) y = 0.f;
         }
@@ -896,7 +987,7 @@ __global__ __launch_bounds__(512) void k_schnet_mol_fwd(MolFwdArgs a) {
 // ------------------------------------------------------------------------------------------ host side
 static long long* g_mol_dbg = nullptr;
 // tuning aid (scripts/mol_timing.py; include/spk_hip.h): device buffer of int64 that receives cycle stamps -- entries
-// [0, 128): phases of thread 0 of workgroup 0; [128 + 4 b, 128 + 4 b + 4): real-time and cycle stamps at the start / end of workgroup b
+// [0, 128): phases of thread 0 of workgroup 0 (64-87: per-wave stamps of forward Dense phases, 101 / 102: the energy head); [128 + 4 b, 128 + 4 b + 4): real-time and cycle stamps at the start / end of workgroup b
 // of the backward launch, so the buffer must hold 128 + 4 * (number of groups) entries.  NULL: off (production)
 extern "C" void spk_schnet_mol_set_debug_buffer(void* p) { g_mol_dbg = (long long*)p; }
 // derivative tasks per pair tile in phase E of the backward: 0 = automatic (the rule at the task queue of k_schnet_mol_bwd), 1, 2

@@ -31,7 +31,9 @@ for base in (0, 32):
         if k >= base and k < base + 32 and st[k]:
             print("  %-36s %8d  (+%d)" % (names[k], st[k] - st[base], st[k] - prev)); prev = st[k]
 # interaction 1 of the forward: when each wave was done with its half of a Dense phase (waves 0-3: the GEMM, 4-7: staging), cycles after the phase began
-for label, first, begin in (("fwd L1 C1", 64, 9), ("fwd L1 C2", 72, 10)):
+if st[101]:
+    print("  fwd head: last C2 %d, barrier + head GEMM + activation %d, barrier + per-molecule sums %d" % (st[101] - st[15], st[102] - st[101], st[31] - st[102]))
+for label, first, begin in (("fwd L1 C1", 64, 9), ("fwd L1 C2", 72, 10), ("fwd L2 C1", 80, 14)):
     if st[first]:
         print("  %-10s waves 0-7 done after" % label, [st[first + w] - st[begin] for w in range(8)])
 import numpy as np
