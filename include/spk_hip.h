@@ -709,6 +709,11 @@ void spk_painn_set_row_table(int32_t mode);
  * atomics; the full backward runs as a geometry launch and a transposed-sums launch.  F = 128, 16 <= n_rbf <= 31, split path on
  * (spk_set_split).  0 = automatic (lists of >= 2^19 pairs, with or without a skin), 1 = whenever the shape has it, -1 = never. */
 void spk_painn_set_rowtile(int32_t mode);
+/* Row-tile forward of the SchNet cfconv (round 6; csrc/spk_cfconv.hip): a wavefront per row of a list sorted by idx_i, the filter of every directed
+ * edge from the split-precision GEMMs of 32-edge chunks of the row, no atomics, y written once; on symmetric lists it saves the raw filters of the
+ * canonical pairs for the pair backward.  n_filters = 128, n_rbf <= 32, split path on (spk_set_split), no per-call compaction when filters are
+ * saved.  0 = automatic (lists of >= 2^19 edges; the initial value follows SPK_CF_ROWTILE=0|1), 1 = whenever the shape has it, -1 = never. */
+void spk_cfconv_set_rowtile(int32_t mode);
 
 /* representation/painn.py:92-117 -- the elementwise parts of PaiNNMixing around its three
  * Dense layers.  mix [N,3,2F] = mu_channel_mix(mu) = (V | W).

@@ -200,6 +200,7 @@ _PROTOS = {
     "spk_schnet_cfconv_fwd_f32": (ctypes.c_int, [P(GraphT), P(RadialT), c_f, c_f, c_f, c_f, c_f, c_f, c_i32, c_f, c_f]),
     "spk_schnet_cfconv_bwd_f32": (ctypes.c_int, [P(GraphT), P(RadialT), c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i32, c_f, c_f, c_f]),
     "spk_cfconv_set_debug_buffer": (None, [c_f]),
+    "spk_cfconv_set_rowtile": (None, [c_i32]),
     "spk_schnet_mol_set_debug_buffer": (None, [c_f]),
     "spk_schnet_mol_set_bwd_task_split": (None, [ctypes.c_int]),
     "spk_painn_mol_set_debug_buffer": (None, [c_f]),

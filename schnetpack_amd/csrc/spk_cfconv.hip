@@ -1439,13 +1439,19 @@ __global__ __launch_bounds__(NWAVES * 64) void k_cfconv_rowtile_fwd(CfArgs a) {
   }
 }
 
+// run-time switch of the row-tile forward (as spk_painn_set_rowtile): 1 = whenever the shape has it, -1 = never; 0 defers to SPK_CF_ROWTILE and,
+// if that variable is unset, to the automatic rule (lists of >= 2^19 edges)
+static int g_cf_rowtile_mode = 0;
+extern "C" void spk_cfconv_set_rowtile(int32_t mode) { g_cf_rowtile_mode = mode > 0 ? 1 : (mode < 0 ? -1 : 0); }
+
 static bool cfconv_rowtile_fwd_ok(const CfArgs& a) {
   static const int env = [] { const char* e = getenv("SPK_CF_ROWTILE"); return e ? (e[0] == '1' ? 1 : -1) : 0; }();
+  const int mode = g_cf_rowtile_mode ? g_cf_rowtile_mode : env;
   // (saving filters for the pair backward needs the plan's pair positions and a list without per-call compaction; a forward that saves nothing -- asymmetric
   //  lists, the by-neighbour pass of their backward -- only needs the rows)
-  if (env < 0 || !a.rowptr || a.N * (int64_t)128 >= (1LL << 30)) return false;
+  if (mode < 0 || !a.rowptr || a.N * (int64_t)128 >= (1LL << 30)) return false;
   if (a.gsave && (!a.edge_pair || !a.half || a.n_half_dev)) return false;
-  return env > 0 || a.E >= (1 << 19);
+  return mode > 0 || a.E >= (1 << 19);
 }
 
 template <int KPB>
