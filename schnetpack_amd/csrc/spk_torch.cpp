@@ -64,8 +64,12 @@ Tensor i64(const Tensor& t, const char* who) {
 }
 const float* fp(const Tensor& t) { return t.defined() ? t.data_ptr<float>() : nullptr; }
 float* fpm(Tensor& t) { return t.defined() ? t.data_ptr<float>() : nullptr; }
-const float* fpo(const c10::optional<Tensor>& t) { return (t.has_value() && t->defined()) ? t->data_ptr<float>() : nullptr; }
-Tensor opt_f32(const c10::optional<Tensor>& t, const char* who) { return (t.has_value() && t->defined()) ? f32(*t, who) : Tensor(); }
+using OptT = c10::optional<Tensor>;
+bool has(const OptT& t) { return t.has_value() && t->defined(); }
+const float* fpo(const c10::optional<Tensor>& t) { return has(t) ? t->data_ptr<float>() : nullptr; }
+Tensor opt_f32(const c10::optional<Tensor>& t, const char* who) { return has(t) ? f32(*t, who) : Tensor(); }
+// the tensor of an optional argument, undefined when it is absent
+Tensor opt_tensor(const c10::optional<Tensor>& t) { return has(t) ? *t : Tensor(); }
 
 uint64_t version_of(const Tensor& t) { return t.defined() ? (uint64_t)t._version() : 0; }
 
@@ -717,10 +721,10 @@ struct HeadCache { Tensor w1, w1t, b1, w2, b2; };
 Lru<HeadCache> g_heads(8);
 std::shared_ptr<HeadCache> get_head(const Tensor& w1_in, const c10::optional<Tensor>& b1_in, const Tensor& w2_in, const c10::optional<Tensor>& b2_in) {
   std::vector<uint64_t> key{(uint64_t)w1_in.data_ptr(), version_of(w1_in), (uint64_t)w2_in.data_ptr(), version_of(w2_in),
-                            (uint64_t)((b1_in.has_value() && b1_in->defined()) ? b1_in->data_ptr() : nullptr),
-                            (b1_in.has_value() && b1_in->defined()) ? version_of(*b1_in) : 0,
-                            (uint64_t)((b2_in.has_value() && b2_in->defined()) ? b2_in->data_ptr() : nullptr),
-                            (b2_in.has_value() && b2_in->defined()) ? version_of(*b2_in) : 0,
+                            (uint64_t)(has(b1_in) ? b1_in->data_ptr() : nullptr),
+                            has(b1_in) ? version_of(*b1_in) : 0,
+                            (uint64_t)(has(b2_in) ? b2_in->data_ptr() : nullptr),
+                            has(b2_in) ? version_of(*b2_in) : 0,
                             g_weight_generation.load(std::memory_order_acquire)};
   std::lock_guard<std::mutex> lock(g_mutex);
   if (auto hit = g_heads.get(key)) return hit;
@@ -743,21 +747,24 @@ std::shared_ptr<Plan> find_plan(const Tensor& idx_i, const Tensor& idx_j, int64_
   return g_plans.get(key);
 }
 
+// What one call of the standard potential works on, for either representation (exactly one of S / P is set): found or built once per call.
 struct PotentialCall {
   std::shared_ptr<Plan> plan;
-  std::shared_ptr<SchnetModel> M;
+  std::shared_ptr<SchnetModel> S;
+  std::shared_ptr<PainnModel> P;
   std::shared_ptr<HeadCache> H;
-  spk_schnet_t m;
+  spk_schnet_t m;              // SchNet: per-call copy of S->m (the cached block is never mutated); PaiNN reads P->m
   spk_head_t head;
   spk_graph_t g;
   spk_radial_t rb;
   Tensor p0, p1;
   bool fused;
 };
-PotentialCall potential_setup(const Tensor& R, const c10::optional<Tensor>& offsets, const Tensor& idx_i, const Tensor& idx_j, int64_t N, int64_t F,
-                              at::TensorList ws, at::TensorList head, int64_t n_filters, int64_t rbf_kind, const Tensor& p0_in,
-                              const c10::optional<Tensor>& p1_in, double cutoff, int64_t head_act) {
-  TORCH_CHECK(head.size() == 4, "schnet_potential: head = [outnet.0.weight, outnet.0.bias, outnet.1.weight, outnet.1.bias]");
+// n_filters belongs to SchNet, (shared_filters, eps) to PaiNN
+PotentialCall potential_setup(const char* who, bool painn, const Tensor& R, const OptT& offsets, const Tensor& idx_i, const Tensor& idx_j, int64_t N, int64_t F,
+                              at::TensorList ws, at::TensorList head, int64_t n_filters, bool shared_filters, double eps, int64_t rbf_kind,
+                              const Tensor& p0_in, const OptT& p1_in, double cutoff, int64_t head_act) {
+  TORCH_CHECK(head.size() == 4, who, ": head = [outnet.0.weight, outnet.0.bias, outnet.1.weight, outnet.1.bias]");
   PotentialCall c;
   c.plan = find_plan(idx_i, idx_j, N);
   if (!c.plan || c.plan->filter_pairs < 0) {       // first call on this list: the plan needs the geometry once
@@ -765,18 +772,23 @@ PotentialCall potential_setup(const Tensor& R, const c10::optional<Tensor>& offs
     c.plan = get_plan(idx_i, idx_j, N, r);
     decide_filter(*c.plan, r, cutoff);
   }
-  c.M = get_schnet(ws, F, n_filters);
+  std::memset(&c.m, 0, sizeof(c.m));
+  if (painn) {
+    c.P = get_painn(ws, F, shared_filters, eps);
+  } else {
+    c.S = get_schnet(ws, F, n_filters);
+    c.m = c.S->m;
+    c.m.reserved = 1;                              // SchNet model word: the forward keeps the raw filter outputs for the backward
+  }
   c.H = get_head(head[0], head[1], head[2], head[3]);
-  c.p0 = f32(p0_in, "schnet_potential");
-  c.p1 = opt_f32(p1_in, "schnet_potential");
-  c.m = c.M->m;
-  c.m.reserved = 1;
+  c.p0 = f32(p0_in, who);
+  c.p1 = opt_f32(p1_in, who);
   c.g = c.plan->graph();
   c.rb = radial_of(rbf_kind, c.p0, c.p1, cutoff);
   c.head.w1 = fp(c.H->w1); c.head.w1t = fp(c.H->w1t); c.head.b1 = fp(c.H->b1); c.head.w2 = fp(c.H->w2); c.head.b2 = fp(c.H->b2);
   c.head.n_hidden = (int32_t)c.H->w1.size(0); c.head.act = (int32_t)head_act;
   c.fused = c.H->w1.dim() == 2 && c.H->w1.size(1) == F && c.H->w2.numel() == c.H->w1.size(0) && c.H->b1.defined() &&
-            spk_schnet_potential_supported(&c.m, &c.head, &c.g, &c.rb) != 0;
+            (painn ? spk_painn_potential_supported(&c.P->m, &c.head, &c.g, &c.rb) : spk_schnet_potential_supported(&c.m, &c.head, &c.g, &c.rb)) != 0;
   return c;
 }
 
@@ -792,7 +804,7 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> schnet_potential_forward_raw(const Te
   const int64_t N = x0.size(0), F = x0.size(1);
   TORCH_CHECK(R.dim() == 2 && R.size(0) == N && R.size(1) == 3, "schnet_potential: positions ", R.sizes(), " do not match ", N, " atoms");
   c10::DeviceGuard guard(x0.device());
-  PotentialCall c = potential_setup(R, offsets_in, idx_i, idx_j, N, F, ws, head, n_filters, rbf_kind, p0, p1, cutoff, head_act);
+  PotentialCall c = potential_setup("schnet_potential", false, R, offsets_in, idx_i, idx_j, N, F, ws, head, n_filters, false, 0.0, rbf_kind, p0, p1, cutoff, head_act);
   if (c.fused) {
     Tensor x = at::empty({N, F}, x0.options()), E = at::empty({n_mol}, x0.options());
     Tensor pre_h = at::empty({N, (int64_t)c.head.n_hidden}, x0.options());
@@ -842,9 +854,9 @@ std::tuple<Tensor, Tensor> schnet_potential_backward_raw(const c10::optional<Ten
   Tensor idx_m = i64(idx_m_in, "schnet_potential backward");
   const int64_t N = x0_in.size(0), F = x0_in.size(1);
   c10::DeviceGuard guard(R.device());
-  Tensor gE = (gE_in.has_value() && gE_in->defined()) ? f32(*gE_in, "schnet_potential backward") : at::zeros({n_mol}, R.options());
-  Tensor gx = (gx_in.has_value() && gx_in->defined()) ? f32(*gx_in, "schnet_potential backward") : Tensor();
-  PotentialCall c = potential_setup(R, offsets_in, idx_i, idx_j, N, F, ws, head, n_filters, rbf_kind, p0, p1, cutoff, head_act);
+  Tensor gE = has(gE_in) ? f32(*gE_in, "schnet_potential backward") : at::zeros({n_mol}, R.options());
+  Tensor gx = has(gx_in) ? f32(*gx_in, "schnet_potential backward") : Tensor();
+  PotentialCall c = potential_setup("schnet_potential", false, R, offsets_in, idx_i, idx_j, N, F, ws, head, n_filters, false, 0.0, rbf_kind, p0, p1, cutoff, head_act);
   if (c.fused) {
     Tensor gR = at::empty({N, 3}, R.options());
     Tensor gx0 = want_gx0 ? at::empty({N, F}, R.options()) : Tensor();
@@ -870,100 +882,6 @@ int64_t potential_plan_op(const Tensor& idx_i, const Tensor& idx_j, int64_t n_at
   return molecules_inside_groups(*plan, i64(idx_m, "potential_plan"), n_mol) ? 1 : 0;
 }
 
-// Energies and forces of the standard potential for eval: no autograd node, (E, F = -dE/dR, scalar_representation).  x0 or
-// (embedding table, Z) -- with the table the lookup happens inside the forward launch.
-std::tuple<Tensor, Tensor, Tensor> schnet_potential_forces_raw(const c10::optional<Tensor>& x0_in, const c10::optional<Tensor>& emb_in, const Tensor& Z_in,
-                                                               const Tensor& R_in, const c10::optional<Tensor>& offsets_in, const Tensor& idx_i,
-                                                               const Tensor& idx_j, const Tensor& idx_m_in, int64_t n_mol, at::TensorList ws,
-                                                               at::TensorList head, int64_t n_filters, int64_t rbf_kind, const Tensor& p0,
-                                                               const c10::optional<Tensor>& p1, double cutoff, int64_t head_act) {
-  const bool has_x0 = x0_in.has_value() && x0_in->defined();
-  TORCH_CHECK(has_x0 || (emb_in.has_value() && emb_in->defined()), "schnet_potential_forces: neither features nor an embedding table");
-  Tensor R = f32(R_in.detach(), "schnet_potential_forces");
-  Tensor off = opt_f32(offsets_in, "schnet_potential_forces");
-  Tensor idx_m = i64(idx_m_in, "schnet_potential_forces"), Z = i64(Z_in, "schnet_potential_forces");
-  Tensor x0 = has_x0 ? f32(x0_in->detach(), "schnet_potential_forces") : Tensor();
-  Tensor emb = has_x0 ? Tensor() : f32(emb_in->detach(), "schnet_potential_forces");
-  const int64_t N = R.size(0), F = has_x0 ? x0.size(1) : emb.size(1);
-  c10::DeviceGuard guard(R.device());
-  c10::optional<Tensor> off_d = off.defined() ? c10::optional<Tensor>(off) : c10::optional<Tensor>();
-  PotentialCall c = potential_setup(R, off_d, idx_i, idx_j, N, F, ws, head, n_filters, rbf_kind, p0, p1, cutoff, head_act);
-  if (c.fused) {
-    const bool inside = molecules_inside_groups(*c.plan, idx_m, n_mol);
-    Tensor x = at::empty({N, F}, R.options()), E = at::empty({n_mol}, R.options()), Fo = at::empty({N, 3}, R.options());
-    Tensor pre_h = at::empty({N, (int64_t)c.head.n_hidden}, R.options());
-    Tensor saved = at::empty({std::max<int64_t>(1, spk_schnet_saved_floats_graph(&c.m, &c.g, &c.rb))}, R.options());
-    check(spk_schnet_potential_forces_f32(&c.m, &c.head, &c.g, &c.rb, fp(x0), fp(emb), Z.data_ptr<int64_t>(), emb.defined() ? (int32_t)emb.size(0) : 0, fp(R),
-                                          fp(off), idx_m.data_ptr<int64_t>(), n_mol, inside ? 1 : 0, fpm(x), fpm(E), fpm(Fo), fpm(pre_h), fpm(saved),
-                                          stream_of(R)));
-    return {E, Fo, x};
-  }
-  if (!has_x0) x0 = emb.index_select(0, Z);
-  auto fw = schnet_potential_forward_raw(x0, R, off_d, idx_i, idx_j, idx_m, n_mol, ws, head, n_filters, rbf_kind, p0, p1, cutoff, head_act);
-  Tensor ones = at::ones({n_mol}, R.options());
-  auto bw = schnet_potential_backward_raw(ones, c10::nullopt, x0, R, off_d, idx_i, idx_j, idx_m, n_mol, std::get<2>(fw), std::get<3>(fw), ws, head, n_filters,
-                                          rbf_kind, p0, p1, cutoff, head_act, false);
-  return {std::get<0>(fw), at::neg(std::get<0>(bw)), std::get<1>(fw)};
-}
-
-// The same for PaiNN: (E, F = -dE/dR, scalar_representation, vector_representation), eval only, no autograd node.  Batches of small
-// molecules: TWO launches (spk_painn_potential_forces_f32); every other list runs the same stages through their own kernels.
-std::tuple<Tensor, Tensor, Tensor, Tensor> painn_potential_forces_raw(const c10::optional<Tensor>& q0_in, const c10::optional<Tensor>& emb_in, const Tensor& Z_in,
-                                                                      const Tensor& R_in, const c10::optional<Tensor>& offsets_in, const Tensor& idx_i,
-                                                                      const Tensor& idx_j, const Tensor& idx_m_in, int64_t n_mol, at::TensorList ws,
-                                                                      at::TensorList head, bool shared_filters, double eps, int64_t rbf_kind,
-                                                                      const Tensor& p0_in, const c10::optional<Tensor>& p1_in, double cutoff, int64_t head_act) {
-  const char* who = "painn_potential_forces";
-  const bool has_q0 = q0_in.has_value() && q0_in->defined();
-  TORCH_CHECK(has_q0 || (emb_in.has_value() && emb_in->defined()), who, ": neither features nor an embedding table");
-  TORCH_CHECK(head.size() == 4, who, ": head = [outnet.0.weight, outnet.0.bias, outnet.1.weight, outnet.1.bias]");
-  Tensor R = f32(R_in.detach(), who);
-  Tensor off = opt_f32(offsets_in, who);
-  Tensor idx_m = i64(idx_m_in, who), Z = i64(Z_in, who);
-  Tensor q0 = has_q0 ? f32(q0_in->detach(), who) : Tensor();
-  Tensor emb = has_q0 ? Tensor() : f32(emb_in->detach(), who);
-  const int64_t N = R.size(0), F = has_q0 ? q0.size(1) : emb.size(1);
-  c10::DeviceGuard guard(R.device());
-  c10::optional<Tensor> off_d = off.defined() ? c10::optional<Tensor>(off) : c10::optional<Tensor>();
-  auto plan = find_plan(idx_i, idx_j, N);
-  if (!plan || plan->filter_pairs < 0) {       // first call on this list: the plan needs the geometry once
-    Tensor r = pairwise_raw(R, idx_i, idx_j, off_d);
-    plan = get_plan(idx_i, idx_j, N, r);
-    decide_filter(*plan, r, cutoff);
-  }
-  auto M = get_painn(ws, F, shared_filters, eps);
-  auto H = get_head(head[0], head[1], head[2], head[3]);
-  Tensor p0 = f32(p0_in, who), p1 = opt_f32(p1_in, who);
-  spk_graph_t g = plan->graph();
-  spk_radial_t rb = radial_of(rbf_kind, p0, p1, cutoff);
-  spk_head_t hd;
-  hd.w1 = fp(H->w1); hd.w1t = fp(H->w1t); hd.b1 = fp(H->b1); hd.w2 = fp(H->w2); hd.b2 = fp(H->b2);
-  hd.n_hidden = (int32_t)H->w1.size(0); hd.act = (int32_t)head_act;
-  const bool fused = H->w1.dim() == 2 && H->w1.size(1) == F && H->w2.numel() == H->w1.size(0) && H->b1.defined() &&
-                     spk_painn_potential_supported(&M->m, &hd, &g, &rb) != 0;
-  if (fused) {
-    const bool inside = molecules_inside_groups(*plan, idx_m, n_mol);
-    Tensor q = at::empty({N, F}, R.options()), mu = at::empty({N, 3, F}, R.options());
-    Tensor E = at::empty({n_mol}, R.options()), Fo = at::empty({N, 3}, R.options());
-    Tensor pre_h = at::empty({N, (int64_t)hd.n_hidden}, R.options());
-    Tensor saved = at::empty({std::max<int64_t>(1, spk_painn_saved_floats(&M->m, N))}, R.options());
-    Tensor scratch = at::empty({std::max<int64_t>(1, spk_painn_scratch_floats(&M->m, N))}, R.options());
-    check(spk_painn_potential_forces_f32(&M->m, &hd, &g, &rb, fp(q0), fp(emb), Z.data_ptr<int64_t>(), emb.defined() ? (int32_t)emb.size(0) : 0, fp(R), fp(off),
-                                         idx_m.data_ptr<int64_t>(), n_mol, inside ? 1 : 0, fpm(q), fpm(mu), fpm(E), fpm(Fo), fpm(pre_h), fpm(saved), fpm(scratch),
-                                         stream_of(R)));
-    return {E, Fo, q, mu};
-  }
-  if (!has_q0) q0 = emb.index_select(0, Z);
-  Tensor r = pairwise_raw(R, idx_i, idx_j, off_d);
-  std::shared_ptr<Plan> pl;
-  auto fw = painn_forward_raw(q0, r, idx_i, idx_j, ws, shared_filters, eps, rbf_kind, p0, p1_in, cutoff, &pl);
-  auto hdf = atomwise_forward_raw(std::get<0>(fw), head[0], head[1], head[2], head[3], idx_m, n_mol, head_act);
-  Tensor gq = atomwise_backward_raw(at::ones({n_mol}, R.options()), Tensor(), std::get<2>(hdf), head[0], head[2], idx_m, n_mol, head_act);
-  auto bw = painn_backward_raw(gq, Tensor(), r, std::get<2>(fw), std::get<3>(fw), *pl, ws, F, shared_filters, eps, rbf_kind, p0, p1_in, cutoff, false);
-  Tensor gR = pairwise_bwd_raw(std::get<0>(bw), idx_i, idx_j, N);
-  return {std::get<0>(hdf), at::neg(gR), std::get<0>(fw), std::get<1>(fw)};
-}
-
 // Virial W [n_mol, 3, 3] = sum over each molecule's edges of dE/dr_e r_e^T from the per-edge gradient (spk_edge_virial_f32: row sums over the
 // plan's CSR, or a by-centre order built on the device for unsorted lists; no atomics, no host synchronisation)
 Tensor edge_virial_raw(const Tensor& gr, const Tensor& R, const Tensor& off, const Plan& plan, const Tensor& idx_m, int64_t n_mol) {
@@ -975,6 +893,117 @@ Tensor edge_virial_raw(const Tensor& gr, const Tensor& R, const Tensor& off, con
   check(spk_edge_virial_f32(gr.numel() ? fp(gr) : nullptr, fp(R), fp(off), &g, idx_m.data_ptr<int64_t>(), n_mol, fpm(W), nullptr, ws.data_ptr(),
                             stream_of(R)));
   return W;
+}
+
+// The eval-mode force call of the standard potential, for either representation, with or without the virial: no autograd node (the inputs are
+// detached), -> (E, F = -dE/dR, W [n_mol, 3, 3] = dE/dS of the strain or undefined, scalar_representation, vector_representation or undefined).
+// Features (x0 / q0) or (embedding table, Z).  Batches of small molecules run as the molecule-resident launches (spk_*_potential_*); every other
+// list runs the same three stages through their own kernels, whose dE/dr lands on the atoms and, when asked, feeds the virial.
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> potential_eval(const char* who, bool painn, bool want_virial, const OptT& x0_in, const OptT& emb_in,
+                                                                  const Tensor& Z_in, const Tensor& R_in, const OptT& offsets_in, const Tensor& idx_i,
+                                                                  const Tensor& idx_j, const Tensor& idx_m_in, int64_t n_mol, at::TensorList ws,
+                                                                  at::TensorList head, int64_t n_filters, bool shared_filters, double eps, int64_t rbf_kind,
+                                                                  const Tensor& p0, const OptT& p1, double cutoff, int64_t head_act) {
+  const bool has_x0 = has(x0_in);
+  TORCH_CHECK(has_x0 || has(emb_in), who, ": neither features nor an embedding table");
+  Tensor R = f32(R_in.detach(), who);
+  Tensor off = opt_f32(offsets_in, who);
+  Tensor idx_m = i64(idx_m_in, who), Z = i64(Z_in, who);
+  Tensor x0 = has_x0 ? f32(x0_in->detach(), who) : Tensor();
+  Tensor emb = has_x0 ? Tensor() : f32(emb_in->detach(), who);
+  const int64_t N = R.size(0), F = has_x0 ? x0.size(1) : emb.size(1);
+  TORCH_CHECK(R.dim() == 2 && R.size(1) == 3 && (!has_x0 || x0.size(0) == N), who, ": positions ", R.sizes(), " do not match the features");
+  c10::DeviceGuard guard(R.device());
+  OptT off_d = off.defined() ? OptT(off) : OptT();
+  PotentialCall c = potential_setup(who, painn, R, off_d, idx_i, idx_j, N, F, ws, head, n_filters, shared_filters, eps, rbf_kind, p0, p1, cutoff, head_act);
+  Tensor W;
+  if (c.fused) {
+    const int32_t inside = molecules_inside_groups(*c.plan, idx_m, n_mol) ? 1 : 0;     // (this branch only: the energy head stores its sums)
+    const int32_t n_emb = emb.defined() ? (int32_t)emb.size(0) : 0;                    // the table route: the rows are looked up inside the launch
+    const int64_t *zp = Z.data_ptr<int64_t>(), *mp = idx_m.data_ptr<int64_t>();
+    Tensor x = at::empty({N, F}, R.options()), mu = painn ? at::empty({N, 3, F}, R.options()) : Tensor();
+    Tensor E = at::empty({n_mol}, R.options()), Fo = at::empty({N, 3}, R.options());
+    Tensor gr = want_virial ? at::empty({c.plan->n_edges, 3}, R.options()) : Tensor();
+    Tensor pre_h = at::empty({N, (int64_t)c.head.n_hidden}, R.options());
+    if (painn) {          // (saved per atom, plus scratch; SchNet below: saved per atom and pair of the plan, no scratch)
+      Tensor saved = at::empty({std::max<int64_t>(1, spk_painn_saved_floats(&c.P->m, N))}, R.options());
+      Tensor scratch = at::empty({std::max<int64_t>(1, spk_painn_scratch_floats(&c.P->m, N))}, R.options());
+      if (!want_virial) {
+        check(spk_painn_potential_forces_f32(&c.P->m, &c.head, &c.g, &c.rb, fp(x0), fp(emb), zp, n_emb, fp(R), fp(off), mp, n_mol, inside, fpm(x), fpm(mu),
+                                             fpm(E), fpm(Fo), fpm(pre_h), fpm(saved), fpm(scratch), stream_of(R)));
+      } else {
+        // PaiNN's molecule-resident backward writes either the forces or dE/dr of every edge: the forces then come from the deterministic row
+        // sum of dE/dr (equal to the stress-free call's to float round-off, not bit for bit)
+        check(spk_painn_potential_gr_f32(&c.P->m, &c.head, &c.g, &c.rb, fp(x0), fp(emb), zp, n_emb, fp(R), fp(off), mp, n_mol, inside, fpm(x), fpm(mu),
+                                         fpm(E), fpm(gr), fpm(pre_h), fpm(saved), fpm(scratch), stream_of(R)));
+        check(spk_pairwise_bwd_graph_f32(fp(gr), &c.g, fpm(Fo), stream_of(R)));
+        Fo = at::neg(Fo);
+      }
+    } else {
+      // SchNet's backward also writes dE/dr when asked: E and F of the two forms are the same launches, bit for bit
+      Tensor saved = at::empty({std::max<int64_t>(1, spk_schnet_saved_floats_graph(&c.m, &c.g, &c.rb))}, R.options());
+      if (!want_virial)
+        check(spk_schnet_potential_forces_f32(&c.m, &c.head, &c.g, &c.rb, fp(x0), fp(emb), zp, n_emb, fp(R), fp(off), mp, n_mol, inside, fpm(x), fpm(E),
+                                              fpm(Fo), fpm(pre_h), fpm(saved), stream_of(R)));
+      else
+        check(spk_schnet_potential_forces_gr_f32(&c.m, &c.head, &c.g, &c.rb, fp(x0), fp(emb), zp, n_emb, fp(R), fp(off), mp, n_mol, inside, fpm(x), fpm(E),
+                                                 fpm(Fo), fpm(gr), fpm(pre_h), fpm(saved), stream_of(R)));
+    }
+    if (want_virial) W = edge_virial_raw(gr, R, off, *c.plan, idx_m, n_mol);
+    return {E, Fo, W, x, mu};
+  }
+  // the three stages: representation -> head -> their backward with dL/dE = 1 -> dE/dr ONCE -> the atoms and, when asked, the virial
+  if (!has_x0) x0 = emb.index_select(0, Z);          // (the table route here: an ordinary lookup)
+  Tensor r = pairwise_raw(R, idx_i, idx_j, off_d);
+  std::shared_ptr<Plan> plan = c.plan;
+  Tensor x, mu, saved, scratch;
+  if (painn) {
+    // (the plan the forward returns is the one the backward and the virial use; no gradient w.r.t. q0)
+    std::tie(x, mu, saved, scratch) = painn_forward_raw(x0, r, idx_i, idx_j, ws, shared_filters, eps, rbf_kind, p0, p1, cutoff, &plan);
+  } else {
+    // (raw filter outputs kept for the backward, which runs on the set-up's plan with a workspace of its own; no gradient w.r.t. x0)
+    std::tie(x, saved, std::ignore) = schnet_forward_raw(x0, r, idx_i, idx_j, ws, n_filters, rbf_kind, p0, p1, cutoff, true);
+    scratch = at::empty({std::max<int64_t>(1, spk_schnet_scratch_floats(&c.m, N))}, R.options());
+  }
+  auto hd = atomwise_forward_raw(x, head[0], head[1], head[2], head[3], idx_m, n_mol, head_act);
+  Tensor gx = atomwise_backward_raw(at::ones({n_mol}, R.options()), Tensor(), std::get<2>(hd), head[0], head[2], idx_m, n_mol, head_act);
+  Tensor gr = painn ? std::get<0>(painn_backward_raw(gx, Tensor(), r, saved, scratch, *plan, ws, F, shared_filters, eps, rbf_kind, p0, p1, cutoff, false))
+                    : std::get<0>(schnet_backward_raw(gx, r, saved, scratch, *plan, ws, F, n_filters, rbf_kind, p0, p1, cutoff, true, false));
+  Tensor gR = pairwise_bwd_raw(gr, idx_i, idx_j, N);
+  if (want_virial) W = edge_virial_raw(gr, R, off, *plan, idx_m, n_mol);
+  return {std::get<0>(hd), at::neg(gR), W, x, mu};
+}
+
+// The four operators over it pick the tuple their schema promises.
+std::tuple<Tensor, Tensor, Tensor> schnet_potential_forces_raw(const OptT& x0, const OptT& emb, const Tensor& Z, const Tensor& R, const OptT& offsets, const Tensor& idx_i,
+                                                               const Tensor& idx_j, const Tensor& idx_m, int64_t n_mol, at::TensorList ws, at::TensorList head,
+                                                               int64_t n_filters, int64_t rbf_kind, const Tensor& p0, const OptT& p1, double cutoff, int64_t head_act) {
+  auto o = potential_eval("schnet_potential_forces", false, false, x0, emb, Z, R, offsets, idx_i, idx_j, idx_m, n_mol, ws, head, n_filters, false, 0.0, rbf_kind,
+                          p0, p1, cutoff, head_act);
+  return {std::get<0>(o), std::get<1>(o), std::get<3>(o)};
+}
+std::tuple<Tensor, Tensor, Tensor, Tensor> painn_potential_forces_raw(const OptT& q0, const OptT& emb, const Tensor& Z, const Tensor& R, const OptT& offsets,
+                                                                      const Tensor& idx_i, const Tensor& idx_j, const Tensor& idx_m, int64_t n_mol, at::TensorList ws,
+                                                                      at::TensorList head, bool shared_filters, double eps, int64_t rbf_kind, const Tensor& p0,
+                                                                      const OptT& p1, double cutoff, int64_t head_act) {
+  auto o = potential_eval("painn_potential_forces", true, false, q0, emb, Z, R, offsets, idx_i, idx_j, idx_m, n_mol, ws, head, 0, shared_filters, eps, rbf_kind,
+                          p0, p1, cutoff, head_act);
+  return {std::get<0>(o), std::get<1>(o), std::get<3>(o), std::get<4>(o)};
+}
+std::tuple<Tensor, Tensor, Tensor, Tensor> schnet_potential_stress_raw(const OptT& x0, const OptT& emb, const Tensor& Z, const Tensor& R, const OptT& offsets,
+                                                                       const Tensor& idx_i, const Tensor& idx_j, const Tensor& idx_m, int64_t n_mol, at::TensorList ws,
+                                                                       at::TensorList head, int64_t n_filters, int64_t rbf_kind, const Tensor& p0, const OptT& p1,
+                                                                       double cutoff, int64_t head_act) {
+  auto o = potential_eval("schnet_potential_stress", false, true, x0, emb, Z, R, offsets, idx_i, idx_j, idx_m, n_mol, ws, head, n_filters, false, 0.0, rbf_kind,
+                          p0, p1, cutoff, head_act);
+  return {std::get<0>(o), std::get<1>(o), std::get<2>(o), std::get<3>(o)};
+}
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> painn_potential_stress_raw(const OptT& q0, const OptT& emb, const Tensor& Z, const Tensor& R, const OptT& offsets,
+                                                                              const Tensor& idx_i, const Tensor& idx_j, const Tensor& idx_m, int64_t n_mol,
+                                                                              at::TensorList ws, at::TensorList head, bool shared_filters, double eps,
+                                                                              int64_t rbf_kind, const Tensor& p0, const OptT& p1, double cutoff, int64_t head_act) {
+  return potential_eval("painn_potential_stress", true, true, q0, emb, Z, R, offsets, idx_i, idx_j, idx_m, n_mol, ws, head, 0, shared_filters, eps, rbf_kind, p0,
+                        p1, cutoff, head_act);
 }
 
 // ZBL nuclear repulsion (atomistic/nuclear_repulsion.py:70-108; csrc/spk_zbl.hip).  params: the 12 effective parameters as a float32 DEVICE
@@ -1025,7 +1054,7 @@ Tensor zbl_forces_raw(const Tensor& R_in, const c10::optional<Tensor>& offsets_i
   const char* who = "zbl_forces";
   Tensor R = f32(R_in.detach(), who), off = opt_f32(offsets_in, who), Z = i64(Z_in, who), idx_m = i64(idx_m_in, who), prm = zbl_params(params, who);
   const int64_t N = R.size(0);
-  Tensor W = (W_in.has_value() && W_in->defined()) ? *W_in : Tensor();
+  Tensor W = opt_tensor(W_in);
   require_device(F, who);
   TORCH_CHECK(F.scalar_type() == at::kFloat && F.is_contiguous() && F.dim() == 2 && F.size(0) == N && F.size(1) == 3, who, ": F must be a contiguous float32 [N, 3] tensor");
   if (W.defined()) {
@@ -1100,8 +1129,8 @@ std::tuple<Tensor, Tensor> dipole_moment_raw(const Tensor& q_in, const c10::opti
                                              const c10::optional<Tensor>& total_in, bool correct) {
   const char* who = "dipole_moment";
   Tensor q = f32(q_in.detach(), who), R = f32(R_in.detach(), who), idx_m = i64(idx_m_in, who);
-  Tensor d = (d_in.has_value() && d_in->defined()) ? f32(d_in->detach(), who) : Tensor();
-  Tensor tot = (total_in.has_value() && total_in->defined()) ? f32(total_in->detach(), who) : Tensor();
+  Tensor d = has(d_in) ? f32(d_in->detach(), who) : Tensor();
+  Tensor tot = has(total_in) ? f32(total_in->detach(), who) : Tensor();
   const int64_t N = R.size(0);
   TORCH_CHECK(R.dim() == 2 && R.size(1) == 3 && q.numel() == N && idx_m.dim() == 1 && idx_m.size(0) == N && n_mol >= 0, who, ": q [N(, 1)], R [N, 3], idx_m [N]");
   TORCH_CHECK(!d.defined() || d.numel() == 3 * N, who, ": d [N, 3(, 1)]");
@@ -1127,113 +1156,6 @@ Tensor polarizability_raw(const Tensor& a0_in, const Tensor& d_in, const Tensor&
   return al;
 }
 
-// Energies, forces AND the virial W = dE/dS of the strain (Strain -> ... -> Forces(calc_stress=True), atomistic/response.py:434-464) for eval:
-// (E, F = -dE/dR, W [n_mol, 3, 3], scalar_representation), no autograd node.  E and F are those of schnet_potential_forces bit for bit: the same
-// two launches (the backward also writes dE/dr of every edge) or the same three stages (whose dE/dr is kept), plus the virial launches.
-std::tuple<Tensor, Tensor, Tensor, Tensor> schnet_potential_stress_raw(const c10::optional<Tensor>& x0_in, const c10::optional<Tensor>& emb_in, const Tensor& Z_in,
-                                                                       const Tensor& R_in, const c10::optional<Tensor>& offsets_in, const Tensor& idx_i,
-                                                                       const Tensor& idx_j, const Tensor& idx_m_in, int64_t n_mol, at::TensorList ws,
-                                                                       at::TensorList head, int64_t n_filters, int64_t rbf_kind, const Tensor& p0,
-                                                                       const c10::optional<Tensor>& p1, double cutoff, int64_t head_act) {
-  const char* who = "schnet_potential_stress";
-  const bool has_x0 = x0_in.has_value() && x0_in->defined();
-  TORCH_CHECK(has_x0 || (emb_in.has_value() && emb_in->defined()), who, ": neither features nor an embedding table");
-  Tensor R = f32(R_in.detach(), who);
-  Tensor off = opt_f32(offsets_in, who);
-  Tensor idx_m = i64(idx_m_in, who), Z = i64(Z_in, who);
-  Tensor x0 = has_x0 ? f32(x0_in->detach(), who) : Tensor();
-  Tensor emb = has_x0 ? Tensor() : f32(emb_in->detach(), who);
-  const int64_t N = R.size(0), F = has_x0 ? x0.size(1) : emb.size(1);
-  c10::DeviceGuard guard(R.device());
-  c10::optional<Tensor> off_d = off.defined() ? c10::optional<Tensor>(off) : c10::optional<Tensor>();
-  PotentialCall c = potential_setup(R, off_d, idx_i, idx_j, N, F, ws, head, n_filters, rbf_kind, p0, p1, cutoff, head_act);
-  if (c.fused) {
-    const bool inside = molecules_inside_groups(*c.plan, idx_m, n_mol);
-    Tensor x = at::empty({N, F}, R.options()), E = at::empty({n_mol}, R.options()), Fo = at::empty({N, 3}, R.options());
-    Tensor gr = at::empty({c.plan->n_edges, 3}, R.options());
-    Tensor pre_h = at::empty({N, (int64_t)c.head.n_hidden}, R.options());
-    Tensor saved = at::empty({std::max<int64_t>(1, spk_schnet_saved_floats_graph(&c.m, &c.g, &c.rb))}, R.options());
-    check(spk_schnet_potential_forces_gr_f32(&c.m, &c.head, &c.g, &c.rb, fp(x0), fp(emb), Z.data_ptr<int64_t>(), emb.defined() ? (int32_t)emb.size(0) : 0,
-                                             fp(R), fp(off), idx_m.data_ptr<int64_t>(), n_mol, inside ? 1 : 0, fpm(x), fpm(E), fpm(Fo), fpm(gr), fpm(pre_h),
-                                             fpm(saved), stream_of(R)));
-    return {E, Fo, edge_virial_raw(gr, R, off, *c.plan, idx_m, n_mol), x};
-  }
-  if (!has_x0) x0 = emb.index_select(0, Z);
-  auto fw = schnet_potential_forward_raw(x0, R, off_d, idx_i, idx_j, idx_m, n_mol, ws, head, n_filters, rbf_kind, p0, p1, cutoff, head_act);
-  // the three-stage branch of schnet_potential_backward_raw with dL/dE = 1, keeping the per-edge gradient
-  Tensor r = pairwise_raw(R, idx_i, idx_j, off_d);
-  Tensor gxh = atomwise_backward_raw(at::ones({n_mol}, R.options()), Tensor(), std::get<3>(fw), head[0], head[2], idx_m, n_mol, head_act);
-  Tensor scratch = at::empty({std::max<int64_t>(1, spk_schnet_scratch_floats(&c.m, N))}, R.options());
-  auto res = schnet_backward_raw(gxh, r, std::get<2>(fw), scratch, *c.plan, ws, F, n_filters, rbf_kind, p0, p1, cutoff, true, false);
-  Tensor gr = std::get<0>(res);
-  Tensor gR = pairwise_bwd_raw(gr, idx_i, idx_j, N);
-  return {std::get<0>(fw), at::neg(gR), edge_virial_raw(gr, R, off, *c.plan, idx_m, n_mol), std::get<1>(fw)};
-}
-
-// The same for PaiNN: (E, F, W [n_mol, 3, 3], scalar_representation, vector_representation).  Batches of small molecules: the two launches
-// with the backward writing dE/dr of every edge (it writes that or the forces), the forces then from the deterministic row sum of
-// spk_pairwise_bwd_graph_f32 (equal to the stress-free call's to float round-off, not bit for bit); other lists: the three stages of
-// painn_potential_forces (bit for bit) with their dE/dr kept.
-std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> painn_potential_stress_raw(const c10::optional<Tensor>& q0_in, const c10::optional<Tensor>& emb_in,
-                                                                              const Tensor& Z_in, const Tensor& R_in, const c10::optional<Tensor>& offsets_in,
-                                                                              const Tensor& idx_i, const Tensor& idx_j, const Tensor& idx_m_in, int64_t n_mol,
-                                                                              at::TensorList ws, at::TensorList head, bool shared_filters, double eps,
-                                                                              int64_t rbf_kind, const Tensor& p0_in, const c10::optional<Tensor>& p1_in,
-                                                                              double cutoff, int64_t head_act) {
-  const char* who = "painn_potential_stress";
-  const bool has_q0 = q0_in.has_value() && q0_in->defined();
-  TORCH_CHECK(has_q0 || (emb_in.has_value() && emb_in->defined()), who, ": neither features nor an embedding table");
-  TORCH_CHECK(head.size() == 4, who, ": head = [outnet.0.weight, outnet.0.bias, outnet.1.weight, outnet.1.bias]");
-  Tensor R = f32(R_in.detach(), who);
-  Tensor off = opt_f32(offsets_in, who);
-  Tensor idx_m = i64(idx_m_in, who), Z = i64(Z_in, who);
-  Tensor q0 = has_q0 ? f32(q0_in->detach(), who) : Tensor();
-  Tensor emb = has_q0 ? Tensor() : f32(emb_in->detach(), who);
-  const int64_t N = R.size(0), F = has_q0 ? q0.size(1) : emb.size(1);
-  c10::DeviceGuard guard(R.device());
-  c10::optional<Tensor> off_d = off.defined() ? c10::optional<Tensor>(off) : c10::optional<Tensor>();
-  auto plan = find_plan(idx_i, idx_j, N);
-  if (!plan || plan->filter_pairs < 0) {
-    Tensor r = pairwise_raw(R, idx_i, idx_j, off_d);
-    plan = get_plan(idx_i, idx_j, N, r);
-    decide_filter(*plan, r, cutoff);
-  }
-  auto M = get_painn(ws, F, shared_filters, eps);
-  auto H = get_head(head[0], head[1], head[2], head[3]);
-  Tensor p0 = f32(p0_in, who), p1 = opt_f32(p1_in, who);
-  spk_graph_t g = plan->graph();
-  spk_radial_t rb = radial_of(rbf_kind, p0, p1, cutoff);
-  spk_head_t hd;
-  hd.w1 = fp(H->w1); hd.w1t = fp(H->w1t); hd.b1 = fp(H->b1); hd.w2 = fp(H->w2); hd.b2 = fp(H->b2);
-  hd.n_hidden = (int32_t)H->w1.size(0); hd.act = (int32_t)head_act;
-  const bool fused = H->w1.dim() == 2 && H->w1.size(1) == F && H->w2.numel() == H->w1.size(0) && H->b1.defined() &&
-                     spk_painn_potential_supported(&M->m, &hd, &g, &rb) != 0;
-  if (fused) {
-    const bool inside = molecules_inside_groups(*plan, idx_m, n_mol);
-    Tensor q = at::empty({N, F}, R.options()), mu = at::empty({N, 3, F}, R.options());
-    Tensor E = at::empty({n_mol}, R.options()), gR = at::empty({N, 3}, R.options());
-    Tensor gr = at::empty({plan->n_edges, 3}, R.options());
-    Tensor pre_h = at::empty({N, (int64_t)hd.n_hidden}, R.options());
-    Tensor saved = at::empty({std::max<int64_t>(1, spk_painn_saved_floats(&M->m, N))}, R.options());
-    Tensor scratch = at::empty({std::max<int64_t>(1, spk_painn_scratch_floats(&M->m, N))}, R.options());
-    check(spk_painn_potential_gr_f32(&M->m, &hd, &g, &rb, fp(q0), fp(emb), Z.data_ptr<int64_t>(), emb.defined() ? (int32_t)emb.size(0) : 0, fp(R), fp(off),
-                                     idx_m.data_ptr<int64_t>(), n_mol, inside ? 1 : 0, fpm(q), fpm(mu), fpm(E), fpm(gr), fpm(pre_h), fpm(saved), fpm(scratch),
-                                     stream_of(R)));
-    check(spk_pairwise_bwd_graph_f32(fp(gr), &g, fpm(gR), stream_of(R)));
-    return {E, at::neg(gR), edge_virial_raw(gr, R, off, *plan, idx_m, n_mol), q, mu};
-  }
-  if (!has_q0) q0 = emb.index_select(0, Z);
-  Tensor r = pairwise_raw(R, idx_i, idx_j, off_d);
-  std::shared_ptr<Plan> pl;
-  auto fw = painn_forward_raw(q0, r, idx_i, idx_j, ws, shared_filters, eps, rbf_kind, p0, p1_in, cutoff, &pl);
-  auto hdf = atomwise_forward_raw(std::get<0>(fw), head[0], head[1], head[2], head[3], idx_m, n_mol, head_act);
-  Tensor gq = atomwise_backward_raw(at::ones({n_mol}, R.options()), Tensor(), std::get<2>(hdf), head[0], head[2], idx_m, n_mol, head_act);
-  auto bw = painn_backward_raw(gq, Tensor(), r, std::get<2>(fw), std::get<3>(fw), *pl, ws, F, shared_filters, eps, rbf_kind, p0, p1_in, cutoff, false);
-  Tensor gr = std::get<0>(bw);
-  Tensor gR = pairwise_bwd_raw(gr, idx_i, idx_j, N);
-  return {std::get<0>(hdf), at::neg(gR), edge_virial_raw(gr, R, off, *pl, idx_m, n_mol), std::get<0>(fw), std::get<1>(fw)};
-}
-
 // ------------------------------------------------------------------------------------------------ dispatcher handles
 template <class Sig>
 c10::TypedOperatorHandle<Sig> op_handle(const char* name) {
@@ -1256,7 +1178,6 @@ Tensor call_pairwise_backward(const Tensor& gr, const Tensor& ii, const Tensor& 
   return op.call(gr, ii, jj, n);
 }
 
-using OptT = c10::optional<Tensor>;
 std::tuple<Tensor, Tensor> call_dense_forward(const Tensor& x, const Tensor& w, const OptT& b, int64_t act) {
   static auto op = op_handle<std::tuple<Tensor, Tensor>(const Tensor&, const Tensor&, const OptT&, int64_t)>("spk_hip::dense_forward");
   return op.call(x, w, b, act);
@@ -1371,7 +1292,7 @@ struct PairwiseFn : public torch::autograd::Function<PairwiseFn> {
     ctx->saved_data["ii"] = ii;
     ctx->saved_data["jj"] = jj;
     ctx->saved_data["n"] = R.size(0);
-    ctx->saved_data["has_off"] = off.has_value() && off->defined();
+    ctx->saved_data["has_off"] = has(off);
     return call_pairwise(R, ii, jj, off);
   }
   static variable_list backward(AutogradContext* ctx, variable_list g) {
@@ -1405,7 +1326,7 @@ struct DenseFn : public torch::autograd::Function<DenseFn> {
     at::AutoDispatchBelowADInplaceOrView guard;
     auto yp = call_dense_forward(x, w, b, act);
     ctx->saved_data["act"] = act;
-    ctx->saved_data["has_bias"] = b.has_value() && b->defined();
+    ctx->saved_data["has_bias"] = has(b);
     ctx->save_for_backward({x, w, std::get<1>(yp)});
     return {std::get<0>(yp), std::get<1>(yp)};
   }
@@ -1449,7 +1370,7 @@ struct RadialCutoffFn : public torch::autograd::Function<RadialCutoffFn> {
                                double cutoff, bool want_phi, bool want_cut) {
     at::AutoDispatchBelowADInplaceOrView guard;
     auto out = call_radial_cutoff(d, kind, p0, p1, cutoff, want_phi, want_cut);
-    ctx->save_for_backward({d, p0, (p1.has_value() && p1->defined()) ? *p1 : Tensor()});
+    ctx->save_for_backward({d, p0, opt_tensor(p1)});
     ctx->saved_data["kind"] = kind;
     ctx->saved_data["cutoff"] = cutoff;
     ctx->saved_data["want"] = std::vector<int64_t>{want_phi, want_cut};
@@ -1485,11 +1406,11 @@ struct SchNetFn : public torch::autograd::Function<SchNetFn> {
                         bool save_filters, at::TensorList ws) {
     at::AutoDispatchBelowADInplaceOrView guard;
     auto out = call_schnet_forward(x0, r_ij, idx_i, idx_j, ws, n_filters, rbf_kind, p0, p1, cutoff, save_filters);
-    std::vector<Tensor> sv{r_ij, std::get<1>(out), std::get<2>(out), p0, (p1.has_value() && p1->defined()) ? *p1 : Tensor(), idx_i, idx_j};
+    std::vector<Tensor> sv{r_ij, std::get<1>(out), std::get<2>(out), p0, opt_tensor(p1), idx_i, idx_j};
     for (const auto& w : ws) sv.push_back(w);
     ctx->save_for_backward(sv);
     ctx->saved_data["cfg"] = std::vector<int64_t>{x0.size(0), x0.size(1), n_filters, rbf_kind, save_filters};
-    ctx->saved_data["n_vars"] = (int64_t)(5 + ((p1.has_value() && p1->defined()) ? 1 : 0) + ws.size());
+    ctx->saved_data["n_vars"] = (int64_t)(5 + (has(p1) ? 1 : 0) + ws.size());
     ctx->saved_data["cutoff"] = cutoff;
     return std::get<0>(out);
   }
@@ -1516,7 +1437,7 @@ struct SchnetPotentialFn : public torch::autograd::Function<SchnetPotentialFn> {
                                at::TensorList head, int64_t n_mol, int64_t n_filters, int64_t rbf_kind, double cutoff, int64_t head_act) {
     at::AutoDispatchBelowADInplaceOrView guard;
     auto out = call_potential_forward(x0, R, offsets, idx_i, idx_j, idx_m, n_mol, ws, head, n_filters, rbf_kind, p0, p1, cutoff, head_act);
-    const bool has_off = offsets.has_value() && offsets->defined(), has_p1 = p1.has_value() && p1->defined();
+    const bool has_off = has(offsets), has_p1 = has(p1);
     std::vector<Tensor> sv{x0, R, idx_i, idx_j, idx_m, p0, has_off ? *offsets : Tensor(), has_p1 ? *p1 : Tensor(), std::get<2>(out), std::get<3>(out)};
     for (const auto& w : ws) sv.push_back(w);
     for (const auto& w : head) sv.push_back(w);
@@ -1564,11 +1485,11 @@ struct PaiNNFn : public torch::autograd::Function<PaiNNFn> {
                                double cutoff, at::TensorList ws) {
     at::AutoDispatchBelowADInplaceOrView guard;
     auto out = call_painn_forward(q0, r_ij, idx_i, idx_j, ws, shared_filters, eps, rbf_kind, p0, p1, cutoff);
-    std::vector<Tensor> sv{r_ij, std::get<2>(out), std::get<3>(out), p0, (p1.has_value() && p1->defined()) ? *p1 : Tensor(), idx_i, idx_j};
+    std::vector<Tensor> sv{r_ij, std::get<2>(out), std::get<3>(out), p0, opt_tensor(p1), idx_i, idx_j};
     for (const auto& w : ws) sv.push_back(w);
     ctx->save_for_backward(sv);
     ctx->saved_data["cfg"] = std::vector<int64_t>{q0.size(0), shared_filters, rbf_kind};
-    ctx->saved_data["n_vars"] = (int64_t)(5 + ((p1.has_value() && p1->defined()) ? 1 : 0) + ws.size());
+    ctx->saved_data["n_vars"] = (int64_t)(5 + (has(p1) ? 1 : 0) + ws.size());
     ctx->saved_data["cutoff"] = cutoff;
     ctx->saved_data["eps"] = eps;
     return {std::get<0>(out), std::get<1>(out)};
@@ -1595,7 +1516,7 @@ struct AtomwiseFn : public torch::autograd::Function<AtomwiseFn> {
     auto out = call_atomwise_forward(x, w1, b1, w2, b2, idx_m, n_mol, act);
     ctx->save_for_backward({std::get<2>(out), w1, w2, idx_m});
     ctx->saved_data["cfg"] = std::vector<int64_t>{n_mol, act};
-    ctx->saved_data["n_vars"] = (int64_t)(4 + ((b1.has_value() && b1->defined()) ? 1 : 0) + ((b2.has_value() && b2->defined()) ? 1 : 0));
+    ctx->saved_data["n_vars"] = (int64_t)(4 + (has(b1) ? 1 : 0) + (has(b2) ? 1 : 0));
     return {std::get<0>(out), std::get<1>(out)};
   }
   static variable_list backward(AutogradContext* ctx, variable_list grads) {
@@ -1667,7 +1588,7 @@ Tensor schnet_ad(const Tensor& x0, const Tensor& r_ij, const Tensor& idx_i, cons
 std::tuple<Tensor, Tensor> schnet_potential_ad(const Tensor& x0, const Tensor& R, const c10::optional<Tensor>& offsets, const Tensor& idx_i, const Tensor& idx_j,
                                                const Tensor& idx_m, int64_t n_mol, at::TensorList ws, at::TensorList head, int64_t n_filters, int64_t rbf_kind,
                                                const Tensor& p0, const c10::optional<Tensor>& p1, double cutoff, int64_t head_act) {
-  TORCH_CHECK(!(offsets.has_value() && offsets->defined() && offsets->requires_grad()),
+  TORCH_CHECK(!(has(offsets) && offsets->requires_grad()),
               "spk_hip::schnet_potential does not return a gradient w.r.t. the offsets (stress): run the modules separately for that");
   auto r = SchnetPotentialFn::apply(x0, R, idx_i, idx_j, idx_m, p0, offsets, p1, ws, head, n_mol, n_filters, rbf_kind, cutoff, head_act);
   return {r[0], r[1]};
@@ -1683,34 +1604,34 @@ std::tuple<Tensor, Tensor> schnet_potential_meta(const Tensor& x0, const Tensor&
                                                  double, int64_t) {
   return {at::empty({n_mol}, x0.options()), at::empty_like(x0)};
 }
-std::tuple<Tensor, Tensor, Tensor> schnet_potential_forces_meta(const c10::optional<Tensor>& x0, const c10::optional<Tensor>& emb, const Tensor&, const Tensor& R,
-                                                                const c10::optional<Tensor>&, const Tensor&, const Tensor&, const Tensor&, int64_t n_mol,
-                                                                at::TensorList, at::TensorList, int64_t, int64_t, const Tensor&, const c10::optional<Tensor>&,
-                                                                double, int64_t) {
-  const int64_t F = (x0.has_value() && x0->defined()) ? x0->size(1) : emb->size(1);
-  return {at::empty({n_mol}, R.options()), at::empty_like(R), at::empty({R.size(0), F}, R.options())};
+// shapes of potential_eval's (E, F, W, scalar_representation, vector_representation); the four Meta kernels pick theirs
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> potential_eval_meta(const OptT& x0, const OptT& emb, const Tensor& R, int64_t n_mol) {
+  const int64_t N = R.size(0), F = has(x0) ? x0->size(1) : emb->size(1);
+  return {at::empty({n_mol}, R.options()), at::empty_like(R), at::empty({n_mol, 3, 3}, R.options()), at::empty({N, F}, R.options()),
+          at::empty({N, 3, F}, R.options())};
 }
-std::tuple<Tensor, Tensor, Tensor, Tensor> painn_potential_forces_meta(const c10::optional<Tensor>& q0, const c10::optional<Tensor>& emb, const Tensor&, const Tensor& R,
-                                                                       const c10::optional<Tensor>&, const Tensor&, const Tensor&, const Tensor&, int64_t n_mol,
-                                                                       at::TensorList, at::TensorList, bool, double, int64_t, const Tensor&,
-                                                                       const c10::optional<Tensor>&, double, int64_t) {
-  const int64_t F = (q0.has_value() && q0->defined()) ? q0->size(1) : emb->size(1);
-  return {at::empty({n_mol}, R.options()), at::empty_like(R), at::empty({R.size(0), F}, R.options()), at::empty({R.size(0), 3, F}, R.options())};
+std::tuple<Tensor, Tensor, Tensor> schnet_potential_forces_meta(const OptT& x0, const OptT& emb, const Tensor&, const Tensor& R, const OptT&, const Tensor&,
+                                                                const Tensor&, const Tensor&, int64_t n_mol, at::TensorList, at::TensorList, int64_t, int64_t,
+                                                                const Tensor&, const OptT&, double, int64_t) {
+  auto o = potential_eval_meta(x0, emb, R, n_mol);
+  return {std::get<0>(o), std::get<1>(o), std::get<3>(o)};
 }
-std::tuple<Tensor, Tensor, Tensor, Tensor> schnet_potential_stress_meta(const c10::optional<Tensor>& x0, const c10::optional<Tensor>& emb, const Tensor&,
-                                                                        const Tensor& R, const c10::optional<Tensor>&, const Tensor&, const Tensor&, const Tensor&,
-                                                                        int64_t n_mol, at::TensorList, at::TensorList, int64_t, int64_t, const Tensor&,
-                                                                        const c10::optional<Tensor>&, double, int64_t) {
-  const int64_t F = (x0.has_value() && x0->defined()) ? x0->size(1) : emb->size(1);
-  return {at::empty({n_mol}, R.options()), at::empty_like(R), at::empty({n_mol, 3, 3}, R.options()), at::empty({R.size(0), F}, R.options())};
+std::tuple<Tensor, Tensor, Tensor, Tensor> painn_potential_forces_meta(const OptT& q0, const OptT& emb, const Tensor&, const Tensor& R, const OptT&, const Tensor&,
+                                                                       const Tensor&, const Tensor&, int64_t n_mol, at::TensorList, at::TensorList, bool, double,
+                                                                       int64_t, const Tensor&, const OptT&, double, int64_t) {
+  auto o = potential_eval_meta(q0, emb, R, n_mol);
+  return {std::get<0>(o), std::get<1>(o), std::get<3>(o), std::get<4>(o)};
 }
-std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> painn_potential_stress_meta(const c10::optional<Tensor>& q0, const c10::optional<Tensor>& emb, const Tensor&,
-                                                                               const Tensor& R, const c10::optional<Tensor>&, const Tensor&, const Tensor&,
-                                                                               const Tensor&, int64_t n_mol, at::TensorList, at::TensorList, bool, double,
-                                                                               int64_t, const Tensor&, const c10::optional<Tensor>&, double, int64_t) {
-  const int64_t F = (q0.has_value() && q0->defined()) ? q0->size(1) : emb->size(1);
-  return {at::empty({n_mol}, R.options()), at::empty_like(R), at::empty({n_mol, 3, 3}, R.options()), at::empty({R.size(0), F}, R.options()),
-          at::empty({R.size(0), 3, F}, R.options())};
+std::tuple<Tensor, Tensor, Tensor, Tensor> schnet_potential_stress_meta(const OptT& x0, const OptT& emb, const Tensor&, const Tensor& R, const OptT&, const Tensor&,
+                                                                        const Tensor&, const Tensor&, int64_t n_mol, at::TensorList, at::TensorList, int64_t, int64_t,
+                                                                        const Tensor&, const OptT&, double, int64_t) {
+  auto o = potential_eval_meta(x0, emb, R, n_mol);
+  return {std::get<0>(o), std::get<1>(o), std::get<2>(o), std::get<3>(o)};
+}
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> painn_potential_stress_meta(const OptT& q0, const OptT& emb, const Tensor&, const Tensor& R, const OptT&,
+                                                                               const Tensor&, const Tensor&, const Tensor&, int64_t n_mol, at::TensorList,
+                                                                               at::TensorList, bool, double, int64_t, const Tensor&, const OptT&, double, int64_t) {
+  return potential_eval_meta(q0, emb, R, n_mol);
 }
 std::tuple<Tensor, Tensor, Tensor, Tensor> schnet_potential_forward_meta(const Tensor& x0, const Tensor&, const c10::optional<Tensor>&, const Tensor& idx_i,
                                                                          const Tensor&, const Tensor&, int64_t n_mol, at::TensorList ws, at::TensorList head,
@@ -1784,13 +1705,13 @@ std::tuple<Tensor, Tensor> painn_backward_op(const c10::optional<Tensor>& gq, co
   auto plan = get_plan(idx_i, idx_j, n_atoms, r_ij);
   if (plan->filter_pairs < 0 && plan->n_edges >= (1 << 19)) decide_filter(*plan, r_ij, cutoff);
   const int64_t F = ws[0].size(0);     // interatomic_context_net.0.weight [F, F]
-  auto res = painn_backward_raw((gq.has_value() && gq->defined()) ? *gq : Tensor(), (gmu.has_value() && gmu->defined()) ? *gmu : Tensor(), r_ij, saved, scratch,
+  auto res = painn_backward_raw(opt_tensor(gq), opt_tensor(gmu), r_ij, saved, scratch,
                                 *plan, ws, F, shared_filters, eps, rbf_kind, p0, p1, cutoff, want_gq0);
   return {std::get<0>(res), want_gq0 ? std::get<1>(res) : at::empty({0}, r_ij.options())};
 }
 Tensor atomwise_backward_op(const c10::optional<Tensor>& gE, const c10::optional<Tensor>& gy, const Tensor& pre, const Tensor& w1, const Tensor& w2,
                             const Tensor& idx_m, int64_t n_mol, int64_t act) {
-  return atomwise_backward_raw((gE.has_value() && gE->defined()) ? *gE : Tensor(), (gy.has_value() && gy->defined()) ? *gy : Tensor(), pre, w1, w2, idx_m, n_mol, act);
+  return atomwise_backward_raw(opt_tensor(gE), opt_tensor(gy), pre, w1, w2, idx_m, n_mol, act);
 }
 
 // (rowptr, rev, half, flags[sorted, symmetric, n_half, filter_pairs, by-neighbour copy built]) of a list; also warms the cache outside a graph capture
@@ -1798,7 +1719,7 @@ Tensor atomwise_backward_op(const c10::optional<Tensor>& gE, const c10::optional
 std::tuple<Tensor, Tensor, Tensor, Tensor> edge_plan_op(const Tensor& idx_i, const Tensor& idx_j, int64_t n_atoms, const c10::optional<Tensor>& r_ij,
                                                         double cutoff, int64_t force_filter) {
   require_device(idx_i, "edge_plan");
-  Tensor r = (r_ij.has_value() && r_ij->defined()) ? *r_ij : Tensor();
+  Tensor r = opt_tensor(r_ij);
   auto p = get_plan(idx_i, idx_j, n_atoms, r);
   if (force_filter >= 0) p->filter_pairs = (force_filter != 0 && p->symmetric && p->n_edges > 0) ? 1 : 0;
   else if (r.defined() && cutoff > 0) decide_filter(*p, r, cutoff);
@@ -1812,7 +1733,7 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> edge_plan_op(const Tensor& idx_i, con
 // n_half, n_groups, max_group_atoms, max_group_pairs, filter_pairs (-1 undecided), n_tiles_grouped] (int64, host).
 std::vector<Tensor> edge_plan_arrays_op(const Tensor& idx_i, const Tensor& idx_j, int64_t n_atoms, const c10::optional<Tensor>& r_ij) {
   require_device(idx_i, "edge_plan_arrays");
-  Tensor r = (r_ij.has_value() && r_ij->defined()) ? *r_ij : Tensor();
+  Tensor r = opt_tensor(r_ij);
   auto p = get_plan(idx_i, idx_j, n_atoms, r);
   auto iopt = at::TensorOptions().dtype(at::kInt).device(idx_i.device());
   auto or_empty = [&](const Tensor& t) { return t.defined() ? t : at::empty({0}, iopt); };

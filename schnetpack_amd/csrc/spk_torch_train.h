@@ -82,8 +82,6 @@ std::tuple<Tensor, Tensor, Tensor> gemm_pair_raw(const Tensor& a_in, const Tenso
   return {out, G, cs};
 }
 
-bool has(const OptT& t) { return t.has_value() && t->defined(); }
-
 Tensor edge_mul_raw(const Tensor& a_in, const Tensor& b_in, const OptT& ia_in, const OptT& ib_in) {
   Tensor a = f32(a_in, "edge_mul"), b = f32(b_in, "edge_mul");
   TORCH_CHECK(has(ia_in) || has(ib_in), "edge_mul: at least one index is required (use a plain product otherwise)");

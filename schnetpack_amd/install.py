@@ -78,23 +78,13 @@ def _fused_potential_call(orig_call):
         if n_tail is None:      # DipoleMoment / Polarizability mirrors at the end of output_modules: they run behind the fused call
             n_tail = M.tensorial_tail(list(self.output_modules))
             self.__dict__["_spk_hip_tail"] = n_tail
-        if mode == 2:
-            inputs = M.potential_forces_forward(self, inputs)
-        elif mode == 3:
-            inputs = M.potential_stress_forward(self, inputs)
-        elif mode in (4, 5):      # ... with a ZBL repulsion aggregated into the energy: one more launch
+        lay = None
+        if mode in (4, 5):      # ... with a ZBL repulsion aggregated into the energy: one more launch
             lay = self.__dict__.get("_spk_hip_zbl")
             if lay is None:
                 lay = M.zbl_layout(list(self.output_modules)[:len(self.output_modules) - n_tail])
                 self.__dict__["_spk_hip_zbl"] = lay
-            inputs = M.potential_stress_forward(self, inputs, lay) if mode == 5 else M.potential_forces_forward(self, inputs, lay)
-        else:
-            inputs = M.potential_forward(self, inputs)
-            for i, m in enumerate(self.output_modules):
-                if i > 0:
-                    inputs = m(inputs)
-            n_tail = 0          # (the loop above has run them)
-        inputs = M.run_tail(self, inputs, n_tail)
+        inputs = M.fused_eval_forward(self, inputs, mode, lay, n_tail)
         inputs = self.postprocess(inputs)
         return self.extract_outputs(inputs)
 

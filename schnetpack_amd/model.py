@@ -153,63 +153,49 @@ def _zbl_add(zbl, inputs: Dict[str, torch.Tensor], n_mol: int, F: torch.Tensor, 
                                         inputs[properties.idx_m], n_mol, zbl.op_params(R), F, W)
 
 
-def potential_forces_forward(model, inputs: Dict[str, torch.Tensor], layout: Optional[Tuple[int, int, int, int]] = None) -> Dict[str, torch.Tensor]:
-    """Energies and forces straight from the two launches (no autograd node: eval only; the embedding rows are looked up
-    inside the forward launch when the nuclear embedding is a plain table).  With a ``layout`` (:func:`zbl_layout`, mode 4) the ZBL
-    repulsion is added by one more operator and the learned, the repulsion and the aggregated energies are all set."""
+def _potential_eval(model, inputs: Dict[str, torch.Tensor], layout: Optional[Tuple[int, int, int, int]], stress: bool) -> Dict[str, torch.Tensor]:
+    """The eval body of modes 2 - 5: the one operator that the representation and ``stress`` select, the ZBL repulsion when a ``layout`` is given,
+    stress = W / V under ``stress``, then the dict."""
     outs = model.output_modules
     rep, head, frc = model.representation, outs[0], outs[1]
     zbl, agg = None, None
     if layout is not None:
         head, zbl, agg, frc = outs[layout[0]], outs[layout[1]], outs[layout[2]], outs[layout[3]]
     idx_m = inputs[properties.idx_m]
+    n_mol = head._n_molecules(inputs, idx_m)
     kind, p0, p1 = rep.radial_basis.kernel_params()
     l0, l1 = head.outnet[0], head.outnet[1]
     plain = type(rep.embedding) is nn.Embedding and len(rep.electronic_embeddings) == 0
-    if isinstance(rep, PaiNN):
-        with torch.no_grad():
-            E, F, x, mu = torch.ops.spk_hip.painn_potential_forces(
-                None if plain else rep.embed(inputs), rep.embedding.weight if plain else None, inputs[properties.Z], inputs[properties.R],
-                inputs.get(properties.offsets), inputs[properties.idx_i], inputs[properties.idx_j], idx_m, head._n_molecules(inputs, idx_m),
-                rep.interaction_weights(), [l0.weight, l0.bias, l1.weight, l1.bias], rep.share_filters, rep.epsilon, kind, p0, p1,
-                rep.cutoff_fn.cutoff_value(), head._head_act)
-            if zbl is not None:
-                Ez = _zbl_add(zbl, inputs, head._n_molecules(inputs, idx_m), F, None)
-                Et = E + Ez
-        if torch.is_grad_enabled():
-            guard = [l0.weight]
-            E, F = torch.ops.spk_hip.eval_guard(E, guard), torch.ops.spk_hip.eval_guard(F, guard)
-            if zbl is not None:
-                Ez, Et = torch.ops.spk_hip.eval_guard(Ez, guard), torch.ops.spk_hip.eval_guard(Et, guard)
-        inputs["scalar_representation"] = x
-        inputs["vector_representation"] = mu
-        inputs[head.output_key] = E
-        inputs[frc.force_key] = F
-        if zbl is not None:
-            inputs[zbl.output_key] = Ez
-            inputs[agg.output_key] = Et
-        return inputs
+    painn = isinstance(rep, PaiNN)
+    op = getattr(torch.ops.spk_hip, ("painn" if painn else "schnet") + ("_potential_stress" if stress else "_potential_forces"))
     with torch.no_grad():
-        x0 = None if plain else rep.embed(inputs)
-        E, F, x = torch.ops.spk_hip.schnet_potential_forces(
-            x0, rep.embedding.weight if plain else None, inputs[properties.Z], inputs[properties.R], inputs.get(properties.offsets),
-            inputs[properties.idx_i], inputs[properties.idx_j], idx_m, head._n_molecules(inputs, idx_m), rep.interaction_weights(),
-            [l0.weight, l0.bias, l1.weight, l1.bias], rep.n_filters, kind, p0, p1, rep.cutoff_fn.cutoff_value(), head._head_act)
+        res = list(op(None if plain else rep.embed(inputs), rep.embedding.weight if plain else None, inputs[properties.Z], inputs[properties.R],
+                      inputs.get(properties.offsets), inputs[properties.idx_i], inputs[properties.idx_j], idx_m, n_mol, rep.interaction_weights(),
+                      [l0.weight, l0.bias, l1.weight, l1.bias], *((rep.share_filters, rep.epsilon) if painn else (rep.n_filters,)), kind, p0, p1,
+                      rep.cutoff_fn.cutoff_value(), head._head_act))
+        E, F, W = res[0], res[1], res[2] if stress else None
+        named = {head.output_key: E, frc.force_key: F}
         if zbl is not None:
-            Ez = _zbl_add(zbl, inputs, head._n_molecules(inputs, idx_m), F, None)
-            Et = E + Ez
+            named[zbl.output_key] = _zbl_add(zbl, inputs, n_mol, F, W)
+            named[agg.output_key] = E + named[zbl.output_key]
+        if stress:
+            cell = inputs[properties.cell]
+            volume = torch.sum(cell[:, 0, :] * torch.cross(cell[:, 1, :], cell[:, 2, :], dim=1), dim=1, keepdim=True)[:, :, None]
+            named[frc.stress_key] = W / volume
     if torch.is_grad_enabled():      # a backward pass into this eval-mode model gets the eval-only message, not silence
-        guard = [l0.weight]
-        E, F = torch.ops.spk_hip.eval_guard(E, guard), torch.ops.spk_hip.eval_guard(F, guard)
-        if zbl is not None:
-            Ez, Et = torch.ops.spk_hip.eval_guard(Ez, guard), torch.ops.spk_hip.eval_guard(Et, guard)
-    inputs["scalar_representation"] = x
-    inputs[head.output_key] = E
-    inputs[frc.force_key] = F
-    if zbl is not None:
-        inputs[zbl.output_key] = Ez
-        inputs[agg.output_key] = Et
+        named = {k: torch.ops.spk_hip.eval_guard(v, [l0.weight]) for k, v in named.items()}
+    inputs["scalar_representation"] = res[-2] if painn else res[-1]
+    if painn:
+        inputs["vector_representation"] = res[-1]
+    inputs.update(named)
     return inputs
+
+
+def potential_forces_forward(model, inputs: Dict[str, torch.Tensor], layout: Optional[Tuple[int, int, int, int]] = None) -> Dict[str, torch.Tensor]:
+    """Energies and forces straight from the two launches (no autograd node: eval only; the embedding rows are looked up
+    inside the forward launch when the nuclear embedding is a plain table).  With a ``layout`` (:func:`zbl_layout`, mode 4) the ZBL
+    repulsion is added by one more operator and the learned, the repulsion and the aggregated energies are all set."""
+    return _potential_eval(model, inputs, layout, False)
 
 
 def potential_stress_forward(model, inputs: Dict[str, torch.Tensor], layout: Optional[Tuple[int, int, int, int]] = None) -> Dict[str, torch.Tensor]:
@@ -217,46 +203,19 @@ def potential_stress_forward(model, inputs: Dict[str, torch.Tensor], layout: Opt
     virial W = dE/dstrain [n_mol, 3, 3]; stress = W / V with the signed cell volume, as ``Forces`` computes it (atomistic/response.py:81-90).
     ``Strain`` itself does not run: at zero strain it leaves positions, offsets and cell as they are.  With a ``layout`` (mode 5) the ZBL
     repulsion is added into forces and virial by one more operator, as in :func:`potential_forces_forward`."""
-    outs = model.output_modules
-    rep, head, frc = model.representation, outs[0], outs[1]
-    zbl, agg = None, None
-    if layout is not None:
-        head, zbl, agg, frc = outs[layout[0]], outs[layout[1]], outs[layout[2]], outs[layout[3]]
-    idx_m = inputs[properties.idx_m]
-    kind, p0, p1 = rep.radial_basis.kernel_params()
-    l0, l1 = head.outnet[0], head.outnet[1]
-    plain = type(rep.embedding) is nn.Embedding and len(rep.electronic_embeddings) == 0
-    common = (inputs[properties.Z], inputs[properties.R], inputs.get(properties.offsets), inputs[properties.idx_i], inputs[properties.idx_j], idx_m,
-              head._n_molecules(inputs, idx_m), rep.interaction_weights(), [l0.weight, l0.bias, l1.weight, l1.bias])
-    with torch.no_grad():
-        if isinstance(rep, PaiNN):
-            E, F, W, x, mu = torch.ops.spk_hip.painn_potential_stress(
-                None if plain else rep.embed(inputs), rep.embedding.weight if plain else None, *common, rep.share_filters, rep.epsilon, kind, p0, p1,
-                rep.cutoff_fn.cutoff_value(), head._head_act)
-            inputs["vector_representation"] = mu
-        else:
-            E, F, W, x = torch.ops.spk_hip.schnet_potential_stress(
-                None if plain else rep.embed(inputs), rep.embedding.weight if plain else None, *common, rep.n_filters, kind, p0, p1,
-                rep.cutoff_fn.cutoff_value(), head._head_act)
-        if zbl is not None:
-            Ez = _zbl_add(zbl, inputs, head._n_molecules(inputs, idx_m), F, W)
-            Et = E + Ez
-        cell = inputs[properties.cell]
-        volume = torch.sum(cell[:, 0, :] * torch.cross(cell[:, 1, :], cell[:, 2, :], dim=1), dim=1, keepdim=True)[:, :, None]
-        S = W / volume
-    if torch.is_grad_enabled():
-        guard = [l0.weight]
-        E, F, S = torch.ops.spk_hip.eval_guard(E, guard), torch.ops.spk_hip.eval_guard(F, guard), torch.ops.spk_hip.eval_guard(S, guard)
-        if zbl is not None:
-            Ez, Et = torch.ops.spk_hip.eval_guard(Ez, guard), torch.ops.spk_hip.eval_guard(Et, guard)
-    inputs["scalar_representation"] = x
-    inputs[head.output_key] = E
-    inputs[frc.force_key] = F
-    inputs[frc.stress_key] = S
-    if zbl is not None:
-        inputs[zbl.output_key] = Ez
-        inputs[agg.output_key] = Et
-    return inputs
+    return _potential_eval(model, inputs, layout, True)
+
+
+def fused_eval_forward(model, inputs: Dict[str, torch.Tensor], mode: int, layout: Optional[Tuple[int, int, int, int]], n_tail: int) -> Dict[str, torch.Tensor]:
+    """The route of a :func:`classify_potential` mode 1 - 5 (``layout``: :func:`zbl_layout` for modes 4 / 5, else None), for
+    ``NeuralNetworkPotential.forward`` and for the hook that ``install`` puts on the reference's class."""
+    if mode == 1:
+        inputs = potential_forward(model, inputs)
+        for i, m in enumerate(model.output_modules):      # (a tensorial tail is among them)
+            if i > 0:
+                inputs = m(inputs)
+        return inputs
+    return run_tail(model, _potential_eval(model, inputs, layout, mode in (3, 5)), n_tail)
 
 
 def potential_fm_forward(model, inputs: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
@@ -385,22 +344,17 @@ class NeuralNetworkPotential(nn.Module):
         return potential_fm_forward(self, inputs)
 
     @torch.jit.unused
-    def _potential_forward(self, inputs: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
-        return potential_forward(self, inputs)
+    def _fused_forward(self, inputs: Dict[str, torch.Tensor], mode: int) -> Dict[str, torch.Tensor]:
+        lay = (self._zbl_layout[0], self._zbl_layout[1], self._zbl_layout[2], self._zbl_layout[3]) if mode in (4, 5) else None
+        return fused_eval_forward(self, inputs, mode, lay, self._n_tail)
 
     @torch.jit.unused
     def _potential_forces_forward(self, inputs: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
-        return run_tail(self, potential_forces_forward(self, inputs), self._n_tail)
-
-    @torch.jit.unused
-    def _potential_zbl_forward(self, inputs: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
-        lay = (self._zbl_layout[0], self._zbl_layout[1], self._zbl_layout[2], self._zbl_layout[3])
-        inputs = potential_stress_forward(self, inputs, lay) if self._zbl_stress else potential_forces_forward(self, inputs, lay)
-        return run_tail(self, inputs, self._n_tail)
+        return self._fused_forward(inputs, 2)
 
     @torch.jit.unused
     def _potential_stress_forward(self, inputs: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
-        return run_tail(self, potential_stress_forward(self, inputs), self._n_tail)
+        return self._fused_forward(inputs, 3)
 
     def forward(self, inputs: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
         for p in self.required_derivatives:
@@ -414,14 +368,19 @@ class NeuralNetworkPotential(nn.Module):
             for m in self.output_modules:
                 inputs = m(inputs)
             return {k: inputs[k] for k in self.model_outputs}
-        if self._potential_forces and not self.training and not torch.jit.is_scripting():
-            inputs = self._potential_forces_forward(inputs)
-            return {k: inputs[k] for k in self.model_outputs}
-        if self._potential_stress and not self.training and not torch.jit.is_scripting():
-            inputs = self._potential_stress_forward(inputs)
-            return {k: inputs[k] for k in self.model_outputs}
-        if self._potential_zbl and not self.training and not torch.jit.is_scripting():
-            inputs = self._potential_zbl_forward(inputs)
+        # the route, from the flags as they are at this call (callers toggle them): forces, stress, zbl, then mode 1; training has the engine below
+        mode = 0
+        if not self.training and not torch.jit.is_scripting():
+            if self._potential_forces:
+                mode = 2
+            elif self._potential_stress:
+                mode = 3
+            elif self._potential_zbl:
+                mode = 5 if self._zbl_stress else 4
+            elif self._potential:
+                mode = 1
+        if mode > 0:
+            inputs = self._fused_forward(inputs, mode)
             return {k: inputs[k] for k in self.model_outputs}
         if self.training and self.fm_engine and not torch.jit.is_scripting():
             pos = inputs[properties.R]
@@ -431,12 +390,6 @@ class NeuralNetworkPotential(nn.Module):
             if pos.is_cuda and pos.dtype == torch.float32 and w0.is_cuda and w0.dtype == torch.float32:
                 inputs = self._potential_fm_forward(inputs)
                 return {k: inputs[k] for k in self.model_outputs}
-        if self._potential and not self.training and not torch.jit.is_scripting():
-            inputs = self._potential_forward(inputs)
-            for i, m in enumerate(self.output_modules):
-                if i > 0:
-                    inputs = m(inputs)
-            return {k: inputs[k] for k in self.model_outputs}
         for m in self.input_modules:
             inputs = m(inputs)
         inputs = self.representation(inputs)

@@ -249,3 +249,71 @@ def test_edge_virial_kernel(dev, sort):
     assert torch.equal(W, W2) and torch.equal(Wa, Wa2)
     assert float(W[3].abs().max()) == 0.0 and float(W[2].abs().max()) == 0.0      # no atoms / no edges
     assert rel_err(W, Wref) < TOL and rel_err(Wa, Waref) < TOL
+
+
+def _three_molecules():
+    """Three fully connected molecules of 3, 9 and 21 atoms (each inside one group: well inside 32 atoms and 384 pairs), every pair inside the 5 A cutoff,
+    in a cubic cell wide enough that every image shift is zero: the offsets are there and vanish."""
+    rng = np.random.RandomState(7)
+    systems = []
+    for n in (3, 9, 21):
+        R = np.zeros((0, 3))
+        while len(R) < n:                     # points of a 2.8 A cube (diagonal 4.85 A), at least 0.8 A apart
+            p = rng.uniform(0.0, 2.8, 3)
+            if len(R) == 0 or np.linalg.norm(R - p, axis=1).min() > 0.8:
+                R = np.vstack([R, p])
+        ii, jj = np.nonzero(~np.eye(n, dtype=bool))          # sorted by (i, j), symmetric
+        systems.append({"Z": rng.choice([1, 6, 7, 8], n), "R": R, "idx_i": ii, "idx_j": jj})
+    return S.collate(systems)
+
+
+@pytest.mark.parametrize("form", ["features", "table"])
+@pytest.mark.parametrize("route", ["fused", "three_stage"])
+@pytest.mark.parametrize("kind", ["schnet", "painn"])
+def test_forces_and_stress_operators_agree(dev, monkeypatch, kind, route, form):
+    """What the comments of the four eval operators promise about each other, on both routes and with both input forms: the stress operator
+    returns the energies, forces and representation of the forces operator bit for bit -- but for PaiNN's molecule-resident launches, whose
+    forces are the row sum of dE/dr and agree to round-off -- and the embedding-table form returns what the feature form returns."""
+    if route == "three_stage":
+        monkeypatch.setenv("SPK_NO_POTENTIAL", "1")
+    torch.manual_seed(0)
+    m = M.build_model(kind, n_interactions=2).to(dev).eval()
+    rep, head = m.representation, m.output_modules[0]
+    b = _three_molecules()
+    inp = _inputs(dict(b, cell=torch.eye(3).repeat(3, 1, 1) * 40.0), dev)
+    assert float(inp["_offsets"].abs().max()) == 0.0 and inp["_offsets"].shape == (3 * 2 + 9 * 8 + 21 * 20, 3)
+    kind_id, p0, p1 = rep.radial_basis.kernel_params()
+    l0, l1 = head.outnet[0], head.outnet[1]
+    model_args = (rep.share_filters, rep.epsilon) if kind == "painn" else (rep.n_filters,)
+    n_rep = 2 if kind == "painn" else 1
+
+    def call(op, table):
+        x0 = None if table else rep.embedding(inp["_atomic_numbers"]).detach()
+        with torch.no_grad():
+            return op(x0, rep.embedding.weight if table else None, inp["_atomic_numbers"], inp["_positions"], inp["_offsets"], inp["_idx_i"],
+                      inp["_idx_j"], inp["_idx_m"], 3, rep.interaction_weights(), [l0.weight, l0.bias, l1.weight, l1.bias], *model_args, kind_id, p0, p1,
+                      rep.cutoff_fn.cutoff_value(), head._head_act)
+
+    ops = torch.ops.spk_hip
+    f_op, s_op = getattr(ops, kind + "_potential_forces"), getattr(ops, kind + "_potential_stress")
+    fo = call(f_op, form == "table")                                         # (first call on this list: the plan)
+    _lib.profile_enable(True)
+    _lib.profile_report()
+    fo, so = call(f_op, form == "table"), call(s_op, form == "table")
+    prof = _lib.profile_report()
+    _lib.profile_enable(False)
+    assert prof[kind + "_mol_fwd"][0] == 2 and ("atomwise_fwd" in prof) == (route == "three_stage"), prof      # the route is the one asked for
+    assert so[2].shape == (3, 3, 3) and torch.isfinite(so[2]).all()
+    assert torch.equal(fo[0], so[0])                                        # energies
+    for k in range(n_rep):                                                  # scalar (and vector) representation
+        assert torch.equal(fo[2 + k], so[3 + k])
+    err = rel_err(so[1], fo[1])
+    print("%s %s %s: forces of the two operators differ by %.3g of max|F|" % (kind, route, form, err))
+    if kind == "painn" and route == "fused":
+        assert err <= TOL
+    else:
+        assert torch.equal(fo[1], so[1])
+    if form == "table":                                                     # ... and the same operator fed the looked-up rows
+        for op, got in ((f_op, fo), (s_op, so)):
+            base = call(op, False)
+            assert torch.equal(got[0], base[0]) and torch.equal(got[1], base[1])
