@@ -573,7 +573,13 @@ typedef struct {
   int32_t n_interactions;
   int32_t reserved;       /* bit 0: `saved` was sized with spk_schnet_saved_floats_graph(): the forward keeps
                              the raw filter outputs of every (undirected) edge so that the backward runs
-                             only the derivative GEMM */
+                             only the derivative GEMM
+                             bit 1 (with bit 0): `saved` was sized with this bit set -- spk_schnet_saved_floats_graph() then adds the
+                             records region of the molecule-resident launches, spk_schnet_mol_records_floats() floats BEHIND every
+                             other region (h | pre3, filter outputs, per-call pair list: their offsets do not depend on the bit): the
+                             forward launch leaves the pair records of every group there (atoms, distance, f_c, f_c', pair vector,
+                             record index per list position, records per group) and the backward launch starts from them instead of
+                             walking half -> idx_i, idx_j -> R again.  Size `saved` with the model block the launches get (wpack set) */
   const spk_schnet_layer_t* layers; /* HOST array of n_interactions entries (device pointers inside) */
   const float* wpack;     /* optional (may be NULL): packed images of the Dense weights, spk_schnet_packed_floats()
                              floats filled by spk_schnet_pack_weights_f32(); refresh it when the weights change */
@@ -588,6 +594,10 @@ int64_t spk_schnet_packed_floats(const spk_schnet_t* m);
 int spk_schnet_pack_weights_f32(const spk_schnet_t* m, float* wpack, void* stream);
 int64_t spk_schnet_saved_floats(const spk_schnet_t* m, int64_t n_atoms);
 int64_t spk_schnet_saved_floats_graph(const spk_schnet_t* m, const spk_graph_t* g, const spk_radial_t* rb);
+/* floats of the records region at the end of `saved`: 0 unless bits 0 and 1 of m->reserved are set, the filters are saved for this
+ * list and the molecule-resident backward covers it (block-diagonal, <= 32 atoms and <= 384 pairs per block, n_rbf <= 24); otherwise
+ * 8 n_half + n_groups + the 0 ... 3 floats that bring its start to a multiple of four */
+int64_t spk_schnet_mol_records_floats(const spk_schnet_t* m, const spk_graph_t* g, const spk_radial_t* rb);
 int64_t spk_schnet_scratch_floats(const spk_schnet_t* m, int64_t n_atoms);
 /* x0 [N,F] = embedding rows (+ electronic embeddings) computed by the caller;
  * x_out [N,F] = scalar_representation. */
@@ -670,6 +680,11 @@ void spk_schnet_mol_set_debug_buffer(void* device_buffer);
  * per (tile, channel-tile pair), the hidden layer twice; 0 = automatic (default; the rule is written at the task queue).  Read at
  * launch.  For tuning and tests. */
 void spk_schnet_mol_set_bwd_task_split(int split);
+/* Where the set-up of that backward takes the pair records of a group from: 0 = automatic (default: from the records region of
+ * `saved` where there is one, see spk_schnet_t::reserved), 1 = always recompute them from the list and the positions (no region is
+ * read; the forward still writes it), 2 = require the region: the backward entry points return SPK_ERR_ARG where `saved` has none.
+ * Results do not depend on the mode, bit for bit.  Read at launch.  For tuning and tests. */
+void spk_schnet_mol_set_bwd_records(int mode);
 /* The same for the molecule-resident PaiNN kernels (spk_painn_mol.hip; representation/painn.py:207-256 with q / mu / context rows
  * of a <= 32-atom block in LDS, all interactions in one launch): >= 256 int64; entry 0 = group start, 1 + 8 l .. 8 + 8 l = phase
  * boundaries of interaction l of the forward (thread 0 of workgroup 0); entries 64.. the backward, 128 + 16 w .. the message phase

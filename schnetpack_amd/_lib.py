@@ -203,9 +203,11 @@ _PROTOS = {
     "spk_cfconv_set_rowtile": (None, [c_i32]),
     "spk_schnet_mol_set_debug_buffer": (None, [c_f]),
     "spk_schnet_mol_set_bwd_task_split": (None, [ctypes.c_int]),
+    "spk_schnet_mol_set_bwd_records": (None, [ctypes.c_int]),
     "spk_painn_mol_set_debug_buffer": (None, [c_f]),
     "spk_schnet_saved_floats": (c_i64, [P(SchnetT), c_i64]),
     "spk_schnet_saved_floats_graph": (c_i64, [P(SchnetT), P(GraphT), P(RadialT)]),
+    "spk_schnet_mol_records_floats": (c_i64, [P(SchnetT), P(GraphT), P(RadialT)]),
     "spk_schnet_scratch_floats": (c_i64, [P(SchnetT), c_i64]),
     "spk_schnet_forward_f32": (ctypes.c_int, [P(SchnetT), P(GraphT), P(RadialT), c_f, c_f, c_f, c_f, c_f, c_f]),
     "spk_schnet_backward_f32": (ctypes.c_int, [P(SchnetT), P(GraphT), P(RadialT), c_f, c_f, c_f, c_f, c_f, c_f, c_f]),

@@ -316,7 +316,7 @@ int run_model(spk_potential* p, int64_t N, int64_t E, int64_t M, bool new_list, 
   if ((rc = spk_embedding_f32(p->t.at("embedding"), p->z.as<int64_t>(), N, F, p->x0.as<float>(), s))) return rc;
   int64_t n_saved, n_scratch;
   if (h.kind == 0) {
-    p->sm.reserved = 1;
+    p->sm.reserved = 3;      // filters and pair records saved for the backward
     n_saved = spk_schnet_saved_floats_graph(&p->sm, g, &p->rb);
     n_scratch = spk_schnet_scratch_floats(&p->sm, N);
   } else {

@@ -44,10 +44,34 @@ static bool schnet_filter_on(const spk_schnet_t* m, const spk_graph_t* g, const 
   return g->filter_pairs && g->n_half > 0 && spk_get_variant() != SPK_VARIANT_MFMA_MOL &&
          spk_cfconv_gsave_floats(g, rb, m->n_filters) > 0;
 }
-extern "C" int64_t spk_schnet_saved_floats_graph(const spk_schnet_t* m, const spk_graph_t* g, const spk_radial_t* rb) {
-  if (!m || !g || !rb) return 0;
+static int64_t schnet_saved_floats_before_records(const spk_schnet_t* m, const spk_graph_t* g, const spk_radial_t* rb) {
   return spk_schnet_saved_floats(m, g->n_atoms) + (int64_t)m->n_interactions * spk_cfconv_gsave_floats(g, rb, m->n_filters) +
          (schnet_filter_on(m, g, rb) ? spk_active_pairs_floats(g->n_half) : 0);
+}
+// The records region (spk_schnet_mol.hip: the pair records of every group, handed from the molecule-resident forward to the backward)
+// lies behind every other region of `saved`, so no other offset depends on it.  It exists exactly when the caller asked for it (bit 1
+// of the model word: `saved` is sized for it), the filters are saved and the molecule-resident backward covers the list -- the
+// condition under which the forward compacts its pair tiles.  *off: first float of the region, rounded up to a multiple of four
+// (16-byte records); *floats: what spk_schnet_saved_floats_graph() grows by = that padding + 8 n_half + n_groups
+// (records 4 n_half | pair vectors 3 n_half | record index per list position n_half | records per group n_groups).
+bool spk_schnet_mol_bwd_eligible(const spk_schnet_t* m, const spk_graph_t* g, const spk_radial_t* rb);
+bool spk_schnet_mol_records_region(const spk_schnet_t* m, const spk_graph_t* g, const spk_radial_t* rb, int64_t* off, int64_t* floats) {
+  *off = 0; *floats = 0;
+  if (!m || !g || !rb || (m->reserved & 3) != 3 || !m->layers || m->n_interactions <= 0) return false;
+  if (spk_cfconv_gsave_floats(g, rb, m->n_filters) <= 0 || !spk_schnet_mol_bwd_eligible(m, g, rb)) return false;
+  const int64_t end = schnet_saved_floats_before_records(m, g, rb);
+  *off = (end + 3) & ~(int64_t)3;
+  *floats = (*off - end) + 8 * (int64_t)g->n_half + g->n_groups;
+  return true;
+}
+extern "C" int64_t spk_schnet_mol_records_floats(const spk_schnet_t* m, const spk_graph_t* g, const spk_radial_t* rb) {
+  int64_t off, floats;
+  spk_schnet_mol_records_region(m, g, rb, &off, &floats);
+  return floats;
+}
+extern "C" int64_t spk_schnet_saved_floats_graph(const spk_schnet_t* m, const spk_graph_t* g, const spk_radial_t* rb) {
+  if (!m || !g || !rb) return 0;
+  return schnet_saved_floats_before_records(m, g, rb) + spk_schnet_mol_records_floats(m, g, rb);
 }
 
 // scratch: forward  y0 | y1 | t0 | t1            (2 nf + 2 max(F, nf))
@@ -66,6 +90,7 @@ bool spk_schnet_mol_eligible(const spk_schnet_t* m, const spk_graph_t* g, const 
 int spk_schnet_mol_forward(const spk_schnet_t* m, const spk_graph_t* g, const spk_radial_t* rb, const SpkPackTable& ptab,
                            const float* x0, const float* r_ij, float* x_out, float* saved, int64_t gsz, hipStream_t stream);
 bool spk_schnet_mol_bwd_eligible(const spk_schnet_t* m, const spk_graph_t* g, const spk_radial_t* rb);
+int spk_schnet_mol_bwd_records_mode();      // spk_schnet_mol_set_bwd_records()
 int spk_schnet_mol_backward(const spk_schnet_t* m, const spk_graph_t* g, const spk_radial_t* rb, const SpkPackTable& ptab,
                             const float* gx_out, const float* r_ij, const float* saved, int64_t gsz, float* gr, float* gx0,
                             hipStream_t stream);
@@ -218,6 +243,7 @@ extern "C" int spk_schnet_backward_f32(const spk_schnet_t* m, const spk_graph_t*
     const int64_t gsz_m = spk_cfconv_gsave_floats(g, rb, NF);
     if (gsz_m > 0) return spk_schnet_mol_backward(m, g, rb, ptab, gx_out, r_ij, saved, gsz_m, gr, gx0, stream);
   }
+  SPK_CHECK_ARG(spk_schnet_mol_bwd_records_mode() != 2, "%s: records mode 2, but `saved` of this model / list has no records region", who);
   // with saved filters the pair kernel runs and writes every entry of gr exactly once per interaction: the
   // first interaction of the backward assigns, the others accumulate -- no clearing pass
   const bool gr_assign = L > 0 && (m->reserved & 1) && E > 0 && spk_cfconv_gsave_floats(g, rb, NF) > 0 &&

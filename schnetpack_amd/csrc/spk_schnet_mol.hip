@@ -38,6 +38,12 @@
 
 bool spk_schnet_mol_bwd_eligible(const spk_schnet_t* m, const spk_graph_t* g, const spk_radial_t* rb);
 
+struct MolPair;
+// The records region of `saved` (spk_schnet_mol_records_region()): what ml_pair_records() of the forward computed, as the backward's
+// set-up wants it -- rec[p0 + r] = compacted record r of the group whose pair list starts at p0, map[p0 + s] = record of list
+// position s or -1, vec[3 (p0 + s)] = its pair vector, np[group] = number of records.  rec == null: no region.
+struct MolHandoff { MolPair* rec; float* vec; int* map; int* np; };
+
 struct MolLayerDev {
   const float* in2f_p;                  // packed forward image of in2f.weight [NF, F] (spk_pack_weight_f32)
   const float *w1, *b1, *w2, *b2;       // filter network, raw state_dict tensors
@@ -89,6 +95,7 @@ struct MolFwdArgs {
   int64_t gsz, N;
   RadialDev rb;
   int compact;              // drop the pairs beyond the cutoff from the tiles (lists with a skin); the backward does the same
+  MolHandoff ho;            // records region of `saved` (rec == null: none): written by the group set-up for the backward
   long long* dbg;           // tuning aid: cycle stamps, see spk_schnet_mol_set_debug_buffer (null in production)
 };
 #define ML_STAMP(n) do { if (a.dbg && blockIdx.x == 0 && threadIdx.x == 0) a.dbg[n] = (long long)__builtin_readcyclecounter(); } while (0)
@@ -122,17 +129,21 @@ __device__ __forceinline__ void ml_edge_vector(const float* __restrict__ rij, co
 __device__ __forceinline__ int ml_pair_records(MolPair* sP, short* sMap, int* sScan, const int32_t* __restrict__ half, const float* __restrict__ rij,
                                                const float* __restrict__ R, const float* __restrict__ offsets,
                                                const int64_t* __restrict__ idx_i, const int64_t* __restrict__ idx_j, int p0, int np, int a0,
-                                               float cutoff, bool compact, int tid, float* r_keep = nullptr) {
+                                               float cutoff, bool compact, int tid, float* r_keep = nullptr, const MolHandoff* ho = nullptr,
+                                               int grp = 0) {
   // r_keep (3 floats of the caller, or null): the vector of the pair at position `tid` of the list (np <= 512: one pair per thread)
+  // ho (or null): the records region of `saved` -- every thread also stores what it holds here for the backward (fire and forget)
   const int lane = tid & 63, wv = tid >> 6;
   MolPair pr;
   bool keep = false;
+  float vx = 0.f, vy = 0.f, vz = 0.f;
   if (r_keep) { r_keep[0] = 0.f; r_keep[1] = 0.f; r_keep[2] = 0.f; }
   if (tid < np) {
     const int64_t e = half[p0 + tid];
     float rx, ry, rz;
     ml_edge_vector(rij, R, offsets, idx_i, idx_j, e, rx, ry, rz);
     if (r_keep) { r_keep[0] = rx; r_keep[1] = ry; r_keep[2] = rz; }
+    vx = rx; vy = ry; vz = rz;
     pr.ij = (int)(idx_i[e] - a0) | ((int)(idx_j[e] - a0) << 8) | (tid << 16);
     pr.d = sqrtf(rx * rx + ry * ry + rz * rz);
     spk_cutoff_eval_fast(cutoff, pr.d, pr.fc, pr.dfc);
@@ -151,6 +162,15 @@ __device__ __forceinline__ int ml_pair_records(MolPair* sP, short* sMap, int* sS
   const int pos = off + __popcll(bal & ((1ull << lane) - 1ull));
   if (keep) sP[pos] = pr;
   if (sMap && tid < np) sMap[tid] = keep ? (short)pos : (short)-1;
+  if (ho) {
+    if (keep) ho->rec[p0 + pos] = pr;
+    if (tid < np) {
+      ho->map[p0 + tid] = keep ? pos : -1;
+      float* v = ho->vec + 3 * (size_t)(p0 + tid);
+      v[0] = vx; v[1] = vy; v[2] = vz;
+    }
+    if (tid == 0) ho->np[grp] = total;
+  }
   __syncthreads();
   return total;
 }
@@ -551,7 +571,9 @@ __global__ __launch_bounds__(512) void k_schnet_mol_fwd(MolFwdArgs a) {
       }
       *(f32x4*)(sX + row * ML_LD + 4 * c4) = v;
     }
-    const int np = ml_pair_records(sP, nullptr, sScan, a.half, a.rij, a.R, a.offsets, a.idx_i, a.idx_j, p0, np_list, a0, a.rb.cutoff, a.compact != 0, tid);
+    // (the records go to `saved` from the registers that hold them, before ml_fwd_pair() below rewrites sP in place)
+    const int np = ml_pair_records(sP, nullptr, sScan, a.half, a.rij, a.R, a.offsets, a.idx_i, a.idx_j, p0, np_list, a0, a.rb.cutoff, a.compact != 0, tid,
+                                   nullptr, a.ho.rec ? &a.ho : nullptr, grp);
     const int ntile = (np + 31) / 32;
     if constexpr (SP) {      // (each thread its own record; the barrier at the top of the first interaction publishes them)
       if (tid < np) sP[tid] = ml_fwd_pair(sP[tid]);
@@ -994,6 +1016,26 @@ extern "C" void spk_schnet_mol_set_debug_buffer(void* p) { g_mol_dbg = (long lon
 static int g_mol_bwd_task_split = 0;
 extern "C" void spk_schnet_mol_set_bwd_task_split(int split) { g_mol_bwd_task_split = (split == 1 || split == 2) ? split : 0; }
 
+// set-up of the backward: 0 = automatic (pair records from the records region of `saved` where the forward left one), 1 = always
+// recompute them (the chain half -> idx_i, idx_j -> R, the form before), 2 = require the region (an error where there is none).
+// The forward writes the region whenever it exists: 1 against 2 is an A/B of the backward alone.
+static int g_mol_bwd_records = 0;
+extern "C" void spk_schnet_mol_set_bwd_records(int mode) { g_mol_bwd_records = (mode == 1 || mode == 2) ? mode : 0; }
+int spk_schnet_mol_bwd_records_mode() { return g_mol_bwd_records; }
+// the region inside `saved` (spk_schnet.hip; one predicate for the sizing function and both launchers), as device pointers
+bool spk_schnet_mol_records_region(const spk_schnet_t* m, const spk_graph_t* g, const spk_radial_t* rb, int64_t* off, int64_t* floats);
+static MolHandoff mol_handoff(const spk_schnet_t* m, const spk_graph_t* g, const spk_radial_t* rb, int64_t gsz, const float* saved) {
+  MolHandoff h = {nullptr, nullptr, nullptr, nullptr};
+  int64_t off = 0, floats = 0;
+  if (gsz <= 0 || !spk_schnet_mol_records_region(m, g, rb, &off, &floats)) return h;
+  float* base = const_cast<float*>(saved) + off;       // 16-byte aligned: rec | vec | map | np
+  h.rec = (MolPair*)base;
+  h.vec = base + 4 * (int64_t)g->n_half;
+  h.map = (int*)(base + 7 * (int64_t)g->n_half);
+  h.np = (int*)(base + 8 * (int64_t)g->n_half);
+  return h;
+}
+
 static size_t mol_w1_floats(int kpb, bool sp) {      // LDS floats of the staged W1 image(s): MlW1Image<KPB>::BYTES twice in the split form
   return sp ? (size_t)2 * (4096 + (kpb > 2 ? (kpb == 4 ? 4096 : 2048) : 0)) / 4 : (size_t)128 * kpb * 8;
 }
@@ -1042,7 +1084,10 @@ static int launch_mol_fwd_sp(const MolFwdArgs& a, hipStream_t stream) {
   return SPK_OK;
 }
 
-// `saved` as laid out by spk_schnet_saved_floats_graph(): L x (h | pre3), then L x gsz floats of raw filter outputs.
+// `saved` as laid out by spk_schnet_saved_floats_graph(): L x (h | pre3), then L x gsz floats of raw filter outputs, then (lists the
+// pair kernels would compact) the space of the per-call pair list, which these launches leave alone, then -- model word bit 1, lists
+// the molecule-resident backward covers -- the records region: per record of a group its MolPair, per list position the pair vector
+// and the record index, per group the number of records (MolHandoff; spk_schnet_mol_records_region()).
 int spk_schnet_mol_forward_ex(const spk_schnet_t* m, const spk_graph_t* g, const spk_radial_t* rb, const SpkPackTable& ptab,
                               const float* x0, const float* r_ij, const float* R, const float* offsets, const MolHeadDev* head, float* x_out,
                               float* saved, int64_t gsz, hipStream_t stream, const float* emb = nullptr, const int64_t* Z = nullptr, int n_types = 0);
@@ -1075,6 +1120,7 @@ int spk_schnet_mol_forward_ex(const spk_schnet_t* m, const spk_graph_t* g, const
   a.gbase = saved + (int64_t)m->n_interactions * g->n_atoms * (m->n_filters + m->n_atom_basis);
   a.rb = spk_radial_dev(rb);
   a.compact = spk_schnet_mol_bwd_eligible(m, g, rb) ? 1 : 0;     // only when the molecule-resident backward (which compacts too) will consume `saved`
+  a.ho = mol_handoff(m, g, rb, gsz, saved);
   a.dbg = g_mol_dbg;
   switch ((rb->n_rbf + 7) / 8) {
     case 1: return launch_mol_fwd<1>(a, stream);
@@ -1129,10 +1175,13 @@ struct MolBwdArgs {
   RadialDev rb;
   int compact;              // as in the forward
   int task_split;           // derivative tasks per pair tile in phase E: 0 = automatic, 1, 2 (spk_schnet_mol_set_bwd_task_split)
+  MolHandoff ho;            // records region of `saved` as the forward of this call left it (rec == null: recompute the records)
   long long* dbg;
 };
 
-template <int KPB, bool SP>
+// HO: the pair records of a group come from the records region of `saved` (a.ho); the instances without it carry the recomputing
+// set-up alone (both in one kernel cost the split instances 48 B per lane of scratch: profiles/r11_mol_bwd_setup.md)
+template <int KPB, bool SP, bool HO>
 __global__ __launch_bounds__(512) void k_schnet_mol_bwd(MolBwdArgs a) {
   constexpr int NF = 128, NT = 4, KB2 = 16;
   constexpr int W1F = SP ? 2 * MlW1Image<KPB>::BYTES / 4 : NF * KPB * 8;     // floats of the W1 image(s)
@@ -1180,6 +1229,10 @@ __global__ __launch_bounds__(512) void k_schnet_mol_bwd(MolBwdArgs a) {
     //      filter weights of the top interaction are staged by the idle half of the two Dense phases below -- the derivative tasks
     //      of phase E are their first reader.
     const bool with_head = a.head.w1t != nullptr;
+    constexpr bool handoff = HO;
+    MolPair ho_pr = {0, 0.f, 0.f, 0.f};
+    int ho_map = -1, ho_np = 0;
+    float pr3[3] = {0.f, 0.f, 0.f};      // this thread's pair vector: used again at the very end (dL/dr, dL/dR) without going back to memory
     for (int s = tid; s < 32 * 32; s += 512) {
       const int row = s >> 5, c4 = s & 31;
       f32x4 v = {0.f, 0.f, 0.f, 0.f};
@@ -1189,6 +1242,21 @@ __global__ __launch_bounds__(512) void k_schnet_mol_bwd(MolBwdArgs a) {
       if (!with_head) *(f32x4*)(sGh + row * ML_LD + 4 * c4) = f32x4{0.f, 0.f, 0.f, 0.f};
     }
     ML_STAMP(120);
+    // With the records region of `saved` (written by the forward of this call: ml_pair_records() there) a thread requests its
+    // record, its map entry and its pair vector here, in one round of independent loads in front of those of the head: no chain
+    // half -> idx_i, idx_j -> R, no distance, no cutoff function, no ballot / prefix -- and one barrier, not two.  (Requested at the
+    // top of the group instead, in front of the feature gradient, the set-up is as long: profiles/r11_mol_bwd_setup.md)
+    if constexpr (handoff) {
+      ho_np = a.ho.np[grp];
+      ho_np = ho_np < 0 ? 0 : (ho_np > np_list ? np_list : ho_np);      // (never beyond the group's span of the region)
+      if (tid < np_list) {
+        ho_map = ml_ld<int>(a.ho.map + p0, (unsigned)tid * 4u);
+        pr3[0] = ml_ld<float>(a.ho.vec + 3 * (size_t)p0, (unsigned)tid * 12u);
+        pr3[1] = ml_ld<float>(a.ho.vec + 3 * (size_t)p0, (unsigned)tid * 12u + 4u);
+        pr3[2] = ml_ld<float>(a.ho.vec + 3 * (size_t)p0, (unsigned)tid * 12u + 8u);
+      }
+      if (tid < ho_np) ho_pr = ml_ld<MolPair>(a.ho.rec + p0, (unsigned)tid * 16u);
+    }
     if (with_head) {
       // ---- dL/dx_L through the energy head, part 1: the hidden gradient gE[mol] w2 . act'(pre_h) -> sGh[:, :H]
       //      (the columns beyond H are not read by part 2, and the first Dense phase rewrites sGh in full)
@@ -1205,8 +1273,15 @@ __global__ __launch_bounds__(512) void k_schnet_mol_bwd(MolBwdArgs a) {
         sGh[row * ML_LD + k] = v;
       }
     }
-    float pr3[3];             // this thread's pair vector: used again at the very end (dL/dr, dL/dR) without going back to memory
-    const int np = ml_pair_records(sP, sMap, sScan, a.half, a.rij, a.R, a.offsets, a.idx_i, a.idx_j, p0, np_list, a0, a.rb.cutoff, a.compact != 0, tid, pr3);
+    int np;
+    if constexpr (handoff) {
+      if (tid < np_list) sMap[tid] = (short)ho_map;
+      if (tid < ho_np) sP[tid] = ho_pr;
+      __syncthreads();        // publishes the records and the head's hidden gradient
+      np = ho_np;
+    } else {
+      np = ml_pair_records(sP, sMap, sScan, a.half, a.rij, a.R, a.offsets, a.idx_i, a.idx_j, p0, np_list, a0, a.rb.cutoff, a.compact != 0, tid, pr3);
+    }
     const int ntile = (np + 31) / 32;
     ML_STAMP(123);
     if (wv < NT) {
@@ -1671,16 +1746,17 @@ static size_t mol_bwd_lds(int kpb, bool sp) {
          (2 * ML_MAXEDGES + 36 + 4 + 8) * sizeof(int) + ML_MAXPAIRS * sizeof(short);
 }
 
-template <int KPB, bool SP>
+template <int KPB, bool SP, bool HO>
 static int launch_mol_bwd_sp(const MolBwdArgs& a, hipStream_t stream);
 template <int KPB>
 static int launch_mol_bwd(const MolBwdArgs& a, hipStream_t stream) {
-  return spk_get_split() ? launch_mol_bwd_sp<KPB, true>(a, stream) : launch_mol_bwd_sp<KPB, false>(a, stream);
+  if (a.ho.rec) return spk_get_split() ? launch_mol_bwd_sp<KPB, true, true>(a, stream) : launch_mol_bwd_sp<KPB, false, true>(a, stream);
+  return spk_get_split() ? launch_mol_bwd_sp<KPB, true, false>(a, stream) : launch_mol_bwd_sp<KPB, false, false>(a, stream);
 }
-template <int KPB, bool SP>
+template <int KPB, bool SP, bool HO>
 static int launch_mol_bwd_sp(const MolBwdArgs& a, hipStream_t stream) {
   const size_t lds = mol_bwd_lds(KPB, SP);
-  auto kern = k_schnet_mol_bwd<KPB, SP>;
+  auto kern = k_schnet_mol_bwd<KPB, SP, HO>;
   static SpkPerDevice attr_set;
   int attr_dev;
   if (attr_set.pending(&attr_dev)) {
@@ -1735,6 +1811,9 @@ int spk_schnet_mol_backward_ex(const spk_schnet_t* m, const spk_graph_t* g, cons
   a.compact = 1;
   a.dbg = g_mol_dbg;
   a.task_split = g_mol_bwd_task_split;
+  a.ho = mol_handoff(m, g, rb, gsz, saved);
+  SPK_CHECK_ARG(g_mol_bwd_records != 2 || a.ho.rec, "spk_schnet_mol_backward: records mode 2, but `saved` of this model / list has no records region");
+  if (g_mol_bwd_records == 1) a.ho.rec = nullptr;
   switch ((rb->n_rbf + 7) / 8) {
     case 1: return launch_mol_bwd<1>(a, stream);
     case 2: return launch_mol_bwd<2>(a, stream);

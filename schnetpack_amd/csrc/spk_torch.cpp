@@ -606,7 +606,7 @@ std::tuple<Tensor, Tensor, Tensor> schnet_forward_raw(const Tensor& x0_in, const
   decide_filter(*plan, r, cutoff);
   auto M = get_schnet(ws, F, n_filters);
   spk_schnet_t m = M->m;            // per-call copy: the cached block is never mutated
-  m.reserved = save_filters ? 1 : 0;
+  m.reserved = save_filters ? 3 : 0;      // filters saved; `saved` sized with the records region of the molecule-resident launches
   spk_graph_t g = plan->graph();
   spk_radial_t rb = radial_of(rbf_kind, p0, p1, cutoff);
   const int64_t n_saved = save_filters ? spk_schnet_saved_floats_graph(&m, &g, &rb) : spk_schnet_saved_floats(&m, N);
@@ -627,7 +627,7 @@ std::tuple<Tensor, Tensor> schnet_backward_raw(const Tensor& gx_in, const Tensor
   c10::DeviceGuard guard(gx.device());
   auto M = get_schnet(ws, F, n_filters);
   spk_schnet_t m = M->m;
-  m.reserved = saved_filters ? 1 : 0;
+  m.reserved = saved_filters ? 3 : 0;
   spk_graph_t g = plan.graph();
   spk_radial_t rb = radial_of(rbf_kind, p0, p1, cutoff);
   Tensor scratch = scratch_in;
@@ -778,7 +778,7 @@ PotentialCall potential_setup(const char* who, bool painn, const Tensor& R, cons
   } else {
     c.S = get_schnet(ws, F, n_filters);
     c.m = c.S->m;
-    c.m.reserved = 1;                              // SchNet model word: the forward keeps the raw filter outputs for the backward
+    c.m.reserved = 3;                              // SchNet model word: the forward keeps the raw filter outputs and the pair records for the backward
   }
   c.H = get_head(head[0], head[1], head[2], head[3]);
   c.p0 = f32(p0_in, who);

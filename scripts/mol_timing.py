@@ -1,6 +1,6 @@
 """Phase timing of the molecule-resident SchNet kernels (cycle stamps of thread 0 / workgroup 0).
 
-    python scripts/mol_timing.py [frames [bwd task split: 0 = automatic, 1, 2]]"""
+    python scripts/mol_timing.py [frames [bwd task split: 0 = automatic, 1, 2 [bwd pair records: 0 = automatic, 1 = recomputed, 2 = from `saved`]]]"""
 import ctypes, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT)
 import torch
@@ -12,6 +12,7 @@ m = M.build_model("schnet").to(dev).eval()
 inp = M.batch_to_inputs(b, dev)
 L = _lib.lib()
 L.spk_schnet_mol_set_bwd_task_split(int(sys.argv[2]) if len(sys.argv) > 2 else 0)
+L.spk_schnet_mol_set_bwd_records(int(sys.argv[3]) if len(sys.argv) > 3 else 0)
 dbg = torch.zeros(128 + 4 * 1024, dtype=torch.int64, device=dev)
 for rep in range(3):
     dbg.zero_()
