@@ -344,6 +344,11 @@ __device__ __forceinline__ void ml_dense_load(f32x4 (&av)[16], const float* __re
 // (B operands are requested four k-blocks ahead of their MFMAs and pinned there: left alone the compiler issues every ds_read
 //  right in front of the four MFMAs that need it and the matrix pipe waits ~100 cycles per group -- round 3, found on spk_painn_mol.hip)
 #define ML_PIN() asm volatile("" ::: "memory")
+// The pin keeps the LOADS where they are written, not the matrix instructions: in the split chains whose operands all come from LDS
+// the scheduler moved every k-step up to its reads ("ds_read x 4, wait, three matrix instructions") and the distance was gone.  The
+// fence stops the scheduler as well.  Decided chain by chain, not in ML_PIN(): a fence costs registers -- on all pins of this file the
+// split forward goes from 68 to 252 B per lane of scratch (profiles/r12_mol_matrix_overlap.md).
+#define ML_FENCE() do { ML_PIN(); __builtin_amdgcn_sched_barrier(0); } while (0)
 // Split form of a Dense block (SP; spk_split.h): `av` then holds chunks of the SPLIT weight image (k_pack_weight_split: chunk 2 s = the high
 // parts of k-step s, chunk 2 s + 1 its low parts -- same bytes, same offsets as the fp32 image), the activations are read from LDS
 // as eight consecutive fp32 values per k-step and split in registers; three f16 instructions per 16 k instead of eight f32 ones.
@@ -686,7 +691,10 @@ __global__ __launch_bounds__(512) void k_schnet_mol_fwd(MolFwdArgs a) {
 #pragma unroll
           for (int r = 0; r < 16; ++r) g[r] = bias2;
           if constexpr (SP) {
-            // A = hidden tile (rows = pairs) from LDS, B = W2 image (columns = channels): both split, requested two k-steps ahead
+            // A = hidden tile (rows = pairs) from LDS, B = W2 image (columns = channels): both split, requested ONE k-step ahead and
+            // fenced there -- the four reads of step s + 1 fly under the three matrix instructions of step s.  (Two and three steps
+            // ahead keep 16 / 32 registers more in flight and gained half as much / nothing: profiles/r12_mol_matrix_overlap.md)
+            constexpr int AHEAD = 1;
             f32x16 gx;
 #pragma unroll
             for (int r = 0; r < 16; ++r) gx[r] = 0.f;
@@ -695,17 +703,17 @@ __global__ __launch_bounds__(512) void k_schnet_mol_fwd(MolFwdArgs a) {
             const char* zr = (const char*)zbuf + el * (ML_LD * 4) + 16 * hi;
             h16x8 zh[8], zl[8], wh[8], wl[8];
 #pragma unroll
-            for (int s = 0; s < 2; ++s) {
+            for (int s = 0; s < AHEAD; ++s) {
               zh[s] = *(const h16x8*)(zr + 32 * s); zl[s] = *(const h16x8*)(zr + 256 + 32 * s);
               wh[s] = wbh[s * 64]; wl[s] = wbl[s * 64];
             }
-            ML_PIN();
+            ML_FENCE();
 #pragma unroll
             for (int s = 0; s < 8; ++s) {
-              if (s + 2 < 8) {
-                zh[s + 2] = *(const h16x8*)(zr + 32 * (s + 2)); zl[s + 2] = *(const h16x8*)(zr + 256 + 32 * (s + 2));
-                wh[s + 2] = wbh[(s + 2) * 64]; wl[s + 2] = wbl[(s + 2) * 64];
-                ML_PIN();
+              if (s + AHEAD < 8) {
+                zh[s + AHEAD] = *(const h16x8*)(zr + 32 * (s + AHEAD)); zl[s + AHEAD] = *(const h16x8*)(zr + 256 + 32 * (s + AHEAD));
+                wh[s + AHEAD] = wbh[(s + AHEAD) * 64]; wl[s + AHEAD] = wbl[(s + AHEAD) * 64];
+                ML_FENCE();
               }
               SP_STEP(zh[s], zl[s], wh[s], wl[s], g, gx);
             }
@@ -1533,10 +1541,10 @@ __global__ __launch_bounds__(512) void k_schnet_mol_bwd(MolBwdArgs a) {
               h16x8 wh[8], wl[8];
 #pragma unroll
               for (int s = 0; s < 2; ++s) { wh[s] = wbh[s * 64]; wl[s] = wbl[s * 64]; }
-              ML_PIN();
+              ML_FENCE();      // (fenced: with the pin alone every k-step waited for reads issued directly in front of it)
 #pragma unroll
               for (int s = 0; s < 8; ++s) {
-                if (s + 2 < 8) { wh[s + 2] = wbh[(s + 2) * 64]; wl[s + 2] = wbl[(s + 2) * 64]; ML_PIN(); }
+                if (s + 2 < 8) { wh[s + 2] = wbh[(s + 2) * 64]; wl[s + 2] = wbl[(s + 2) * 64]; ML_FENCE(); }
                 SP_STEP(wh[s], wl[s], zph[s >> 1][s & 1], zpl[s >> 1][s & 1], gp, gpx);
               }
               SP_FOLD(gp, gpx);
