@@ -256,6 +256,45 @@ int spk_zbl_bwd_f32(const float* gE, const float* r_ij, const int64_t* Z, const 
 int spk_zbl_forces_f32(const float* R, const float* offsets, const int64_t* Z, const spk_graph_t* g, const int64_t* idx_m, int64_t n_mol,
                        const float* params, float* E_zbl, float* F, float* W, void* workspace, void* stream);
 
+/* ------------------------------------------------------------------ atomistic/electrostatic.py:14-152, :266-308 (CoulombPotential,
+ * DampedCoulombPotential, EnergyCoulomb, the real-space part of EnergyEwald)
+ *   phi_i = sum_{j in row i} q_j v(d_ij),  E_atom[i] = 1/2 ke q_i phi_i,  E[m] = sum_{i in m} E_atom[i]
+ * params: 8 floats in DEVICE memory -- ke, kind, rc (0: no cutoff), shift, switch_on, switch_off, alpha, screened (0 / 1).
+ *   kind 0: chi = 1/d;  kind 1: chi = s(d)/sqrt(d^2 + 1) + (1 - s(d))/d;  kind 2: chi = erfc(sqrt(alpha) d)/d (times 1 - s(d) when screened)
+ * with s the switch function between switch_on and switch_off.  rc > 0 (kinds 0, 1): v = (chi - shift)^2 / chi for d <= rc, exactly 0 beyond;
+ * else v = chi.  q [N]; pairs with q_i q_j = 0 contribute exact zeros (also at d = 0); a pair at d = 0 with charges gives inf / NaN like the
+ * reference.  Indices outside the atoms are clamped for the read.  idx_m ascending.  No float atomics on lists sorted by idx_i.
+ * workspace: spk_coulomb_workspace_bytes(g, n_mol) bytes.
+ * spk_coulomb_fwd_f32: E [n_mol], E_atom [N] and phi [N] (all overwritten; phi is what the backward reads).
+ * spk_coulomb_bwd_f32: gr [E, 3] = gE[idx_m[idx_i[e]]] 1/2 ke q_i q_j v'(d_e) r_e / d_e (lands on the atoms through spk_pairwise_bwd_graph_f32
+ * and on the virial through spk_edge_virial_f32) and, if gq != NULL, gq [N] = dE/dq: gE[m] ke phi_i on sorted symmetric lists, else the
+ * per-edge shares scattered over idx_i and idx_j by spk_scatter_add_f32.  gr must be given. */
+int64_t spk_coulomb_workspace_bytes(const spk_graph_t* g, int64_t n_mol);
+int spk_coulomb_fwd_f32(const float* r_ij, const float* q, const spk_graph_t* g, const int64_t* idx_m, int64_t n_mol, const float* params,
+                        float* E, float* E_atom, float* phi, void* workspace, void* stream);
+int spk_coulomb_bwd_f32(const float* gE, const float* r_ij, const float* q, const float* phi, const spk_graph_t* g, const int64_t* idx_m,
+                        int64_t n_mol, const float* params, float* gr, float* gq, void* workspace, void* stream);
+
+/* ------------------------------------------------------------------ atomistic/electrostatic.py:310-375 (EnergyEwald._reciprocal_space)
+ *   S(k) = sum_{i in m} q_i e^{i k r_i},  E_rec[m] = ke (2 pi / V sum_k g_k |S(k)|^2 - sqrt(alpha / pi) sum_i q_i^2),  g_k = exp(-k^2 / 4 alpha) / k^2
+ * with k = n 2 pi C^-T for the integer vectors n = kvecs [K, 3] (float32, DEVICE memory, |n_a| <= k_max <= spk_ewald_max_kmax() = 8).
+ * params: 2 floats in DEVICE memory, ke and alpha.  R [N, 3], q [N], cell [n_mol, 3, 3], idx_m [N] ascending.
+ * spk_ewald_recip_fwd_f32: E [n_mol] and coeffs [n_mol, K, 2] = g_k S(k) (re, im), which the backward reads.  A cell without volume gives
+ * NaN for that molecule (no host synchronisation, so no error).  workspace (both calls): spk_ewald_workspace_bytes(N, K, n_mol) bytes.
+ * spk_ewald_recip_bwd_f32: gR [N, 3] = gE[m] dE_rec/dr_i and gq [N] = gE[m] dE_rec/dq_i (either may be NULL).
+ * No float atomics: the same input gives the same bits on every call.  spk_ewald_atom_tile / _slab: atoms staged at a time / per block of
+ * the structure-factor kernel (molecules larger than a slab are summed over slabs in a fixed order). */
+int32_t spk_ewald_max_kmax(void);
+int32_t spk_ewald_atom_tile(void);
+int32_t spk_ewald_atom_slab(void);
+int64_t spk_ewald_workspace_bytes(int64_t n_atoms, int64_t n_kvecs, int64_t n_mol);
+int spk_ewald_recip_fwd_f32(const float* R, const float* q, const float* cell, const int64_t* idx_m, int64_t n_atoms, int64_t n_mol,
+                            const float* kvecs, int64_t n_kvecs, int32_t k_max, const float* params, float* E, float* coeffs, void* workspace,
+                            void* stream);
+int spk_ewald_recip_bwd_f32(const float* gE, const float* R, const float* q, const float* cell, const int64_t* idx_m, int64_t n_atoms,
+                            int64_t n_mol, const float* kvecs, int64_t n_kvecs, int32_t k_max, const float* params, const float* coeffs,
+                            float* gR, float* gq, void* workspace, void* stream);
+
 /* ------------------------------------------------------------------ atomistic/atomwise.py:91-293 (DipoleMoment, Polarizability),
  * nn/equivariant.py:11-71 (GatedEquivariantBlock), nn/blocks.py:79-156 (build_gated_equivariant_mlp)
  * spk_gated_mlp_fwd_f32: the whole gated equivariant MLP of a head, build_gated_equivariant_mlp(n_in, n_out = 1, n_hidden = None,

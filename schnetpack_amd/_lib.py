@@ -157,6 +157,15 @@ _PROTOS = {
     "spk_zbl_fwd_f32": (ctypes.c_int, [c_f, c_f, P(GraphT), c_f, c_i64, c_f, c_f, c_f, c_f, c_f]),
     "spk_zbl_bwd_f32": (ctypes.c_int, [c_f, c_f, c_f, P(GraphT), c_f, c_i64, c_f, c_f, c_f]),
     "spk_zbl_forces_f32": (ctypes.c_int, [c_f, c_f, c_f, P(GraphT), c_f, c_i64, c_f, c_f, c_f, c_f, c_f, c_f]),
+    "spk_coulomb_workspace_bytes": (c_i64, [P(GraphT), c_i64]),
+    "spk_coulomb_fwd_f32": (ctypes.c_int, [c_f, c_f, P(GraphT), c_f, c_i64, c_f, c_f, c_f, c_f, c_f, c_f]),
+    "spk_coulomb_bwd_f32": (ctypes.c_int, [c_f, c_f, c_f, c_f, P(GraphT), c_f, c_i64, c_f, c_f, c_f, c_f, c_f]),
+    "spk_ewald_max_kmax": (c_i32, []),
+    "spk_ewald_atom_tile": (c_i32, []),
+    "spk_ewald_atom_slab": (c_i32, []),
+    "spk_ewald_workspace_bytes": (c_i64, [c_i64, c_i64, c_i64]),
+    "spk_ewald_recip_fwd_f32": (ctypes.c_int, [c_f, c_f, c_f, c_f, c_i64, c_i64, c_f, c_i64, c_i32, c_f, c_f, c_f, c_f, c_f]),
+    "spk_ewald_recip_bwd_f32": (ctypes.c_int, [c_f, c_f, c_f, c_f, c_f, c_i64, c_i64, c_f, c_i64, c_i32, c_f, c_f, c_f, c_f, c_f, c_f]),
     "spk_gated_mlp_supported": (ctypes.c_int, [c_i32, c_i32, c_i32]),
     "spk_gated_mlp_fwd_f32": (ctypes.c_int, [c_f, c_f, c_i64, c_i32, c_i32, c_i32, P(ctypes.c_void_p), c_f, c_f, c_f]),
     "spk_moment_reduce_f32": (ctypes.c_int, [c_i32, c_f, c_f, c_f, c_f, c_i64, c_i64, c_f, c_i32, c_f, c_f, c_f]),

@@ -6,7 +6,10 @@ reference's own modules run unchanged on top of the HIP classes (tests/test_gpu_
 ``Atomwise`` for its one-kernel energy head.  ``ZBLRepulsionEnergy`` (atomistic/nuclear_repulsion.py:13-108) and ``Aggregation``
 (atomistic/aggregation.py:9-28) add the short-range nuclear repulsion production potentials carry next to the learned energy.
 ``DipoleMoment`` and ``Polarizability`` (atomistic/atomwise.py:91-293) are the tensorial heads on PaiNN's vector representation.
+``FilterShortRange`` (atomistic/distances.py:29-57), ``CoulombPotential``, ``DampedCoulombPotential``, ``EnergyCoulomb`` and ``EnergyEwald``
+(atomistic/electrostatic.py) are the point-charge electrostatics that consume the partial charges.
 """
+import math
 from typing import Callable, Dict, Final, List, Optional, Sequence, Union
 
 import torch
@@ -16,11 +19,12 @@ import torch.nn.functional as F
 from . import _lib, properties
 from . import units as spk_units
 from . import torchops  # noqa: F401  (registers torch.ops.spk_hip)
-from .nn import CosineCutoff, Dense, GatedEquivariantBlock, build_gated_equivariant_mlp, build_mlp, scatter_add
+from .nn import CosineCutoff, Dense, GatedEquivariantBlock, SwitchFunction, build_gated_equivariant_mlp, build_mlp, scatter_add
 from .nn.base import activation_id
 from .nn.fallback import note_fallback, use_aten
 
-__all__ = ["Strain", "PairwiseDistances", "Atomwise", "Forces", "ZBLRepulsionEnergy", "Aggregation", "DipoleMoment", "Polarizability"]
+__all__ = ["Strain", "PairwiseDistances", "Atomwise", "Forces", "ZBLRepulsionEnergy", "Aggregation", "DipoleMoment", "Polarizability",
+           "FilterShortRange", "CoulombPotential", "DampedCoulombPotential", "EnergyCoulomb", "EnergyEwald", "EnergyEwaldError"]
 
 
 class Strain(nn.Module):
@@ -402,11 +406,19 @@ class DipoleMoment(nn.Module):
     raises.  Training mode, float64, host tensors and heads without a fused kernel (any ``n_hidden`` / ``n_layers`` but the default two pyramidal
     layers of width 64 or 128, other activations) run the reference's formula on the ``Dense`` / ``scatter_add`` mirrors -- the route with parameter
     gradients and derivatives w.r.t. the positions.  A molecule without atoms gets a zero moment on both routes (the reference's 0 / 0 correction of
-    such a molecule is never gathered by an atom).  ``_n_atoms`` is read on the ATen route only, and counted from ``idx_m`` when absent."""
+    such a molecule is never gathered by an atom).  ``_n_atoms`` is read on the ATen route only, and counted from ``idx_m`` when absent.
+
+    When a later ``EnergyCoulomb`` / ``EnergyEwald`` of the model reads ``charges_key``, ``NeuralNetworkPotential`` sets ``_charges_differentiable``: with
+    autograd enabled the head then runs that differentiable route in eval mode as well (no ``eval_guard``), so ``Forces`` of the electrostatic energy
+    includes the dq/dR term; under ``torch.no_grad()`` it keeps the two fused launches."""
 
     use_vector_representation: Final[bool]
     _gated_act: Final[int]
     _scalar_act: Final[int]
+    #: set by ``NeuralNetworkPotential`` (and by ``install()``'s hook on the reference's model) when a later ``EnergyCoulomb`` / ``EnergyEwald`` reads
+    #: ``charges_key``: with autograd enabled the head then runs its differentiable ``outnet`` route in eval mode too, so that ``Forces`` of the
+    #: electrostatic energy gets the dq/dR term.  False (the default): the two fused launches, outputs behind ``eval_guard``.
+    _charges_differentiable: bool
 
     def __init__(self, n_in: int, n_hidden: Optional[Union[int, Sequence[int]]] = None, n_layers: int = 2, activation: Callable = F.silu,
                  predict_magnitude: bool = False, return_charges: bool = False, dipole_key: str = properties.dipole_moment,
@@ -428,6 +440,7 @@ class DipoleMoment(nn.Module):
         else:
             self.outnet = build_mlp(n_in=n_in, n_out=1, n_hidden=n_hidden, n_layers=n_layers, activation=activation)
         self.n_molecules_key = n_molecules_key
+        self._charges_differentiable = False
         self._init_operator()
 
     def _init_operator(self):
@@ -441,6 +454,8 @@ class DipoleMoment(nn.Module):
             self.n_molecules_key = "_n_molecules"
         if "_gated_act" not in self.__dict__ or "_scalar_act" not in self.__dict__:
             self._init_operator()
+        if "_charges_differentiable" not in self.__dict__:
+            self._charges_differentiable = False
 
     def _n_molecules(self, inputs: Dict[str, torch.Tensor], idx_m: torch.Tensor) -> int:
         # like Atomwise: a host-side molecule count in the batch avoids the reference's int(idx_m[-1]) + 1 (a device sync)
@@ -467,6 +482,8 @@ class DipoleMoment(nn.Module):
         if properties.total_charge in inputs:
             total = inputs[properties.total_charge]
         device_ok = not self.training and l0.dim() == 2 and not use_aten(l0) and not use_aten(positions)
+        if self._charges_differentiable and torch.is_grad_enabled():      # an electrostatic term differentiates the charges it reads
+            device_ok = False
         if self.use_vector_representation:
             l1 = inputs["vector_representation"]
             if self._gated_act > 0 and device_ok and l1.dim() == 3:
@@ -605,3 +622,374 @@ class Polarizability(nn.Module):
         alpha = scatter_add(alpha, idx_m, dim_size=maxm)
         inputs[self.polarizability_key] = alpha
         return inputs
+
+
+class FilterShortRange(nn.Module):
+    """Separate the short-range pairs from all supplied pairs (atomistic/distances.py:29-57): the full list moves to the long-range keys
+    (``_Rij_lr``, ``_idx_i_lr``, ``_idx_j_lr``) and the pairs with ``d <= short_range_cutoff`` stay under the original keys.  The reference's formula
+    on ATen (a compaction with a data-dependent size: plumbing, not a hot path)."""
+
+    def __init__(self, short_range_cutoff: float):
+        super().__init__()
+        self.short_range_cutoff = short_range_cutoff
+
+    def forward(self, inputs: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+        idx_i = inputs[properties.idx_i]
+        idx_j = inputs[properties.idx_j]
+        Rij = inputs[properties.Rij]
+        rij = torch.norm(Rij, dim=-1)
+        cidx = torch.nonzero(rij <= self.short_range_cutoff).squeeze(-1)
+        inputs[properties.Rij_lr] = Rij
+        inputs[properties.idx_i_lr] = idx_i
+        inputs[properties.idx_j_lr] = idx_j
+        inputs[properties.Rij] = Rij[cidx]
+        inputs[properties.idx_i] = idx_i[cidx]
+        inputs[properties.idx_j] = idx_j[cidx]
+        return inputs
+
+
+class CoulombPotential(nn.Module):
+    """1 / d (atomistic/electrostatic.py:14-23)."""
+
+    def forward(self, d_ij: torch.Tensor) -> torch.Tensor:
+        return 1.0 / d_ij
+
+
+class DampedCoulombPotential(nn.Module):
+    """PhysNet's damped Coulomb potential ``s(d) / sqrt(d^2 + 1) + (1 - s(d)) / d`` (atomistic/electrostatic.py:26-57)."""
+
+    def __init__(self, switch_fn: nn.Module):
+        super().__init__()
+        self.switch_fn = switch_fn
+
+    def forward(self, d_ij: torch.Tensor) -> torch.Tensor:
+        potential = 1.0 / d_ij
+        damped = 1.0 / torch.sqrt(d_ij ** 2 + 1)
+        f_switch = self.switch_fn(d_ij)
+        return f_switch * damped + (1 - f_switch) * potential
+
+
+class EnergyEwaldError(Exception):
+    pass
+
+
+def _pair_kind(potential) -> int:
+    """Pair function of csrc/spk_coulomb.hip for a potential module: 0 the mirror ``CoulombPotential``, 1 the mirror ``DampedCoulombPotential``
+    around the mirror ``SwitchFunction``, -1 anything else (ATen route)."""
+    if type(potential) is CoulombPotential:
+        return 0
+    if type(potential) is DampedCoulombPotential and type(potential.switch_fn) is SwitchFunction:
+        return 1
+    return -1
+
+
+class EnergyCoulomb(nn.Module):
+    """Coulomb energy of point charges by direct summation over a neighbour list (atomistic/electrostatic.py:60-152):
+    ``E = 1/2 ke sum_pairs q_i q_j chi(d_ij)``; with ``cutoff`` the potential is shifted (``chi + shift^2 / chi - 2 shift`` for ``d <= cutoff``, zero
+    beyond) so that it and its slope vanish at the cutoff.  Constructor, attributes and buffers (``ke`` [1], 0-dim ``cutoff`` and ``shift``) are
+    the reference's, so its ``state_dict``s and pickles load.
+
+    In eval mode, on float32 device tensors and with ``coulomb_potential`` the mirror ``CoulombPotential`` or the mirror ``DampedCoulombPotential``
+    around the mirror ``SwitchFunction``, the energy is ONE operator, ``torch.ops.spk_hip.coulomb`` (csrc/spk_coulomb.hip), whose backward returns
+    dE/dr_ij and dE/dq -- what ``Forces`` asks for, also through predicted charges.  Everything else runs the reference's formula on ATen, on
+    whatever device the tensors are on (``note_fallback()``): training mode (second order for ``Forces(create_graph=True)``), float64, host tensors,
+    any other potential callable.
+
+    The operator reads 8 floats from a device buffer that ``op_params()`` -- host code, run by every eager call -- rewrites IN PLACE when ``ke``,
+    ``cutoff``, ``shift`` or the switch radii have changed, so a captured HIP graph replays with the new values after one eager call.  Under
+    TorchScript the floats are those the module had when it was scripted.  A host-side molecule count under ``_n_molecules`` in the batch avoids
+    the reference's ``int(idx_m[-1]) + 1`` (a device sync)."""
+
+    _kind: Final[int]
+    use_neighbors_lr: Final[bool]
+
+    def __init__(self, energy_unit: Union[str, float], position_unit: Union[str, float], coulomb_potential: nn.Module, output_key: str,
+                 charges_key: str = properties.partial_charges, use_neighbors_lr: bool = True, cutoff: Optional[float] = None,
+                 n_molecules_key: str = "_n_molecules"):
+        super().__init__()
+        ke = spk_units.convert_units("Ha", energy_unit) * spk_units.convert_units("Bohr", position_unit)
+        self.register_buffer("ke", torch.Tensor([ke]))
+        self.coulomb_potential = coulomb_potential
+        self.charges_key = charges_key
+        self.output_key = output_key
+        self.model_outputs = [output_key]
+        self.use_neighbors_lr = use_neighbors_lr
+        if cutoff is not None:
+            cutoff = torch.tensor(cutoff)
+            shift = self.coulomb_potential(cutoff).detach()
+            self.register_buffer("cutoff", cutoff)
+            self.register_buffer("shift", shift)
+        else:
+            self.cutoff = None
+            self.shift = None
+        self.n_molecules_key = n_molecules_key
+        self._init_operator()
+
+    def _init_operator(self):
+        self._kind = _pair_kind(self.coulomb_potential)
+        self.register_buffer("_op_params", torch.zeros(8), persistent=False)
+        self._op_key = None
+        self._read_host()
+
+    def _read_host(self):
+        """Host copies of the buffers (read when they change, not per call)."""
+        self._ke_host = float(self.ke.reshape(-1)[0])
+        self._rc_host = float(self.cutoff) if self.cutoff is not None else 0.0
+        self._shift_host = float(self.shift) if self.shift is not None else 0.0
+        self._on_host, self._off_host = 0.0, 1.0
+        if self._kind == 1:
+            self._on_host, self._off_host = self.coulomb_potential.switch_fn.switch_values()
+
+    def __setstate__(self, state):
+        # a pickle made by the REFERENCE class unpickled onto this one after install() never ran __init__
+        super().__setstate__(state)
+        if "n_molecules_key" not in self.__dict__:
+            self.n_molecules_key = "_n_molecules"
+        if "_kind" not in self.__dict__ or "_op_params" not in self._buffers:
+            self._init_operator()
+
+    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
+        super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
+        if not self.ke.is_meta:
+            self._read_host()
+            on = state_dict.get(prefix + "coulomb_potential.switch_fn.switch_on")      # (children load after this module)
+            off = state_dict.get(prefix + "coulomb_potential.switch_fn.switch_off")
+            if self._kind == 1 and on is not None and off is not None and not on.is_meta:
+                self._on_host, self._off_host = float(on.reshape(-1)[0]), float(off.reshape(-1)[0])
+            self._op_key = None
+
+    def _params8(self, like: torch.Tensor) -> torch.Tensor:
+        """ke, kind, cutoff (0: none), shift, switch_on, switch_off, 0, 0 as float32 on the device of ``like``."""
+        return torch.tensor([self._ke_host, float(self._kind), self._rc_host, self._shift_host, self._on_host, self._off_host, 0.0, 0.0],
+                            dtype=torch.float32, device=like.device)
+
+    @torch.jit.unused
+    def op_params(self, like: torch.Tensor) -> torch.Tensor:
+        """The operator's parameter buffer, rewritten (in place: captured graphs keep pointing at it) only when a buffer or a switch radius has
+        changed since the last call."""
+        bufs = [self.ke] + ([self.cutoff, self.shift] if self.cutoff is not None else [])
+        sw = self.coulomb_potential.switch_fn.switch_values() if self._kind == 1 else (0.0, 1.0)
+        key = (str(like.device), sw) + tuple((t.data_ptr(), t._version) for t in bufs)
+        if key != self._op_key or self._op_params.device != like.device:
+            self._read_host()
+            with torch.no_grad():
+                prm = self._params8(like)
+                if self._op_params.device != like.device or self._op_params.dtype != torch.float32:
+                    self._op_params = prm
+                else:
+                    self._op_params.copy_(prm)
+            self._op_key = key
+        return self._op_params
+
+    def _n_molecules(self, inputs: Dict[str, torch.Tensor], idx_m: torch.Tensor) -> int:
+        if self.n_molecules_key in inputs:
+            return int(inputs[self.n_molecules_key])
+        return int(idx_m[-1]) + 1
+
+    def forward(self, inputs: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+        q = inputs[self.charges_key].squeeze(-1)
+        idx_m = inputs[properties.idx_m]
+        if self.use_neighbors_lr:
+            r_ij = inputs[properties.Rij_lr]
+            idx_i = inputs[properties.idx_i_lr]
+            idx_j = inputs[properties.idx_j_lr]
+        else:
+            r_ij = inputs[properties.Rij]
+            idx_i = inputs[properties.idx_i]
+            idx_j = inputs[properties.idx_j]
+        n_molecules = self._n_molecules(inputs, idx_m)
+        if self._kind >= 0 and not self.training and not use_aten(r_ij) and not use_aten(q):
+            if torch.jit.is_scripting():
+                prm = self._params8(r_ij)
+            else:
+                prm = self.op_params(r_ij)
+            inputs[self.output_key] = torch.ops.spk_hip.coulomb(r_ij, q, idx_i, idx_j, idx_m, n_molecules, prm)[0]
+            return inputs
+        note_fallback()
+        # the reference's formula (atomistic/electrostatic.py:131-151), differentiable to any order
+        d_ij = torch.norm(r_ij, dim=1)
+        n_atoms = q.shape[0]
+        q_ij = q[idx_i] * q[idx_j]
+        potential = self.coulomb_potential(d_ij)
+        cutoff = self.cutoff
+        shift = self.shift
+        if cutoff is not None and shift is not None:
+            potential = potential + shift ** 2 / potential - 2.0 * shift
+            potential = torch.where(d_ij <= cutoff, potential, torch.zeros_like(potential))
+        y = scatter_add((q_ij * potential), idx_i, dim_size=n_atoms)
+        y = scatter_add(y, idx_m, dim_size=n_molecules)
+        y = 0.5 * self.ke * torch.squeeze(y, -1)
+        inputs[self.output_key] = y
+        return inputs
+
+
+class EnergyEwald(nn.Module):
+    """Coulomb energy of point charges in a periodic box by Ewald summation (atomistic/electrostatic.py:159-375): a real-space sum of
+    ``erfc(sqrt(alpha) d) / d`` over the neighbour list (optionally screened by ``1 - screening_fn(d)``) plus the reciprocal-space sum over the
+    integer vectors ``kvecs`` and the self-interaction term.  Constructor, attributes and buffers (``ke`` [1], ``alpha`` [1], ``kvecs`` [K, 3], in the
+    reference's order) are the reference's, so its ``state_dict``s and pickles load.
+
+    In eval mode, on float32 device tensors, with ``screening_fn`` None or the mirror ``SwitchFunction``, ``k_max <= 8`` (the factor table of
+    csrc/spk_ewald.hip) and a cell that does not require grad, the energy is two operators: ``torch.ops.spk_hip.coulomb`` (pair function 2) and
+    ``torch.ops.spk_hip.ewald_recip``, whose backwards return dE/dr_ij, dE/dR and dE/dq.  Everything else runs the reference's formula on ATen
+    (``note_fallback()``): training mode, float64, host tensors, another screening callable, ``k_max`` beyond the cap, and a strained cell -- the
+    route of the Ewald stress.  A cell without volume raises ``EnergyEwaldError`` on the ATen route like the reference; on the operator route it
+    yields NaN for that molecule (raising would need a device sync).  Parameters reach the kernels as in :class:`EnergyCoulomb`."""
+
+    _screen: Final[int]
+    use_neighbors_lr: Final[bool]
+    k_max: Final[int]
+
+    def __init__(self, alpha: float, k_max: int, energy_unit: Union[str, float], position_unit: Union[str, float], output_key: str,
+                 charges_key: str = properties.partial_charges, use_neighbors_lr: bool = True, screening_fn: Optional[nn.Module] = None,
+                 n_molecules_key: str = "_n_molecules"):
+        super().__init__()
+        ke = spk_units.convert_units("Ha", energy_unit) * spk_units.convert_units("Bohr", position_unit)
+        self.register_buffer("ke", torch.Tensor([ke]))
+        self.charges_key = charges_key
+        self.output_key = output_key
+        self.model_outputs = [output_key]
+        self.use_neighbors_lr = use_neighbors_lr
+        self.screening_fn = screening_fn
+        self.register_buffer("alpha", torch.Tensor([alpha]))
+        self.k_max = k_max
+        kvecs = self._generate_kvecs()
+        self.register_buffer("kvecs", kvecs)
+        self.n_molecules_key = n_molecules_key
+        self._init_operator()
+
+    @torch.jit.unused
+    def _generate_kvecs(self) -> torch.Tensor:
+        """The integer k-vectors, in the reference's order (atomistic/electrostatic.py:209-224)."""
+        krange = torch.arange(0, self.k_max + 1, dtype=self.alpha.dtype)
+        krange = torch.cat([krange, -krange[1:]])
+        kvecs = torch.cartesian_prod(krange, krange, krange)
+        norm = torch.sum(kvecs ** 2, dim=1)
+        kvecs = kvecs[norm <= self.k_max ** 2 + 2, :]
+        norm = norm[norm <= self.k_max ** 2 + 2]
+        kvecs = kvecs[norm != 0, :]
+        return kvecs
+
+    def _init_operator(self):
+        self._screen = 0 if self.screening_fn is None else (1 if type(self.screening_fn) is SwitchFunction else -1)
+        self._kmax_ok = 0 < int(self.k_max) <= int(_lib.lib().spk_ewald_max_kmax())
+        self.register_buffer("_op_params", torch.zeros(10), persistent=False)
+        self._op_key = None
+        self._read_host()
+
+    def _read_host(self):
+        self._ke_host = float(self.ke.reshape(-1)[0])
+        self._alpha_host = float(self.alpha.reshape(-1)[0])
+        self._on_host, self._off_host = 0.0, 1.0
+        if self._screen == 1:
+            self._on_host, self._off_host = self.screening_fn.switch_values()
+
+    def __setstate__(self, state):
+        super().__setstate__(state)
+        if "n_molecules_key" not in self.__dict__:
+            self.n_molecules_key = "_n_molecules"
+        if "_screen" not in self.__dict__ or "_op_params" not in self._buffers:
+            self._init_operator()
+
+    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
+        super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
+        if not self.ke.is_meta:
+            self._read_host()
+            on = state_dict.get(prefix + "screening_fn.switch_on")      # (children load after this module)
+            off = state_dict.get(prefix + "screening_fn.switch_off")
+            if self._screen == 1 and on is not None and off is not None and not on.is_meta:
+                self._on_host, self._off_host = float(on.reshape(-1)[0]), float(off.reshape(-1)[0])
+            self._op_key = None
+
+    def _params10(self, like: torch.Tensor) -> torch.Tensor:
+        """[0:8] the pair-function block of ``spk_hip::coulomb`` (kind 2), [8:10] ke and alpha for ``spk_hip::ewald_recip``."""
+        return torch.tensor([self._ke_host, 2.0, 0.0, 0.0, self._on_host, self._off_host, self._alpha_host, 1.0 if self._screen == 1 else 0.0,
+                             self._ke_host, self._alpha_host], dtype=torch.float32, device=like.device)
+
+    @torch.jit.unused
+    def op_params(self, like: torch.Tensor) -> torch.Tensor:
+        """The operators' parameter buffer, rewritten in place only when ``ke``, ``alpha`` or a switch radius has changed since the last call."""
+        sw = self.screening_fn.switch_values() if self._screen == 1 else (0.0, 1.0)
+        key = (str(like.device), sw) + tuple((t.data_ptr(), t._version) for t in (self.ke, self.alpha))
+        if key != self._op_key or self._op_params.device != like.device:
+            self._read_host()
+            with torch.no_grad():
+                prm = self._params10(like)
+                if self._op_params.device != like.device or self._op_params.dtype != torch.float32:
+                    self._op_params = prm
+                else:
+                    self._op_params.copy_(prm)
+            self._op_key = key
+        return self._op_params
+
+    def _n_molecules(self, inputs: Dict[str, torch.Tensor], idx_m: torch.Tensor) -> int:
+        if self.n_molecules_key in inputs:
+            return int(inputs[self.n_molecules_key])
+        return int(idx_m[-1]) + 1
+
+    def forward(self, inputs: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+        q = inputs[self.charges_key].squeeze(-1)
+        idx_m = inputs[properties.idx_m]
+        if self.use_neighbors_lr:
+            r_ij = inputs[properties.Rij_lr]
+            idx_i = inputs[properties.idx_i_lr]
+            idx_j = inputs[properties.idx_j_lr]
+        else:
+            r_ij = inputs[properties.Rij]
+            idx_i = inputs[properties.idx_i]
+            idx_j = inputs[properties.idx_j]
+        positions = inputs[properties.R]
+        cell = inputs[properties.cell]
+        n_molecules = self._n_molecules(inputs, idx_m)
+        if (self._screen >= 0 and self._kmax_ok and not self.training and not use_aten(r_ij) and not use_aten(q) and not use_aten(positions)
+                and not use_aten(cell) and not cell.requires_grad):
+            if torch.jit.is_scripting():
+                prm = self._params10(r_ij)
+            else:
+                prm = self.op_params(r_ij)
+            y_real = torch.ops.spk_hip.coulomb(r_ij, q, idx_i, idx_j, idx_m, n_molecules, prm[0:8])[0]
+            y_rec = torch.ops.spk_hip.ewald_recip(positions, q, cell, idx_m, n_molecules, self.kvecs.to(torch.float32), prm[8:10])[0]
+            inputs[self.output_key] = y_real + y_rec
+            return inputs
+        note_fallback()
+        d_ij = torch.norm(r_ij, dim=1)
+        n_atoms = q.shape[0]
+        y_real = self._real_space(q, d_ij, idx_i, idx_j, idx_m, n_atoms, n_molecules)
+        y_reciprocal = self._reciprocal_space(q, positions, cell, idx_m, n_molecules)
+        inputs[self.output_key] = y_real + y_reciprocal
+        return inputs
+
+    def _real_space(self, q: torch.Tensor, d_ij: torch.Tensor, idx_i: torch.Tensor, idx_j: torch.Tensor, idx_m: torch.Tensor, n_atoms: int,
+                    n_molecules: int) -> torch.Tensor:
+        """The reference's formula (atomistic/electrostatic.py:266-308)."""
+        f_r = torch.erfc(torch.sqrt(self.alpha) * d_ij) / d_ij
+        screening_fn = self.screening_fn
+        if screening_fn is not None:
+            f_r = f_r * (1.0 - screening_fn(d_ij))
+        potential_ij = q[idx_i] * q[idx_j] * f_r
+        y = scatter_add(potential_ij, idx_i, dim_size=n_atoms)
+        y = scatter_add(y, idx_m, dim_size=n_molecules)
+        return 0.5 * self.ke * y.squeeze(-1)
+
+    @torch.jit.unused
+    def _check_volume(self, v_box: torch.Tensor) -> None:
+        if torch.any(torch.isclose(v_box, torch.zeros_like(v_box))):
+            raise EnergyEwaldError("Simulation box has no volume.")
+
+    def _reciprocal_space(self, q: torch.Tensor, positions: torch.Tensor, cell: torch.Tensor, idx_m: torch.Tensor, n_molecules: int) -> torch.Tensor:
+        """The reference's formula (atomistic/electrostatic.py:310-375)."""
+        recip_box = 2.0 * math.pi * torch.linalg.inv(cell).transpose(1, 2)
+        v_box = torch.abs(torch.linalg.det(cell))
+        if not torch.jit.is_scripting():      # (a scripted module cannot raise the class: a cell without volume gives inf / NaN there)
+            self._check_volume(v_box)
+        prefactor = 2.0 * math.pi / v_box
+        kvecs = torch.matmul(self.kvecs[None, :, :], recip_box)
+        k_squared = torch.sum(kvecs ** 2, dim=2)
+        q_gauss = torch.exp(-0.25 * k_squared / self.alpha)
+        kvec_dot_pos = torch.sum(kvecs[idx_m] * positions[:, None, :], dim=2)
+        q_real = scatter_add((q[:, None] * torch.cos(kvec_dot_pos)), idx_m, dim_size=n_molecules)
+        q_imag = scatter_add((q[:, None] * torch.sin(kvec_dot_pos)), idx_m, dim_size=n_molecules)
+        q_dens = q_real ** 2 + q_imag ** 2
+        y_ewald = prefactor * torch.sum(q_dens * q_gauss / k_squared, dim=1)
+        self_interaction = math.sqrt(1.0 / math.pi) * torch.sqrt(self.alpha) * scatter_add(q ** 2, idx_m, dim_size=n_molecules)
+        return self.ke * (y_ewald - self_interaction)

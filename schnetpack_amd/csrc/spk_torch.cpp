@@ -1086,6 +1086,112 @@ Tensor zbl_forces_raw(const Tensor& R_in, const c10::optional<Tensor>& offsets_i
   return E;
 }
 
+// Point-charge electrostatics over a neighbour list (atomistic/electrostatic.py:14-152, :266-308; csrc/spk_coulomb.hip).  params: 8 floats as a
+// float32 DEVICE tensor (ke, kind, rc or 0, shift, switch_on, switch_off, alpha, screened): a replayed graph reads what the host last wrote there.
+Tensor coulomb_params(const Tensor& params, const char* who) {
+  Tensor p = f32(params.detach(), who);
+  TORCH_CHECK(p.numel() == 8, who, ": params = [ke, kind, cutoff (0: none), shift, switch_on, switch_off, alpha, screened] (8 floats), got ", p.sizes());
+  return p;
+}
+Tensor coulomb_workspace(const spk_graph_t& g, int64_t n_mol, const Tensor& like) {
+  const int64_t bytes = spk_coulomb_workspace_bytes(&g, n_mol);
+  TORCH_CHECK(bytes >= 0, "coulomb: bad list");
+  return at::empty({std::max<int64_t>(1, bytes)}, like.options().dtype(at::kByte));
+}
+std::tuple<Tensor, Tensor, Tensor> coulomb_forward_raw(const Tensor& r_in, const Tensor& q_in, const Tensor& idx_i, const Tensor& idx_j, const Tensor& idx_m_in,
+                                                       int64_t n_mol, const Tensor& params) {
+  const char* who = "coulomb";
+  Tensor r = f32(r_in.detach(), who), q = f32(q_in.detach(), who), idx_m = i64(idx_m_in, who), prm = coulomb_params(params, who);
+  const int64_t N = idx_m.size(0);
+  TORCH_CHECK(r.dim() == 2 && r.size(1) == 3 && r.size(0) == idx_i.size(0) && q.numel() == N && idx_m.dim() == 1 && n_mol >= 0, who,
+              ": r_ij [E, 3], q [N(, 1)], idx_m [N]");
+  c10::DeviceGuard guard(r.device());
+  Tensor E = at::empty({n_mol}, r.options()), Ea = at::empty({N}, r.options()), phi = at::empty({N}, r.options());
+  auto plan = get_plan(idx_i, idx_j, N, r);
+  spk_graph_t g = plan->graph();
+  Tensor ws = coulomb_workspace(g, n_mol, r);
+  check(spk_coulomb_fwd_f32(r.numel() ? fp(r) : nullptr, N ? fp(q) : nullptr, &g, N ? idx_m.data_ptr<int64_t>() : nullptr, n_mol, fp(prm),
+                            n_mol ? fpm(E) : nullptr, N ? fpm(Ea) : nullptr, N ? fpm(phi) : nullptr, ws.data_ptr(), stream_of(r)));
+  return {E, Ea, phi};
+}
+std::tuple<Tensor, Tensor> coulomb_backward_raw(const Tensor& gE_in, const Tensor& r_in, const Tensor& q_in, const Tensor& phi_in, const Tensor& idx_i,
+                                                const Tensor& idx_j, const Tensor& idx_m_in, int64_t n_mol, const Tensor& params) {
+  const char* who = "coulomb_backward";
+  Tensor gE = f32(gE_in, who), r = f32(r_in.detach(), who), q = f32(q_in.detach(), who), phi = f32(phi_in.detach(), who), idx_m = i64(idx_m_in, who),
+         prm = coulomb_params(params, who);
+  const int64_t N = idx_m.size(0);
+  TORCH_CHECK(gE.numel() == n_mol && r.dim() == 2 && r.size(1) == 3 && r.size(0) == idx_i.size(0) && q.numel() == N && phi.numel() == N, who,
+              ": gE [n_mol], r_ij [E, 3], q / phi [N]");
+  c10::DeviceGuard guard(r.device());
+  Tensor gr = at::empty_like(r), gq = at::empty(q_in.sizes(), r.options());
+  if (N == 0) return {gr, gq};
+  auto plan = get_plan(idx_i, idx_j, N, r);
+  spk_graph_t g = plan->graph();
+  Tensor ws = coulomb_workspace(g, n_mol, r);
+  check(spk_coulomb_bwd_f32(fp(gE), r.numel() ? fp(r) : nullptr, fp(q), fp(phi), &g, idx_m.data_ptr<int64_t>(), n_mol, fp(prm), r.numel() ? fpm(gr) : nullptr,
+                            fpm(gq), ws.data_ptr(), stream_of(r)));
+  return {gr, gq};
+}
+
+// Reciprocal-space Ewald sum (atomistic/electrostatic.py:310-375; csrc/spk_ewald.hip).  kvecs [K, 3]: the module's integer vectors (float32 on the
+// device); params: ke and alpha as a float32 DEVICE tensor.  k_max is recovered from K (the reference's rule |n|^2 <= k_max^2 + 2), else the cap.
+int32_t ewald_kmax_of(int64_t K) {
+  const int32_t cap = spk_ewald_max_kmax();
+  for (int32_t km = 1; km <= cap; ++km) {
+    int64_t n = 0;
+    for (int a = -km; a <= km; ++a)
+      for (int b = -km; b <= km; ++b)
+        for (int c = -km; c <= km; ++c) {
+          const int s = a * a + b * b + c * c;
+          n += (s != 0 && s <= km * km + 2);
+        }
+    if (n == K) return km;
+  }
+  return cap;
+}
+struct EwaldArgs { Tensor R, q, cell, idx_m, kvecs, prm; int64_t N, K; };
+EwaldArgs ewald_args(const Tensor& R_in, const Tensor& q_in, const Tensor& cell_in, const Tensor& idx_m_in, int64_t n_mol, const Tensor& kvecs_in,
+                     const Tensor& params, const char* who) {
+  EwaldArgs a{f32(R_in.detach(), who), f32(q_in.detach(), who), f32(cell_in.detach(), who), i64(idx_m_in, who), f32(kvecs_in.detach(), who),
+              f32(params.detach(), who), 0, 0};
+  a.N = a.R.size(0);
+  TORCH_CHECK(a.R.dim() == 2 && a.R.size(1) == 3 && a.q.numel() == a.N && a.idx_m.dim() == 1 && a.idx_m.size(0) == a.N && a.cell.numel() == 9 * n_mol && n_mol >= 0,
+              who, ": R [N, 3], q [N(, 1)], cell [n_mol, 3, 3], idx_m [N]");
+  TORCH_CHECK(a.kvecs.dim() == 2 && a.kvecs.size(1) == 3 && a.prm.numel() == 2, who, ": kvecs [K, 3], params = [ke, alpha]");
+  a.K = a.kvecs.size(0);
+  return a;
+}
+std::tuple<Tensor, Tensor> ewald_recip_forward_raw(const Tensor& R_in, const Tensor& q_in, const Tensor& cell_in, const Tensor& idx_m_in, int64_t n_mol,
+                                                   const Tensor& kvecs_in, const Tensor& params) {
+  const char* who = "ewald_recip";
+  EwaldArgs a = ewald_args(R_in, q_in, cell_in, idx_m_in, n_mol, kvecs_in, params, who);
+  c10::DeviceGuard guard(a.R.device());
+  Tensor E = at::empty({n_mol}, a.R.options()), coef = at::empty({n_mol, a.K, 2}, a.R.options());
+  const int64_t bytes = spk_ewald_workspace_bytes(a.N, a.K, n_mol);
+  TORCH_CHECK(bytes >= 0, who, ": bad sizes");
+  Tensor ws = at::empty({std::max<int64_t>(1, bytes)}, a.R.options().dtype(at::kByte));
+  check(spk_ewald_recip_fwd_f32(a.N ? fp(a.R) : nullptr, a.N ? fp(a.q) : nullptr, n_mol ? fp(a.cell) : nullptr, a.N ? a.idx_m.data_ptr<int64_t>() : nullptr, a.N, n_mol,
+                                a.K ? fp(a.kvecs) : nullptr, a.K, ewald_kmax_of(a.K), fp(a.prm), n_mol ? fpm(E) : nullptr, coef.numel() ? fpm(coef) : nullptr,
+                                ws.data_ptr(), stream_of(a.R)));
+  return {E, coef};
+}
+std::tuple<Tensor, Tensor> ewald_recip_backward_raw(const Tensor& gE_in, const Tensor& R_in, const Tensor& q_in, const Tensor& cell_in, const Tensor& idx_m_in,
+                                                    int64_t n_mol, const Tensor& kvecs_in, const Tensor& params, const Tensor& coef_in) {
+  const char* who = "ewald_recip_backward";
+  EwaldArgs a = ewald_args(R_in, q_in, cell_in, idx_m_in, n_mol, kvecs_in, params, who);
+  Tensor gE = f32(gE_in, who), coef = f32(coef_in.detach(), who);
+  TORCH_CHECK(gE.numel() == n_mol && coef.numel() == n_mol * a.K * 2, who, ": gE [n_mol], coeffs [n_mol, K, 2]");
+  c10::DeviceGuard guard(a.R.device());
+  Tensor gR = at::empty_like(a.R), gq = at::empty(q_in.sizes(), a.R.options());
+  if (a.N == 0) return {gR, gq};
+  const int64_t bytes = spk_ewald_workspace_bytes(a.N, a.K, n_mol);
+  TORCH_CHECK(bytes >= 0, who, ": bad sizes");
+  Tensor ws = at::empty({std::max<int64_t>(1, bytes)}, a.R.options().dtype(at::kByte));
+  check(spk_ewald_recip_bwd_f32(fp(gE), fp(a.R), fp(a.q), fp(a.cell), a.idx_m.data_ptr<int64_t>(), a.N, n_mol, a.K ? fp(a.kvecs) : nullptr, a.K,
+                                ewald_kmax_of(a.K), fp(a.prm), coef.numel() ? fp(coef) : nullptr, fpm(gR), fpm(gq), ws.data_ptr(), stream_of(a.R)));
+  return {gR, gq};
+}
+
 // Tensorial heads (atomistic/atomwise.py:91-293; csrc/spk_tensorial.hip), eval only, no autograd node: the mirrors hand in detached tensors and
 // pass the outputs through eval_guard.
 // gated_mlp: the gated equivariant MLP of a head in one launch.  weights = per block [mix_vectors.weight, scalar_net.0.weight, scalar_net.0.bias,
@@ -1563,6 +1669,93 @@ struct ZblFn : public torch::autograd::Function<ZblFn> {
   }
 };
 
+// Electrostatics: first-order gradients w.r.t. the pair vectors / positions and the charges (what Forces asks for in eval mode, also through
+// predicted charges)
+using T3 = std::tuple<Tensor, Tensor, Tensor>;
+using T2 = std::tuple<Tensor, Tensor>;
+T3 call_coulomb(const Tensor& r, const Tensor& q, const Tensor& ii, const Tensor& jj, const Tensor& idx_m, int64_t n_mol, const Tensor& prm) {
+  static auto op = op_handle<T3(const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, int64_t, const Tensor&)>("spk_hip::coulomb");
+  return op.call(r, q, ii, jj, idx_m, n_mol, prm);
+}
+T2 call_coulomb_backward(const Tensor& gE, const Tensor& r, const Tensor& q, const Tensor& phi, const Tensor& ii, const Tensor& jj, const Tensor& idx_m,
+                         int64_t n_mol, const Tensor& prm) {
+  static auto op = op_handle<T2(const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, int64_t, const Tensor&)>(
+      "spk_hip::coulomb_backward");
+  return op.call(gE, r, q, phi, ii, jj, idx_m, n_mol, prm);
+}
+T2 call_ewald_recip(const Tensor& R, const Tensor& q, const Tensor& cell, const Tensor& idx_m, int64_t n_mol, const Tensor& kvecs, const Tensor& prm) {
+  static auto op = op_handle<T2(const Tensor&, const Tensor&, const Tensor&, const Tensor&, int64_t, const Tensor&, const Tensor&)>("spk_hip::ewald_recip");
+  return op.call(R, q, cell, idx_m, n_mol, kvecs, prm);
+}
+T2 call_ewald_recip_backward(const Tensor& gE, const Tensor& R, const Tensor& q, const Tensor& cell, const Tensor& idx_m, int64_t n_mol, const Tensor& kvecs,
+                             const Tensor& prm, const Tensor& coef) {
+  static auto op = op_handle<T2(const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, int64_t, const Tensor&, const Tensor&, const Tensor&)>(
+      "spk_hip::ewald_recip_backward");
+  return op.call(gE, R, q, cell, idx_m, n_mol, kvecs, prm, coef);
+}
+const char* kCoulombFirstOrder =
+    "spk_hip::coulomb: the operator returns first-order gradients w.r.t. the pair vectors and the charges only -- a recorded backward "
+    "(create_graph=True) or a gradient w.r.t. the per-atom outputs was requested.  Put the module in training mode (module.train()): EnergyCoulomb / "
+    "EnergyEwald then run the reference's formula on ATen, differentiable to any order.";
+const char* kEwaldFirstOrder =
+    "spk_hip::ewald_recip: the operator returns first-order gradients w.r.t. the positions and the charges only -- a recorded backward "
+    "(create_graph=True), a gradient w.r.t. the structure-factor coefficients or w.r.t. the cell was requested.  Put the module in training mode "
+    "(module.train()): EnergyEwald then runs the reference's formula on ATen, differentiable to any order (the route of the Ewald stress).";
+struct CoulombFn : public torch::autograd::Function<CoulombFn> {
+  static variable_list forward(AutogradContext* ctx, const Tensor& r, const Tensor& q, const Tensor& ii, const Tensor& jj, const Tensor& idx_m, int64_t n_mol,
+                               const Tensor& prm) {
+    at::AutoDispatchBelowADInplaceOrView guard;
+    ctx->set_materialize_grads(false);
+    auto out = call_coulomb(r, q, ii, jj, idx_m, n_mol, prm);
+    ctx->save_for_backward({r, q, ii, jj, idx_m, prm, std::get<2>(out)});
+    ctx->saved_data["n_mol"] = n_mol;
+    return {std::get<0>(out), std::get<1>(out), std::get<2>(out)};
+  }
+  static variable_list backward(AutogradContext* ctx, variable_list grads) {
+    TORCH_CHECK(!at::GradMode::is_enabled(), kCoulombFirstOrder);
+    TORCH_CHECK(!grads[1].defined() && !grads[2].defined(), kCoulombFirstOrder);
+    auto sv = ctx->get_saved_variables();
+    Tensor gr, gq;
+    if ((ctx->needs_input_grad(0) || ctx->needs_input_grad(1)) && grads[0].defined()) {
+      auto g = call_coulomb_backward(grads[0], sv[0], sv[1], sv[6], sv[2], sv[3], sv[4], ctx->saved_data["n_mol"].toInt(), sv[5]);
+      if (ctx->needs_input_grad(0)) gr = std::get<0>(g);
+      if (ctx->needs_input_grad(1)) gq = std::get<1>(g);
+    }
+    return {gr, gq, Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
+  }
+};
+struct EwaldRecipFn : public torch::autograd::Function<EwaldRecipFn> {
+  static variable_list forward(AutogradContext* ctx, const Tensor& R, const Tensor& q, const Tensor& cell, const Tensor& idx_m, int64_t n_mol,
+                               const Tensor& kvecs, const Tensor& prm) {
+    at::AutoDispatchBelowADInplaceOrView guard;
+    ctx->set_materialize_grads(false);
+    auto out = call_ewald_recip(R, q, cell, idx_m, n_mol, kvecs, prm);
+    ctx->save_for_backward({R, q, cell, idx_m, kvecs, prm, std::get<1>(out)});
+    ctx->saved_data["n_mol"] = n_mol;
+    return {std::get<0>(out), std::get<1>(out)};
+  }
+  static variable_list backward(AutogradContext* ctx, variable_list grads) {
+    TORCH_CHECK(!at::GradMode::is_enabled(), kEwaldFirstOrder);
+    TORCH_CHECK(!grads[1].defined() && !ctx->needs_input_grad(2), kEwaldFirstOrder);
+    auto sv = ctx->get_saved_variables();
+    Tensor gR, gq;
+    if ((ctx->needs_input_grad(0) || ctx->needs_input_grad(1)) && grads[0].defined()) {
+      auto g = call_ewald_recip_backward(grads[0], sv[0], sv[1], sv[2], sv[3], ctx->saved_data["n_mol"].toInt(), sv[4], sv[5], sv[6]);
+      if (ctx->needs_input_grad(0)) gR = std::get<0>(g);
+      if (ctx->needs_input_grad(1)) gq = std::get<1>(g);
+    }
+    return {gR, gq, Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
+  }
+};
+T3 coulomb_ad(const Tensor& r, const Tensor& q, const Tensor& ii, const Tensor& jj, const Tensor& idx_m, int64_t n_mol, const Tensor& prm) {
+  auto o = CoulombFn::apply(r, q, ii, jj, idx_m, n_mol, prm);
+  return {o[0], o[1], o[2]};
+}
+T2 ewald_recip_ad(const Tensor& R, const Tensor& q, const Tensor& cell, const Tensor& idx_m, int64_t n_mol, const Tensor& kvecs, const Tensor& prm) {
+  auto o = EwaldRecipFn::apply(R, q, cell, idx_m, n_mol, kvecs, prm);
+  return {o[0], o[1]};
+}
+
 // ------------------------------------------------------------------------------------------------ operator entry points
 // --- Autograd key
 Tensor scatter_add_ad(const Tensor& x, const Tensor& idx, int64_t dim_size, int64_t dim) { return ScatterAddFn::apply(x, idx, dim_size, dim); }
@@ -1914,6 +2107,20 @@ Tensor zbl_forces_meta(const Tensor& R, const c10::optional<Tensor>&, const Tens
                        c10::optional<Tensor>) {
   return at::empty({n_mol}, R.options());
 }
+std::tuple<Tensor, Tensor, Tensor> coulomb_meta(const Tensor& r, const Tensor&, const Tensor&, const Tensor&, const Tensor& idx_m, int64_t n_mol, const Tensor&) {
+  return {at::empty({n_mol}, r.options()), at::empty({idx_m.size(0)}, r.options()), at::empty({idx_m.size(0)}, r.options())};
+}
+std::tuple<Tensor, Tensor> coulomb_backward_meta(const Tensor&, const Tensor& r, const Tensor& q, const Tensor&, const Tensor&, const Tensor&, const Tensor&, int64_t,
+                                                 const Tensor&) {
+  return {at::empty_like(r), at::empty_like(q)};
+}
+std::tuple<Tensor, Tensor> ewald_recip_meta(const Tensor& R, const Tensor&, const Tensor&, const Tensor&, int64_t n_mol, const Tensor& kvecs, const Tensor&) {
+  return {at::empty({n_mol}, R.options()), at::empty({n_mol, kvecs.size(0), 2}, R.options())};
+}
+std::tuple<Tensor, Tensor> ewald_recip_backward_meta(const Tensor&, const Tensor& R, const Tensor& q, const Tensor&, const Tensor&, int64_t, const Tensor&,
+                                                     const Tensor&, const Tensor&) {
+  return {at::empty_like(R), at::empty_like(q)};
+}
 std::tuple<Tensor, Tensor> gated_mlp_meta(const Tensor& s, const Tensor&, at::TensorList, int64_t) {
   return {at::empty({s.size(0), 1}, s.options()), at::empty({s.size(0), 3, 1}, s.options())};
 }
@@ -2003,6 +2210,12 @@ TORCH_LIBRARY(spk_hip, m) {
   m.def("zbl(Tensor r_ij, Tensor Z, Tensor idx_i, Tensor idx_j, Tensor idx_m, int n_mol, Tensor params) -> (Tensor, Tensor)");
   m.def("zbl_backward(Tensor gE, Tensor r_ij, Tensor Z, Tensor idx_i, Tensor idx_j, Tensor idx_m, int n_mol, Tensor params) -> Tensor");
   m.def("zbl_forces(Tensor R, Tensor? offsets, Tensor Z, Tensor idx_i, Tensor idx_j, Tensor idx_m, int n_mol, Tensor params, Tensor(a!) F, Tensor(b!)? W) -> Tensor");  // eval: E_zbl; F, W += in place
+  // atomistic/electrostatic.py: point charges over a list (E [n_mol], E_atom [N], phi [N]; params = 8 floats on the device, csrc/spk_coulomb.hip) and the
+  // reciprocal-space Ewald sum (E [n_mol], coeffs [n_mol, K, 2] = g_k S(k); params = ke, alpha on the device, csrc/spk_ewald.hip)
+  m.def("coulomb(Tensor r_ij, Tensor q, Tensor idx_i, Tensor idx_j, Tensor idx_m, int n_mol, Tensor params) -> (Tensor, Tensor, Tensor)");
+  m.def("coulomb_backward(Tensor gE, Tensor r_ij, Tensor q, Tensor phi, Tensor idx_i, Tensor idx_j, Tensor idx_m, int n_mol, Tensor params) -> (Tensor, Tensor)");
+  m.def("ewald_recip(Tensor R, Tensor q, Tensor cell, Tensor idx_m, int n_mol, Tensor kvecs, Tensor params) -> (Tensor, Tensor)");
+  m.def("ewald_recip_backward(Tensor gE, Tensor R, Tensor q, Tensor cell, Tensor idx_m, int n_mol, Tensor kvecs, Tensor params, Tensor coeffs) -> (Tensor, Tensor)");
   // tensorial heads (atomistic/atomwise.py:91-293; csrc/spk_tensorial.hip), eval only: the gated equivariant MLP in one launch, the moments in one more
   m.def("gated_mlp(Tensor s, Tensor v, Tensor[] weights, int act) -> (Tensor, Tensor)");
   m.def("dipole_moment(Tensor q, Tensor? d, Tensor R, Tensor idx_m, int n_mol, Tensor? total_charge, bool correct) -> (Tensor, Tensor)");
@@ -2060,6 +2273,10 @@ TORCH_LIBRARY_IMPL(spk_hip, CUDA, m) {   // "CUDA" is the dispatch key of ROCm d
   m.impl("zbl", zbl_forward_raw);
   m.impl("zbl_backward", zbl_backward_raw);
   m.impl("zbl_forces", zbl_forces_raw);
+  m.impl("coulomb", coulomb_forward_raw);
+  m.impl("coulomb_backward", coulomb_backward_raw);
+  m.impl("ewald_recip", ewald_recip_forward_raw);
+  m.impl("ewald_recip_backward", ewald_recip_backward_raw);
   m.impl("gated_mlp", gated_mlp_raw);
   m.impl("dipole_moment", dipole_moment_raw);
   m.impl("polarizability", polarizability_raw);
@@ -2096,6 +2313,8 @@ TORCH_LIBRARY_IMPL(spk_hip, Autograd, m) {
   m.impl("schnet_potential", schnet_potential_ad);
   m.impl("eval_guard", eval_guard_ad);
   m.impl("zbl", zbl_ad);
+  m.impl("coulomb", coulomb_ad);
+  m.impl("ewald_recip", ewald_recip_ad);
   train_impl_autograd(m);
   fm_impl_autograd(m);
 }
@@ -2106,7 +2325,7 @@ TORCH_LIBRARY_IMPL(spk_hip, CPU, m) {
                            "painn_backward", "atomwise_forward", "atomwise_backward", "edge_plan", "static_declare", "static_declare_range", "schnet_potential",
                            "schnet_potential_forward", "schnet_potential_backward", "schnet_potential_forces", "painn_potential_forces", "potential_plan",
                            "schnet_potential_stress", "painn_potential_stress", "zbl", "zbl_backward", "zbl_forces", "gated_mlp",
-                           "dipole_moment", "polarizability"})
+                           "dipole_moment", "polarizability", "coulomb", "coulomb_backward", "ewald_recip", "ewald_recip_backward"})
     m.impl(name, torch::CppFunction::makeFromBoxedFunction<&no_cpu_boxed>());
   for (const char* name : kTrainOps) m.impl(name, torch::CppFunction::makeFromBoxedFunction<&no_cpu_boxed>());
   for (const char* name : kFmOps) m.impl(name, torch::CppFunction::makeFromBoxedFunction<&no_cpu_boxed>());
@@ -2142,6 +2361,10 @@ TORCH_LIBRARY_IMPL(spk_hip, Meta, m) {
   m.impl("zbl", zbl_meta);
   m.impl("zbl_backward", zbl_backward_meta);
   m.impl("zbl_forces", zbl_forces_meta);
+  m.impl("coulomb", coulomb_meta);
+  m.impl("coulomb_backward", coulomb_backward_meta);
+  m.impl("ewald_recip", ewald_recip_meta);
+  m.impl("ewald_recip_backward", ewald_recip_backward_meta);
   m.impl("gated_mlp", gated_mlp_meta);
   m.impl("dipole_moment", dipole_moment_meta);
   m.impl("polarizability", polarizability_meta);

@@ -7,8 +7,9 @@ Patches, inside the already imported ``schnetpack`` package, exactly the names o
 section 8(b): ``nn.scatter_add`` (+ ``nn.scatter.scatter_add``), ``nn.Dense``, ``nn.GaussianRBF``,
 ``nn.BesselRBF``, ``nn.CosineCutoff``, ``representation.{SchNet, SchNetInteraction, PaiNN,
 PaiNNInteraction, PaiNNMixing}``, ``atomistic.PairwiseDistances``, ``atomistic.ZBLRepulsionEnergy``,
-``atomistic.Aggregation``, ``nn.GatedEquivariantBlock``, ``nn.build_gated_equivariant_mlp`` and
-``atomistic.{DipoleMoment, Polarizability}``.  Classes are replaced both on
+``atomistic.Aggregation``, ``nn.GatedEquivariantBlock``, ``nn.build_gated_equivariant_mlp``,
+``atomistic.{DipoleMoment, Polarizability}``, ``nn.SwitchFunction``, ``atomistic.FilterShortRange`` and
+``atomistic.{CoulombPotential, DampedCoulombPotential, EnergyCoulomb, EnergyEwald}``.  Classes are replaced both on
 the package and on the defining sub-module, so Hydra ``_target_`` paths and pickled models
 (``torch.load`` resolves ``schnetpack.representation.painn.PaiNN`` by attribute) pick up the
 mirrors; parameter names and shapes are identical, so existing ``state_dict``s and whole-model
@@ -59,6 +60,8 @@ def _fused_potential_call(orig_call):
     from . import model as M
 
     def __call__(self, *args, **kwargs):
+        if "_spk_hip_linked" not in self.__dict__:      # predicted charges that a later electrostatic term reads: differentiable in eval mode too
+            self.__dict__["_spk_hip_linked"] = M.link_charge_consumers(self)
         if (self.training or len(args) != 1 or kwargs or not isinstance(args[0], dict)
                 or self._forward_hooks or self._forward_pre_hooks):
             return orig_call(self, *args, **kwargs)
@@ -156,6 +159,14 @@ def install(spk=None, verbose=False, fused_head=True, neighbor_lists=False, fuse
     for mod in (getattr(spk, "atomistic", None), sub("atomistic.atomwise")):
         _set(mod, "DipoleMoment", A.DipoleMoment, log)
         _set(mod, "Polarizability", A.Polarizability, log)
+    # point-charge electrostatics (when the reference has loaded them): same constructors, buffers and state_dict keys
+    for mod in (getattr(spk, "nn", None), sub("nn.cutoff")):
+        _set(mod, "SwitchFunction", N.SwitchFunction, log)
+    for mod in (getattr(spk, "atomistic", None), sub("atomistic.distances")):
+        _set(mod, "FilterShortRange", A.FilterShortRange, log)
+    for mod in (getattr(spk, "atomistic", None), sub("atomistic.electrostatic")):
+        for name in ("CoulombPotential", "DampedCoulombPotential", "EnergyCoulomb", "EnergyEwald"):
+            _set(mod, name, getattr(A, name), log)
     if fused_potential and fused_head:
         mb = sub("model.base")
         cls = getattr(mb, "NeuralNetworkPotential", None) if mb is not None else None

@@ -6,7 +6,8 @@ import torch
 import torch.nn as nn
 
 from . import properties
-from .atomistic import Aggregation, Atomwise, DipoleMoment, Forces, PairwiseDistances, Polarizability, Strain, ZBLRepulsionEnergy
+from .atomistic import (Aggregation, Atomwise, DipoleMoment, EnergyCoulomb, EnergyEwald, Forces, PairwiseDistances, Polarizability, Strain,
+                        ZBLRepulsionEnergy)
 from .nn import CosineCutoff, GaussianRBF, BesselRBF
 from .representation import PaiNN, SchNet
 
@@ -81,6 +82,29 @@ def run_tail(model, inputs: Dict[str, torch.Tensor], n_tail: int) -> Dict[str, t
     return inputs
 
 
+def _is_electrostatic(m) -> bool:
+    """The mirrors' ``EnergyCoulomb`` / ``EnergyEwald`` (subclasses included) or the reference's own (atomistic/electrostatic.py)."""
+    if isinstance(m, (EnergyCoulomb, EnergyEwald)):
+        return True
+    t = type(m)
+    return t.__name__ in ("EnergyCoulomb", "EnergyEwald") and t.__module__ == "schnetpack.atomistic.electrostatic"
+
+
+def link_charge_consumers(model) -> int:
+    """Tell every ``DipoleMoment(return_charges=True)`` mirror whose ``charges_key`` a LATER electrostatic output module reads that its charges are
+    differentiated (``_charges_differentiable``): in eval mode with autograd enabled that head then takes its differentiable route, so ``Forces`` of
+    the electrostatic energy includes the dq/dR term.  Heads without such a consumer are left as they are (two fused launches, outputs behind
+    ``eval_guard``).  Returns the number of heads linked."""
+    outs = list(model.output_modules)
+    n = 0
+    for i, m in enumerate(outs):
+        if type(m) is DipoleMoment and m.return_charges:
+            if any(_is_electrostatic(c) and getattr(c, "charges_key", None) == m.charges_key for c in outs[i + 1:]):
+                m._charges_differentiable = True
+                n += 1
+    return n
+
+
 def classify_potential(model) -> int:
     """0: module-by-module.  1: the standard potential -- ``PairwiseDistances`` -> fused ``SchNet`` -> ``Atomwise`` (default
     head, summed or averaged over the molecule) -> ``Forces`` without stress: representation + head are ONE operator.
@@ -91,10 +115,13 @@ def classify_potential(model) -> int:
     (:func:`zbl_layout`): the same operators, then one ``zbl_forces`` operator (a row pass, two reductions, a row-pointer kernel) that adds the
     repulsion into their forces and virial, and one add of the two energies.
     A tail of ``DipoleMoment`` / ``Polarizability`` mirrors (:func:`tensorial_tail`) is set aside first: the rest classifies as above and the
-    tail runs module by module behind the fused call; such a module anywhere else gives 0.
+    tail runs module by module behind the fused call; such a module anywhere else gives 0.  Any model with an ``EnergyCoulomb`` / ``EnergyEwald``
+    term gives 0.
     Works on any model with the reference's ``NeuralNetworkPotential`` layout (model/base.py:132-190), i.e. also on the
     reference's own class around the HIP modules."""
     rep, ins, outs = model.representation, list(model.input_modules), list(model.output_modules)
+    if any(_is_electrostatic(m) for m in outs):      # electrostatic terms run module by module: a fused force call must never drop them
+        return 0
     outs = outs[:len(outs) - tensorial_tail(outs)]
     is_painn = isinstance(rep, PaiNN)
     if not (isinstance(rep, (SchNet, PaiNN)) and rep._fused and len(rep.interactions) > 0):
@@ -318,6 +345,7 @@ class NeuralNetworkPotential(nn.Module):
                 if k not in outs:
                     outs.append(k)
         self.model_outputs = outs
+        link_charge_consumers(self)
         mode = classify_potential(self)
         self._potential = mode in (1, 2)
         # ... and when the only other output is Forces' -dE/dR, energies AND forces come from the two launches directly

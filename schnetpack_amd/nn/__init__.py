@@ -2,7 +2,7 @@ from .activations import shifted_softplus
 from .base import Dense
 from .blocks import build_gated_equivariant_mlp, build_mlp
 from .equivariant import GatedEquivariantBlock
-from .cutoff import CosineCutoff, cosine_cutoff
+from .cutoff import CosineCutoff, SwitchFunction, cosine_cutoff
 from .radial import BesselRBF, GaussianRBF, gaussian_rbf
 from .scatter import scatter_add
 from .utils import replicate_module

@@ -13,9 +13,10 @@ import warnings
 
 import torch
 
-__all__ = ["use_aten", "note_fallback", "cosine_cutoff_aten", "gaussian_rbf_aten", "bessel_rbf_aten"]
+__all__ = ["use_aten", "note_fallback", "fallback_count", "cosine_cutoff_aten", "gaussian_rbf_aten", "bessel_rbf_aten"]
 
 _NOTED = False
+_COUNT = 0      # calls of note_fallback() in this process (tests read it to see which route a module took)
 
 
 def use_aten(x: torch.Tensor) -> bool:
@@ -26,11 +27,17 @@ def use_aten(x: torch.Tensor) -> bool:
 
 @torch.jit.unused
 def _note() -> None:
-    global _NOTED
+    global _NOTED, _COUNT
+    _COUNT += 1
     if not _NOTED:
         _NOTED = True
         warnings.warn("schnetpack_amd: a host / non-float32 tensor takes the plain ATen route of the module mirrors (the reference's formulas); "
                       "the HIP kernels run float32 tensors on the ROCm device", stacklevel=3)
+
+
+def fallback_count() -> int:
+    """Number of ``note_fallback()`` calls so far (eager calls only)."""
+    return _COUNT
 
 
 def note_fallback() -> None:
