@@ -275,6 +275,30 @@ int spk_coulomb_fwd_f32(const float* r_ij, const float* q, const spk_graph_t* g,
 int spk_coulomb_bwd_f32(const float* gE, const float* r_ij, const float* q, const float* phi, const spk_graph_t* g, const int64_t* idx_m,
                         int64_t n_mol, const float* params, float* gr, float* gq, void* workspace, void* stream);
 
+/* ------------------------------------------------------------------ nn/so3.py (RealSphericalHarmonics, SO3Convolution, SO3TensorProduct)
+ * Combined index s = l^2 + l + m, S = (lmax + 1)^2, lmax 1..3; F features, a multiple of 32 up to 256 (spk_so3_supported).
+ * spk_rsh_fwd_f32: Y [P, S] from directions [P, 3], Y_lm = N_l Pi_l^|m|(z) AB_m(x, y) as the reference evaluates it: closed polynomials in
+ *   independent x, y, z, nothing normalised.  spk_rsh_bwd_f32: gdir [P, 3] = sum_s gY[p, s] dY_s/d(x, y, z), the derivative of that polynomial.
+ * spk_so3_conv_fwd_f32: y[i,s,f] = sum_{p in row i} sum_{(s1,s2)->s} C Y[p,s1] fcut[p] W[p,l(s1),f] x[idx_j[p],s2,f] on a list sorted by idx_i;
+ *   x, y [N, S, F], W [P, (lmax+1) F], Y [P, S], fcut [P].  y is overwritten, rows without neighbours with zeros.
+ * spk_so3_conv_bwd_f32: gx [N, S, F] (needs the symmetric list's g->rev), gW [P, (lmax+1) F], gY [P, S], gfcut [P]; gx may be NULL, and so
+ *   may the three pair gradients together.  workspace: spk_so3_conv_workspace_bytes(g, lmax, F) bytes (pair gradients only).
+ * spk_so3_product_fwd_f32: y[n,s,f] = sum C x1[n,s1,f] x2[n,s2,f]; _bwd: gx1 and gx2.
+ * No atomics anywhere: the same inputs give the same bits.  spk_so3_cg_table (host only): the compiled-in real Clebsch-Gordan non-zeros of lmax
+ *   in row-major (s1, s2, s) order; returns their number (10 / 83 / 353) and fills up to cap entries of the arrays that are not NULL. */
+int spk_so3_supported(int32_t lmax, int32_t F);
+int32_t spk_so3_cg_table(int32_t lmax, int32_t cap, int32_t* s1, int32_t* s2, int32_t* s, float* c);
+int spk_rsh_fwd_f32(const float* directions, int64_t P, int32_t lmax, float* Y, void* stream);
+int spk_rsh_bwd_f32(const float* gY, const float* directions, int64_t P, int32_t lmax, float* gdir, void* stream);
+int64_t spk_so3_conv_workspace_bytes(const spk_graph_t* g, int32_t lmax, int32_t F);
+int spk_so3_conv_fwd_f32(const float* x, const float* W, const float* Y, const float* fcut, const spk_graph_t* g, int32_t lmax, int32_t F,
+                         float* y, void* stream);
+int spk_so3_conv_bwd_f32(const float* gy, const float* x, const float* W, const float* Y, const float* fcut, const spk_graph_t* g, int32_t lmax,
+                         int32_t F, float* gx, float* gW, float* gY, float* gfcut, void* workspace, void* stream);
+int spk_so3_product_fwd_f32(const float* x1, const float* x2, int64_t N, int32_t lmax, int32_t F, float* y, void* stream);
+int spk_so3_product_bwd_f32(const float* gy, const float* x1, const float* x2, int64_t N, int32_t lmax, int32_t F, float* gx1, float* gx2,
+                            void* stream);
+
 /* ------------------------------------------------------------------ atomistic/electrostatic.py:310-375 (EnergyEwald._reciprocal_space)
  *   S(k) = sum_{i in m} q_i e^{i k r_i},  E_rec[m] = ke (2 pi / V sum_k g_k |S(k)|^2 - sqrt(alpha / pi) sum_i q_i^2),  g_k = exp(-k^2 / 4 alpha) / k^2
  * with k = n 2 pi C^-T for the integer vectors n = kvecs [K, 3] (float32, DEVICE memory, |n_a| <= k_max <= spk_ewald_max_kmax() = 8).

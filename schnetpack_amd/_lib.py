@@ -160,6 +160,15 @@ _PROTOS = {
     "spk_coulomb_workspace_bytes": (c_i64, [P(GraphT), c_i64]),
     "spk_coulomb_fwd_f32": (ctypes.c_int, [c_f, c_f, P(GraphT), c_f, c_i64, c_f, c_f, c_f, c_f, c_f, c_f]),
     "spk_coulomb_bwd_f32": (ctypes.c_int, [c_f, c_f, c_f, c_f, P(GraphT), c_f, c_i64, c_f, c_f, c_f, c_f, c_f]),
+    "spk_so3_supported": (ctypes.c_int, [c_i32, c_i32]),
+    "spk_so3_cg_table": (c_i32, [c_i32, c_i32, P(c_i32), P(c_i32), P(c_i32), P(ctypes.c_float)]),
+    "spk_rsh_fwd_f32": (ctypes.c_int, [c_f, c_i64, c_i32, c_f, c_f]),
+    "spk_rsh_bwd_f32": (ctypes.c_int, [c_f, c_f, c_i64, c_i32, c_f, c_f]),
+    "spk_so3_conv_workspace_bytes": (c_i64, [P(GraphT), c_i32, c_i32]),
+    "spk_so3_conv_fwd_f32": (ctypes.c_int, [c_f, c_f, c_f, c_f, P(GraphT), c_i32, c_i32, c_f, c_f]),
+    "spk_so3_conv_bwd_f32": (ctypes.c_int, [c_f, c_f, c_f, c_f, c_f, P(GraphT), c_i32, c_i32, c_f, c_f, c_f, c_f, c_f, c_f]),
+    "spk_so3_product_fwd_f32": (ctypes.c_int, [c_f, c_f, c_i64, c_i32, c_i32, c_f, c_f]),
+    "spk_so3_product_bwd_f32": (ctypes.c_int, [c_f, c_f, c_f, c_i64, c_i32, c_i32, c_f, c_f, c_f]),
     "spk_ewald_max_kmax": (c_i32, []),
     "spk_ewald_atom_tile": (c_i32, []),
     "spk_ewald_atom_slab": (c_i32, []),

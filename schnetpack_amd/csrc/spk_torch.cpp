@@ -1133,6 +1133,128 @@ std::tuple<Tensor, Tensor> coulomb_backward_raw(const Tensor& gE_in, const Tenso
   return {gr, gq};
 }
 
+// SO(3) layers (nn/so3.py; csrc/spk_so3.hip): real spherical harmonics, the Clebsch-Gordan convolution over a list and the tensor product.
+// x, y [N, S, F] with S = (lmax + 1)^2; filter [P, (lmax + 1) F] (any shape with that many elements per pair); Y [P, S]; fcut: one value per pair.
+int64_t so3_S(int64_t lmax, const char* who) {
+  TORCH_CHECK(lmax >= 1 && lmax <= 3, who, ": lmax ", lmax, " outside 1..3 (the module mirrors route other orders to ATen)");
+  return (lmax + 1) * (lmax + 1);
+}
+void so3_check_features(const Tensor& x, int64_t lmax, const char* who) {
+  const int64_t S = so3_S(lmax, who);
+  TORCH_CHECK(x.dim() == 3 && x.size(1) == S, who, ": features [N, ", S, ", F], got ", x.sizes());
+  TORCH_CHECK(spk_so3_supported((int32_t)lmax, (int32_t)std::min<int64_t>(x.size(2), 1 << 20)), who, ": ", x.size(2),
+              " features -- the kernels take a multiple of 32 up to 256 (the module mirrors route other widths to ATen)");
+}
+// The plan of the list.  Its reverse-edge map needs a vector per pair that changes sign with the pair: a plan that already knows the geometry
+// (same index tensors) is taken as it is; otherwise the l = 1 harmonics times the cutoff value stand in (odd in r_ij, and distinct for the
+// images of one pair as long as the cutoff function separates their distances).
+std::shared_ptr<Plan> so3_plan(const Tensor& Y, const Tensor& fcut, const Tensor& idx_i, const Tensor& idx_j, int64_t N) {
+  if (idx_i.size(0) > 0) {
+    std::vector<uint64_t> key{(uint64_t)idx_i.data_ptr(), (uint64_t)idx_j.data_ptr(), version_of(idx_i), version_of(idx_j), (uint64_t)idx_i.size(0),
+                              (uint64_t)N, (uint64_t)idx_i.device().index(), 1, 1, (uint64_t)idx_i.scalar_type()};
+    std::lock_guard<std::mutex> lock(g_mutex);
+    if (auto hit = g_plans.get(key)) return hit;
+  }
+  Tensor v = (Y.detach().slice(1, 1, 4) * fcut.detach().reshape({-1, 1})).contiguous();
+  return get_plan(idx_i, idx_j, N, v);
+}
+struct So3Args { Tensor x, W, Y, fc; int64_t N, P, S, F; };
+So3Args so3_conv_args(const Tensor& x_in, const Tensor& W_in, const Tensor& Y_in, const Tensor& fc_in, const Tensor& idx_i, int64_t lmax, const char* who) {
+  So3Args a;
+  a.x = f32(x_in.detach(), who); a.W = f32(W_in.detach(), who); a.Y = f32(Y_in.detach(), who); a.fc = f32(fc_in.detach(), who);
+  so3_check_features(a.x, lmax, who);
+  a.N = a.x.size(0); a.S = a.x.size(1); a.F = a.x.size(2); a.P = idx_i.size(0);
+  TORCH_CHECK(a.Y.dim() == 2 && a.Y.size(0) == a.P && a.Y.size(1) == a.S && a.fc.numel() == a.P && a.W.numel() == a.P * (lmax + 1) * a.F, who,
+              ": filter [P, (lmax+1) F], Y [P, S], fcut [P(, 1)] for P = ", a.P, " pairs; got ", a.W.sizes(), ", ", a.Y.sizes(), ", ", a.fc.sizes());
+  return a;
+}
+int64_t so3_list_ok_op(const Tensor& Y, const Tensor& fcut, const Tensor& idx_i, const Tensor& idx_j, int64_t n_atoms) {
+  require_device(idx_i, "so3_list_ok");
+  if (idx_i.size(0) == 0) return 1;
+  auto p = so3_plan(f32(Y, "so3_list_ok"), f32(fcut, "so3_list_ok"), idx_i, idx_j, n_atoms);
+  return p->sorted && p->symmetric;
+}
+Tensor real_sph_harm_raw(const Tensor& dir_in, int64_t lmax) {
+  const char* who = "real_sph_harm";
+  const int64_t S = so3_S(lmax, who);
+  Tensor d = f32(dir_in.detach(), who);
+  TORCH_CHECK(d.dim() == 2 && d.size(1) == 3, who, ": directions [P, 3], got ", d.sizes());
+  c10::DeviceGuard guard(d.device());
+  Tensor Y = at::empty({d.size(0), S}, d.options());
+  check(spk_rsh_fwd_f32(d.numel() ? fp(d) : nullptr, d.size(0), (int32_t)lmax, d.numel() ? fpm(Y) : nullptr, stream_of(d)));
+  return Y;
+}
+Tensor real_sph_harm_backward_raw(const Tensor& gY_in, const Tensor& dir_in, int64_t lmax) {
+  const char* who = "real_sph_harm_backward";
+  const int64_t S = so3_S(lmax, who);
+  Tensor d = f32(dir_in.detach(), who), gY = f32(gY_in, who);
+  TORCH_CHECK(d.dim() == 2 && d.size(1) == 3 && gY.dim() == 2 && gY.size(0) == d.size(0) && gY.size(1) == S, who, ": gY [P, ", S, "], directions [P, 3]");
+  c10::DeviceGuard guard(d.device());
+  Tensor gd = at::empty_like(d);
+  check(spk_rsh_bwd_f32(d.numel() ? fp(gY) : nullptr, d.numel() ? fp(d) : nullptr, d.size(0), (int32_t)lmax, d.numel() ? fpm(gd) : nullptr, stream_of(d)));
+  return gd;
+}
+Tensor so3_conv_raw(const Tensor& x_in, const Tensor& W_in, const Tensor& Y_in, const Tensor& fc_in, const Tensor& idx_i, const Tensor& idx_j, int64_t lmax) {
+  const char* who = "so3_conv";
+  So3Args a = so3_conv_args(x_in, W_in, Y_in, fc_in, idx_i, lmax, who);
+  c10::DeviceGuard guard(a.x.device());
+  Tensor y = at::empty_like(a.x);
+  auto plan = so3_plan(a.Y, a.fc, idx_i, idx_j, a.N);
+  TORCH_CHECK(a.P == 0 || plan->sorted, who, ": the list must be sorted by idx_i (SO3Convolution routes other lists to ATen)");
+  spk_graph_t g = plan->graph();
+  check(spk_so3_conv_fwd_f32(fp(a.x), a.P ? fp(a.W) : nullptr, a.P ? fp(a.Y) : nullptr, a.P ? fp(a.fc) : nullptr, &g, (int32_t)lmax, (int32_t)a.F,
+                             a.N ? fpm(y) : nullptr, stream_of(a.x)));
+  return y;
+}
+std::tuple<Tensor, Tensor, Tensor, Tensor> so3_conv_backward_raw(const Tensor& gy_in, const Tensor& x_in, const Tensor& W_in, const Tensor& Y_in,
+                                                                 const Tensor& fc_in, const Tensor& idx_i, const Tensor& idx_j, int64_t lmax, bool want_gx,
+                                                                 bool want_pair) {
+  const char* who = "so3_conv_backward";
+  So3Args a = so3_conv_args(x_in, W_in, Y_in, fc_in, idx_i, lmax, who);
+  Tensor gy = f32(gy_in, who);
+  TORCH_CHECK(gy.sizes() == a.x.sizes(), who, ": gy ", gy.sizes(), " against x ", a.x.sizes());
+  c10::DeviceGuard guard(a.x.device());
+  Tensor gx = want_gx ? at::empty_like(a.x) : at::empty({0}, a.x.options());
+  Tensor gW = want_pair ? at::empty(W_in.sizes(), a.x.options()) : at::empty({0}, a.x.options());
+  Tensor gY = want_pair ? at::empty_like(a.Y) : at::empty({0}, a.x.options());
+  Tensor gf = want_pair ? at::empty(fc_in.sizes(), a.x.options()) : at::empty({0}, a.x.options());
+  if (a.N == 0 || !(want_gx || want_pair)) return {gx, gW, gY, gf};
+  auto plan = so3_plan(a.Y, a.fc, idx_i, idx_j, a.N);
+  TORCH_CHECK(a.P == 0 || (plan->sorted && plan->symmetric), who,
+              ": the list must be sorted by idx_i and symmetric (SO3Convolution routes other lists to ATen)");
+  spk_graph_t g = plan->graph();
+  const int64_t bytes = spk_so3_conv_workspace_bytes(&g, (int32_t)lmax, (int32_t)a.F);
+  TORCH_CHECK(bytes >= 0, who, ": bad list");
+  Tensor ws = at::empty({std::max<int64_t>(1, bytes)}, a.x.options().dtype(at::kByte));
+  const bool pair = want_pair && a.P > 0;
+  check(spk_so3_conv_bwd_f32(fp(gy), fp(a.x), a.P ? fp(a.W) : nullptr, a.P ? fp(a.Y) : nullptr, a.P ? fp(a.fc) : nullptr, &g, (int32_t)lmax, (int32_t)a.F,
+                             want_gx ? fpm(gx) : nullptr, pair ? fpm(gW) : nullptr, pair ? fpm(gY) : nullptr, pair ? fpm(gf) : nullptr, ws.data_ptr(),
+                             stream_of(a.x)));
+  return {gx, gW, gY, gf};
+}
+Tensor so3_product_raw(const Tensor& x1_in, const Tensor& x2_in, int64_t lmax) {
+  const char* who = "so3_product";
+  Tensor x1 = f32(x1_in.detach(), who), x2 = f32(x2_in.detach(), who);
+  so3_check_features(x1, lmax, who);
+  TORCH_CHECK(x1.sizes() == x2.sizes(), who, ": x1 ", x1.sizes(), " against x2 ", x2.sizes());
+  c10::DeviceGuard guard(x1.device());
+  Tensor y = at::empty_like(x1);
+  check(spk_so3_product_fwd_f32(x1.numel() ? fp(x1) : nullptr, x1.numel() ? fp(x2) : nullptr, x1.size(0), (int32_t)lmax, (int32_t)x1.size(2),
+                                x1.numel() ? fpm(y) : nullptr, stream_of(x1)));
+  return y;
+}
+std::tuple<Tensor, Tensor> so3_product_backward_raw(const Tensor& gy_in, const Tensor& x1_in, const Tensor& x2_in, int64_t lmax) {
+  const char* who = "so3_product_backward";
+  Tensor gy = f32(gy_in, who), x1 = f32(x1_in.detach(), who), x2 = f32(x2_in.detach(), who);
+  so3_check_features(x1, lmax, who);
+  TORCH_CHECK(x1.sizes() == x2.sizes() && gy.sizes() == x1.sizes(), who, ": gy, x1, x2 of one shape");
+  c10::DeviceGuard guard(x1.device());
+  Tensor g1 = at::empty_like(x1), g2 = at::empty_like(x1);
+  if (x1.numel() == 0) return {g1, g2};
+  check(spk_so3_product_bwd_f32(fp(gy), fp(x1), fp(x2), x1.size(0), (int32_t)lmax, (int32_t)x1.size(2), fpm(g1), fpm(g2), stream_of(x1)));
+  return {g1, g2};
+}
+
 // Reciprocal-space Ewald sum (atomistic/electrostatic.py:310-375; csrc/spk_ewald.hip).  kvecs [K, 3]: the module's integer vectors (float32 on the
 // device); params: ke and alpha as a float32 DEVICE tensor.  k_max is recovered from K (the reference's rule |n|^2 <= k_max^2 + 2), else the cap.
 int32_t ewald_kmax_of(int64_t K) {
@@ -1756,6 +1878,88 @@ T2 ewald_recip_ad(const Tensor& R, const Tensor& q, const Tensor& cell, const Te
   return {o[0], o[1]};
 }
 
+// SO(3) layers: first-order gradients (what Forces asks for in eval mode); a recorded backward raises the eval-only message
+using T4 = std::tuple<Tensor, Tensor, Tensor, Tensor>;
+Tensor call_rsh_backward(const Tensor& gY, const Tensor& d, int64_t lmax) {
+  static auto op = op_handle<Tensor(const Tensor&, const Tensor&, int64_t)>("spk_hip::real_sph_harm_backward");
+  return op.call(gY, d, lmax);
+}
+T4 call_so3_conv_backward(const Tensor& gy, const Tensor& x, const Tensor& W, const Tensor& Y, const Tensor& fc, const Tensor& ii, const Tensor& jj, int64_t lmax,
+                          bool want_gx, bool want_pair) {
+  static auto op = op_handle<T4(const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, int64_t, bool, bool)>(
+      "spk_hip::so3_conv_backward");
+  return op.call(gy, x, W, Y, fc, ii, jj, lmax, want_gx, want_pair);
+}
+T2 call_so3_product_backward(const Tensor& gy, const Tensor& x1, const Tensor& x2, int64_t lmax) {
+  static auto op = op_handle<T2(const Tensor&, const Tensor&, const Tensor&, int64_t)>("spk_hip::so3_product_backward");
+  return op.call(gy, x1, x2, lmax);
+}
+struct RshFn : public torch::autograd::Function<RshFn> {
+  static Tensor forward(AutogradContext* ctx, const Tensor& d, int64_t lmax) {
+    at::AutoDispatchBelowADInplaceOrView guard;
+    static auto op = op_handle<Tensor(const Tensor&, int64_t)>("spk_hip::real_sph_harm");
+    ctx->save_for_backward({d});
+    ctx->saved_data["lmax"] = lmax;
+    return op.call(d, lmax);
+  }
+  static variable_list backward(AutogradContext* ctx, variable_list grads) {
+    TORCH_CHECK(!at::GradMode::is_enabled(), "spk_hip::real_sph_harm", kEvalOnly);
+    auto sv = ctx->get_saved_variables();
+    Tensor gd;
+    if (ctx->needs_input_grad(0) && grads[0].defined()) gd = call_rsh_backward(grads[0], sv[0], ctx->saved_data["lmax"].toInt());
+    return {gd, Tensor()};
+  }
+};
+struct So3ConvFn : public torch::autograd::Function<So3ConvFn> {
+  static Tensor forward(AutogradContext* ctx, const Tensor& x, const Tensor& W, const Tensor& Y, const Tensor& fc, const Tensor& ii, const Tensor& jj,
+                        int64_t lmax) {
+    at::AutoDispatchBelowADInplaceOrView guard;
+    static auto op = op_handle<Tensor(const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, int64_t)>("spk_hip::so3_conv");
+    ctx->save_for_backward({x, W, Y, fc, ii, jj});
+    ctx->saved_data["lmax"] = lmax;
+    return op.call(x, W, Y, fc, ii, jj, lmax);
+  }
+  static variable_list backward(AutogradContext* ctx, variable_list grads) {
+    TORCH_CHECK(!at::GradMode::is_enabled(), "spk_hip::so3_conv", kEvalOnly);
+    auto sv = ctx->get_saved_variables();
+    variable_list out(7);
+    const bool want_gx = ctx->needs_input_grad(0), want_pair = ctx->needs_input_grad(1) || ctx->needs_input_grad(2) || ctx->needs_input_grad(3);
+    if (grads[0].defined() && (want_gx || want_pair)) {
+      auto g = call_so3_conv_backward(grads[0], sv[0], sv[1], sv[2], sv[3], sv[4], sv[5], ctx->saved_data["lmax"].toInt(), want_gx, want_pair);
+      if (ctx->needs_input_grad(0)) out[0] = std::get<0>(g);
+      if (ctx->needs_input_grad(1)) out[1] = std::get<1>(g);
+      if (ctx->needs_input_grad(2)) out[2] = std::get<2>(g);
+      if (ctx->needs_input_grad(3)) out[3] = std::get<3>(g);
+    }
+    return out;
+  }
+};
+struct So3ProductFn : public torch::autograd::Function<So3ProductFn> {
+  static Tensor forward(AutogradContext* ctx, const Tensor& x1, const Tensor& x2, int64_t lmax) {
+    at::AutoDispatchBelowADInplaceOrView guard;
+    static auto op = op_handle<Tensor(const Tensor&, const Tensor&, int64_t)>("spk_hip::so3_product");
+    ctx->save_for_backward({x1, x2});
+    ctx->saved_data["lmax"] = lmax;
+    return op.call(x1, x2, lmax);
+  }
+  static variable_list backward(AutogradContext* ctx, variable_list grads) {
+    TORCH_CHECK(!at::GradMode::is_enabled(), "spk_hip::so3_product", kEvalOnly);
+    auto sv = ctx->get_saved_variables();
+    variable_list out(3);
+    if (grads[0].defined() && (ctx->needs_input_grad(0) || ctx->needs_input_grad(1))) {
+      auto g = call_so3_product_backward(grads[0], sv[0], sv[1], ctx->saved_data["lmax"].toInt());
+      if (ctx->needs_input_grad(0)) out[0] = std::get<0>(g);
+      if (ctx->needs_input_grad(1)) out[1] = std::get<1>(g);
+    }
+    return out;
+  }
+};
+Tensor real_sph_harm_ad(const Tensor& d, int64_t lmax) { return RshFn::apply(d, lmax); }
+Tensor so3_conv_ad(const Tensor& x, const Tensor& W, const Tensor& Y, const Tensor& fc, const Tensor& ii, const Tensor& jj, int64_t lmax) {
+  return So3ConvFn::apply(x, W, Y, fc, ii, jj, lmax);
+}
+Tensor so3_product_ad(const Tensor& x1, const Tensor& x2, int64_t lmax) { return So3ProductFn::apply(x1, x2, lmax); }
+
 // ------------------------------------------------------------------------------------------------ operator entry points
 // --- Autograd key
 Tensor scatter_add_ad(const Tensor& x, const Tensor& idx, int64_t dim_size, int64_t dim) { return ScatterAddFn::apply(x, idx, dim_size, dim); }
@@ -2114,6 +2318,16 @@ std::tuple<Tensor, Tensor> coulomb_backward_meta(const Tensor&, const Tensor& r,
                                                  const Tensor&) {
   return {at::empty_like(r), at::empty_like(q)};
 }
+Tensor real_sph_harm_meta(const Tensor& d, int64_t lmax) { return at::empty({d.size(0), (lmax + 1) * (lmax + 1)}, d.options()); }
+Tensor real_sph_harm_backward_meta(const Tensor&, const Tensor& d, int64_t) { return at::empty_like(d); }
+Tensor so3_conv_meta(const Tensor& x, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, int64_t) { return at::empty_like(x); }
+std::tuple<Tensor, Tensor, Tensor, Tensor> so3_conv_backward_meta(const Tensor&, const Tensor& x, const Tensor& W, const Tensor& Y, const Tensor& fc, const Tensor&,
+                                                                  const Tensor&, int64_t, bool, bool) {
+  return {at::empty_like(x), at::empty_like(W), at::empty_like(Y), at::empty_like(fc)};
+}
+Tensor so3_product_meta(const Tensor& x1, const Tensor&, int64_t) { return at::empty_like(x1); }
+std::tuple<Tensor, Tensor> so3_product_backward_meta(const Tensor&, const Tensor& x1, const Tensor& x2, int64_t) { return {at::empty_like(x1), at::empty_like(x2)}; }
+int64_t so3_list_ok_meta(const Tensor&, const Tensor&, const Tensor&, const Tensor&, int64_t) { return 1; }
 std::tuple<Tensor, Tensor> ewald_recip_meta(const Tensor& R, const Tensor&, const Tensor&, const Tensor&, int64_t n_mol, const Tensor& kvecs, const Tensor&) {
   return {at::empty({n_mol}, R.options()), at::empty({n_mol, kvecs.size(0), 2}, R.options())};
 }
@@ -2216,6 +2430,15 @@ TORCH_LIBRARY(spk_hip, m) {
   m.def("coulomb_backward(Tensor gE, Tensor r_ij, Tensor q, Tensor phi, Tensor idx_i, Tensor idx_j, Tensor idx_m, int n_mol, Tensor params) -> (Tensor, Tensor)");
   m.def("ewald_recip(Tensor R, Tensor q, Tensor cell, Tensor idx_m, int n_mol, Tensor kvecs, Tensor params) -> (Tensor, Tensor)");
   m.def("ewald_recip_backward(Tensor gE, Tensor R, Tensor q, Tensor cell, Tensor idx_m, int n_mol, Tensor kvecs, Tensor params, Tensor coeffs) -> (Tensor, Tensor)");
+  // nn/so3.py (csrc/spk_so3.hip): real spherical harmonics [P, (lmax+1)^2], the Clebsch-Gordan convolution over a sorted symmetric list and the
+  // Clebsch-Gordan tensor product; lmax 1..3, F a multiple of 32 up to 256.  so3_list_ok: 1 when the list is sorted by idx_i and symmetric.
+  m.def("real_sph_harm(Tensor directions, int lmax) -> Tensor");
+  m.def("real_sph_harm_backward(Tensor gY, Tensor directions, int lmax) -> Tensor");
+  m.def("so3_conv(Tensor x, Tensor filter, Tensor Y, Tensor fcut, Tensor idx_i, Tensor idx_j, int lmax) -> Tensor");
+  m.def("so3_conv_backward(Tensor gy, Tensor x, Tensor filter, Tensor Y, Tensor fcut, Tensor idx_i, Tensor idx_j, int lmax, bool want_gx, bool want_pair) -> (Tensor, Tensor, Tensor, Tensor)");
+  m.def("so3_product(Tensor x1, Tensor x2, int lmax) -> Tensor");
+  m.def("so3_product_backward(Tensor gy, Tensor x1, Tensor x2, int lmax) -> (Tensor, Tensor)");
+  m.def("so3_list_ok(Tensor Y, Tensor fcut, Tensor idx_i, Tensor idx_j, int n_atoms) -> int");
   // tensorial heads (atomistic/atomwise.py:91-293; csrc/spk_tensorial.hip), eval only: the gated equivariant MLP in one launch, the moments in one more
   m.def("gated_mlp(Tensor s, Tensor v, Tensor[] weights, int act) -> (Tensor, Tensor)");
   m.def("dipole_moment(Tensor q, Tensor? d, Tensor R, Tensor idx_m, int n_mol, Tensor? total_charge, bool correct) -> (Tensor, Tensor)");
@@ -2277,6 +2500,13 @@ TORCH_LIBRARY_IMPL(spk_hip, CUDA, m) {   // "CUDA" is the dispatch key of ROCm d
   m.impl("coulomb_backward", coulomb_backward_raw);
   m.impl("ewald_recip", ewald_recip_forward_raw);
   m.impl("ewald_recip_backward", ewald_recip_backward_raw);
+  m.impl("real_sph_harm", real_sph_harm_raw);
+  m.impl("real_sph_harm_backward", real_sph_harm_backward_raw);
+  m.impl("so3_conv", so3_conv_raw);
+  m.impl("so3_conv_backward", so3_conv_backward_raw);
+  m.impl("so3_product", so3_product_raw);
+  m.impl("so3_product_backward", so3_product_backward_raw);
+  m.impl("so3_list_ok", so3_list_ok_op);
   m.impl("gated_mlp", gated_mlp_raw);
   m.impl("dipole_moment", dipole_moment_raw);
   m.impl("polarizability", polarizability_raw);
@@ -2315,6 +2545,9 @@ TORCH_LIBRARY_IMPL(spk_hip, Autograd, m) {
   m.impl("zbl", zbl_ad);
   m.impl("coulomb", coulomb_ad);
   m.impl("ewald_recip", ewald_recip_ad);
+  m.impl("real_sph_harm", real_sph_harm_ad);
+  m.impl("so3_conv", so3_conv_ad);
+  m.impl("so3_product", so3_product_ad);
   train_impl_autograd(m);
   fm_impl_autograd(m);
 }
@@ -2325,7 +2558,8 @@ TORCH_LIBRARY_IMPL(spk_hip, CPU, m) {
                            "painn_backward", "atomwise_forward", "atomwise_backward", "edge_plan", "static_declare", "static_declare_range", "schnet_potential",
                            "schnet_potential_forward", "schnet_potential_backward", "schnet_potential_forces", "painn_potential_forces", "potential_plan",
                            "schnet_potential_stress", "painn_potential_stress", "zbl", "zbl_backward", "zbl_forces", "gated_mlp",
-                           "dipole_moment", "polarizability", "coulomb", "coulomb_backward", "ewald_recip", "ewald_recip_backward"})
+                           "dipole_moment", "polarizability", "coulomb", "coulomb_backward", "ewald_recip", "ewald_recip_backward",
+                           "real_sph_harm", "real_sph_harm_backward", "so3_conv", "so3_conv_backward", "so3_product", "so3_product_backward", "so3_list_ok"})
     m.impl(name, torch::CppFunction::makeFromBoxedFunction<&no_cpu_boxed>());
   for (const char* name : kTrainOps) m.impl(name, torch::CppFunction::makeFromBoxedFunction<&no_cpu_boxed>());
   for (const char* name : kFmOps) m.impl(name, torch::CppFunction::makeFromBoxedFunction<&no_cpu_boxed>());
@@ -2365,6 +2599,13 @@ TORCH_LIBRARY_IMPL(spk_hip, Meta, m) {
   m.impl("coulomb_backward", coulomb_backward_meta);
   m.impl("ewald_recip", ewald_recip_meta);
   m.impl("ewald_recip_backward", ewald_recip_backward_meta);
+  m.impl("real_sph_harm", real_sph_harm_meta);
+  m.impl("real_sph_harm_backward", real_sph_harm_backward_meta);
+  m.impl("so3_conv", so3_conv_meta);
+  m.impl("so3_conv_backward", so3_conv_backward_meta);
+  m.impl("so3_product", so3_product_meta);
+  m.impl("so3_product_backward", so3_product_backward_meta);
+  m.impl("so3_list_ok", so3_list_ok_meta);
   m.impl("gated_mlp", gated_mlp_meta);
   m.impl("dipole_moment", dipole_moment_meta);
   m.impl("polarizability", polarizability_meta);

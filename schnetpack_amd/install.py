@@ -9,7 +9,9 @@ section 8(b): ``nn.scatter_add`` (+ ``nn.scatter.scatter_add``), ``nn.Dense``, `
 PaiNNInteraction, PaiNNMixing}``, ``atomistic.PairwiseDistances``, ``atomistic.ZBLRepulsionEnergy``,
 ``atomistic.Aggregation``, ``nn.GatedEquivariantBlock``, ``nn.build_gated_equivariant_mlp``,
 ``atomistic.{DipoleMoment, Polarizability}``, ``nn.SwitchFunction``, ``atomistic.FilterShortRange`` and
-``atomistic.{CoulombPotential, DampedCoulombPotential, EnergyCoulomb, EnergyEwald}``.  Classes are replaced both on
+``atomistic.{CoulombPotential, DampedCoulombPotential, EnergyCoulomb, EnergyEwald}``, ``nn.so3.{RealSphericalHarmonics, scalar2rsh,
+SO3TensorProduct, SO3Convolution, SO3ParametricGatedNonlinearity, SO3GatedNonlinearity}`` (+ the names ``nn`` re-exports) and
+``representation.SO3net``.  Classes are replaced both on
 the package and on the defining sub-module, so Hydra ``_target_`` paths and pickled models
 (``torch.load`` resolves ``schnetpack.representation.painn.PaiNN`` by attribute) pick up the
 mirrors; parameter names and shapes are identical, so existing ``state_dict``s and whole-model
@@ -167,6 +169,14 @@ def install(spk=None, verbose=False, fused_head=True, neighbor_lists=False, fuse
     for mod in (getattr(spk, "atomistic", None), sub("atomistic.electrostatic")):
         for name in ("CoulombPotential", "DampedCoulombPotential", "EnergyCoulomb", "EnergyEwald"):
             _set(mod, name, getattr(A, name), log)
+    # the SO(3) layers and SO3net (when the reference has loaded them): same constructors, buffers and state_dict keys
+    from .nn import so3 as S3
+    for mod in (getattr(spk, "nn", None), sub("nn.so3")):
+        for name in ("RealSphericalHarmonics", "scalar2rsh", "SO3TensorProduct", "SO3Convolution", "SO3ParametricGatedNonlinearity",
+                     "SO3GatedNonlinearity"):
+            _set(mod, name, getattr(S3, name), log)
+    for mod in (getattr(spk, "representation", None), sub("representation.so3net")):
+        _set(mod, "SO3net", R.SO3net, log)
     if fused_potential and fused_head:
         mb = sub("model.base")
         cls = getattr(mb, "NeuralNetworkPotential", None) if mb is not None else None

@@ -5,4 +5,6 @@ from .equivariant import GatedEquivariantBlock
 from .cutoff import CosineCutoff, SwitchFunction, cosine_cutoff
 from .radial import BesselRBF, GaussianRBF, gaussian_rbf
 from .scatter import scatter_add
+from .so3 import (RealSphericalHarmonics, SO3Convolution, SO3GatedNonlinearity, SO3ParametricGatedNonlinearity, SO3TensorProduct, scalar2rsh,
+                  sh_indices)
 from .utils import replicate_module
