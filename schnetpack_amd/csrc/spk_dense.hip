@@ -605,7 +605,9 @@ __global__ __launch_bounds__(256) void k_atomwise_fwd16(
         const bool last = (lane == 15) || (mnext != mol);
         if (last && mol >= 0 && mol < n_mol) {
           const int64_t rel = mol - mol0;
-          if (rel >= 0 && rel < 128) { s_sum[rel] += v; s_flag[rel] = 1; }   // only this wave touches s_sum inside the loop
+          // only this wave touches s_sum inside the loop, but idx_m need not ascend: two segments of one tile may carry the
+          // same molecule, so lanes can meet on a slot -- an LDS atomic, as in k_atomwise_fwd
+          if (rel >= 0 && rel < 128) { atomicAdd(&s_sum[rel], v); s_flag[rel] = 1; }
           else unsafeAtomicAdd(&E[mol], v);
         }
       }
