@@ -343,6 +343,27 @@ int spk_gated_mlp_fwd_f32(const float* s, const float* v, int64_t N, int32_t n_i
 int spk_moment_reduce_f32(int32_t kind, const float* q, const float* d, const float* R, const int64_t* idx_m, int64_t N, int64_t n_mol,
                           const float* total_charge, int32_t correct, float* out, float* q_out, void* stream);
 
+/* ------------------------------------------------------------------ nn/embedding.py:239-349 (ElectronicEmbedding), nn/blocks.py:159-296
+ * (Residual, ResidualStack, ResidualMLP without biases) -- forward only, three launches (csrc/spk_eembed.hip):
+ *   e_m = (relu(psi_m), relu(-psi_m)) (is_charged) or |psi_m|,  k_m = W_k e_m / max(e_m, 1),  v_m = W_v e_m,
+ *   w_i = k_m(i) . (W_q x_i + b_q) / sqrt(F),  a_i = softmax_{all atoms}(w)_i / (sum_{j in m(i)} softmax(w)_j + eps)  -- evaluated per molecule
+ *   as exp(w_i - M_m) / (S_m + eps Z exp(M - M_m)), without overflow; a_i = 0 where the eps term overflows,
+ *   y_i = a_i v_m;  per residual block y <- y + W2 act(W1 act(y));  out = W_L act(y)  (+ x with add_input).
+ * x [N, F], psi [n_mol], idx_m [N] ASCENDING, out [N, F] (overwritten; may not alias x).  host_weights: HOST array of 5 + 2 n_residual device
+ * pointers -- linear_q.weight [F, F], linear_q.bias [F], linear_k.weight [F, n_e], linear_v.weight [F, n_e] (n_e = 2 if is_charged else 1),
+ * per block linear1.weight, linear2.weight [F, F], then resblock.linear.weight [F, F]; x and the F x F matrices of the stack 16-byte aligned.
+ * Covered (spk_eembed_supported): F a multiple of 32 up to 256, n_residual 0..4, SPK_ACT_SSP or SPK_ACT_SILU; anything else returns
+ * SPK_ERR_ARG.  workspace: spk_eembed_workspace_bytes(N, n_mol) bytes, 16-byte aligned.  No float atomics, no host synchronisation: the same
+ * inputs give the same bits.  An idx_m entry outside [0, n_mol) is never used as an address; that atom, an atom outside the range its molecule
+ * was found at by bisection and all atoms of a molecule whose range holds a foreign atom receive NaN.  A molecule without atoms writes
+ * nothing; psi_m = 0 gives exact zeros (x itself with add_input); N = 0 returns without a launch. */
+int spk_eembed_supported(int32_t F, int32_t n_residual, int32_t act);
+int64_t spk_eembed_workspace_bytes(int64_t N, int64_t n_mol);
+int64_t spk_eembed_lds_bytes(int32_t F); /* LDS of one 32-atom workgroup of the residual-stack kernel (four waves); -1: F not covered */
+int spk_eembed_fwd_f32(const float* x, const float* psi, const int64_t* idx_m, int64_t N, int64_t n_mol, int32_t F, int32_t n_residual,
+                       int32_t act, int32_t is_charged, float eps, int32_t add_input, const float* const* host_weights, float* out,
+                       void* workspace, void* stream);
+
 /* ------------------------------------------------------------------ transform/neighborlist.py:438-507
  * (TorchNeighborList) and md/neighborlist_md.py:100-159 -- cell-list neighbour list on the device for
  * a batch of independent systems (molecules / MD replicas).  Result: every DIRECTED pair (i, j, S)

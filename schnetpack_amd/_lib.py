@@ -175,6 +175,10 @@ _PROTOS = {
     "spk_ewald_workspace_bytes": (c_i64, [c_i64, c_i64, c_i64]),
     "spk_ewald_recip_fwd_f32": (ctypes.c_int, [c_f, c_f, c_f, c_f, c_i64, c_i64, c_f, c_i64, c_i32, c_f, c_f, c_f, c_f, c_f]),
     "spk_ewald_recip_bwd_f32": (ctypes.c_int, [c_f, c_f, c_f, c_f, c_f, c_i64, c_i64, c_f, c_i64, c_i32, c_f, c_f, c_f, c_f, c_f, c_f]),
+    "spk_eembed_supported": (ctypes.c_int, [c_i32, c_i32, c_i32]),
+    "spk_eembed_workspace_bytes": (c_i64, [c_i64, c_i64]),
+    "spk_eembed_lds_bytes": (c_i64, [c_i32]),
+    "spk_eembed_fwd_f32": (ctypes.c_int, [c_f, c_f, c_f, c_i64, c_i64, c_i32, c_i32, c_i32, c_i32, ctypes.c_float, c_i32, P(ctypes.c_void_p), c_f, c_f, c_f]),
     "spk_gated_mlp_supported": (ctypes.c_int, [c_i32, c_i32, c_i32]),
     "spk_gated_mlp_fwd_f32": (ctypes.c_int, [c_f, c_f, c_i64, c_i32, c_i32, c_i32, P(ctypes.c_void_p), c_f, c_f, c_f]),
     "spk_moment_reduce_f32": (ctypes.c_int, [c_i32, c_f, c_f, c_f, c_f, c_i64, c_i64, c_f, c_i32, c_f, c_f, c_f]),

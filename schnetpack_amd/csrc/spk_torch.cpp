@@ -1384,6 +1384,43 @@ Tensor polarizability_raw(const Tensor& a0_in, const Tensor& d_in, const Tensor&
   return al;
 }
 
+// electronic_embedding: the charge / spin embedding of nn/embedding.py:239-349 in three launches (csrc/spk_eembed.hip), eval only, no autograd node.
+// weights = [linear_q.weight, linear_q.bias, linear_k.weight, linear_v.weight, (linear1.weight, linear2.weight) per residual block,
+// resblock.linear.weight]; psi [n_mol] is the molecular charge or spin (the number of molecules is its length); idx_m ascending.
+Tensor electronic_embedding_raw(const Tensor& x_in, const Tensor& psi_in, const Tensor& idx_m_in, at::TensorList weights, bool is_charged, int64_t act,
+                                double eps, bool add_input) {
+  const char* who = "electronic_embedding";
+  Tensor x = f32(x_in.detach(), who), psi = f32(psi_in.detach(), who), idx_m = i64(idx_m_in, who);
+  TORCH_CHECK(x.dim() == 2 && idx_m.dim() == 1 && idx_m.size(0) == x.size(0) && psi.dim() <= 1, who, ": x [N, F], psi [n_mol], idx_m [N]");
+  const int64_t N = x.size(0), F = x.size(1), n_mol = psi.numel(), n_e = is_charged ? 2 : 1;
+  TORCH_CHECK(weights.size() >= 5 && weights.size() % 2 == 1, who, ": weights = [W_q, b_q, W_k, W_v, (W1, W2) per residual block, W_L]");
+  const int64_t n_res = ((int64_t)weights.size() - 5) / 2;
+  TORCH_CHECK(spk_eembed_supported((int32_t)F, (int32_t)n_res, (int32_t)act), who, ": no kernel for F = ", F, ", ", n_res, " residual blocks, act = ", act,
+              " (spk_eembed_supported); the module mirror takes its ATen route for such shapes");
+  std::vector<Tensor> w;
+  std::vector<const float*> ptr;
+  for (size_t k = 0; k < weights.size(); ++k) {
+    Tensor t = f32(weights[k].detach(), who);
+    const bool ok = k == 1 ? (t.dim() == 1 && t.size(0) == F)
+                           : (t.dim() == 2 && t.size(0) == F && t.size(1) == ((k == 2 || k == 3) ? n_e : F));
+    TORCH_CHECK(ok, who, ": weight ", k, " has shape ", t.sizes(), " (F = ", F, ", ", n_e, " electronic features)");
+    if (((uintptr_t)t.data_ptr() & 15) != 0) t = t.clone();
+    w.push_back(t);
+    ptr.push_back(fp(t));
+  }
+  if (N && (((uintptr_t)x.data_ptr() & 15) != 0)) x = x.clone();
+  c10::DeviceGuard guard(x.device());
+  Tensor out = at::empty_like(x);
+  if (N == 0) return out;
+  TORCH_CHECK(n_mol > 0, who, ": atoms without molecules");
+  const int64_t bytes = spk_eembed_workspace_bytes(N, n_mol);
+  TORCH_CHECK(bytes >= 0, who, ": bad sizes");
+  Tensor ws = at::empty({std::max<int64_t>(1, bytes)}, x.options().dtype(at::kByte));
+  check(spk_eembed_fwd_f32(fp(x), fp(psi), idx_m.data_ptr<int64_t>(), N, n_mol, (int32_t)F, (int32_t)n_res, (int32_t)act, is_charged ? 1 : 0, (float)eps,
+                           add_input ? 1 : 0, ptr.data(), fpm(out), ws.data_ptr(), stream_of(x)));
+  return out;
+}
+
 // ------------------------------------------------------------------------------------------------ dispatcher handles
 template <class Sig>
 c10::TypedOperatorHandle<Sig> op_handle(const char* name) {
@@ -2335,6 +2372,7 @@ std::tuple<Tensor, Tensor> ewald_recip_backward_meta(const Tensor&, const Tensor
                                                      const Tensor&, const Tensor&) {
   return {at::empty_like(R), at::empty_like(q)};
 }
+Tensor electronic_embedding_meta(const Tensor& x, const Tensor&, const Tensor&, at::TensorList, bool, int64_t, double, bool) { return at::empty_like(x); }
 std::tuple<Tensor, Tensor> gated_mlp_meta(const Tensor& s, const Tensor&, at::TensorList, int64_t) {
   return {at::empty({s.size(0), 1}, s.options()), at::empty({s.size(0), 3, 1}, s.options())};
 }
@@ -2441,6 +2479,8 @@ TORCH_LIBRARY(spk_hip, m) {
   m.def("so3_list_ok(Tensor Y, Tensor fcut, Tensor idx_i, Tensor idx_j, int n_atoms) -> int");
   // tensorial heads (atomistic/atomwise.py:91-293; csrc/spk_tensorial.hip), eval only: the gated equivariant MLP in one launch, the moments in one more
   m.def("gated_mlp(Tensor s, Tensor v, Tensor[] weights, int act) -> (Tensor, Tensor)");
+  // nn/embedding.py:239-349 (csrc/spk_eembed.hip), eval only: x0 (+)= the charge / spin embedding; psi [n_mol], idx_m ascending
+  m.def("electronic_embedding(Tensor x, Tensor psi, Tensor idx_m, Tensor[] weights, bool is_charged, int act, float eps, bool add_input) -> Tensor");
   m.def("dipole_moment(Tensor q, Tensor? d, Tensor R, Tensor idx_m, int n_mol, Tensor? total_charge, bool correct) -> (Tensor, Tensor)");
   m.def("polarizability(Tensor a0, Tensor d, Tensor R, Tensor idx_m, int n_mol) -> Tensor");
   m.def("potential_plan(Tensor idx_i, Tensor idx_j, int n_atoms, Tensor idx_m, int n_mol) -> int");
@@ -2508,6 +2548,7 @@ TORCH_LIBRARY_IMPL(spk_hip, CUDA, m) {   // "CUDA" is the dispatch key of ROCm d
   m.impl("so3_product_backward", so3_product_backward_raw);
   m.impl("so3_list_ok", so3_list_ok_op);
   m.impl("gated_mlp", gated_mlp_raw);
+  m.impl("electronic_embedding", electronic_embedding_raw);
   m.impl("dipole_moment", dipole_moment_raw);
   m.impl("polarizability", polarizability_raw);
   m.impl("potential_plan", potential_plan_op);
@@ -2557,7 +2598,7 @@ TORCH_LIBRARY_IMPL(spk_hip, CPU, m) {
                            "dense_forward", "dense_backward_input", "radial_cutoff_backward", "schnet_forward", "schnet_backward", "painn_forward",
                            "painn_backward", "atomwise_forward", "atomwise_backward", "edge_plan", "static_declare", "static_declare_range", "schnet_potential",
                            "schnet_potential_forward", "schnet_potential_backward", "schnet_potential_forces", "painn_potential_forces", "potential_plan",
-                           "schnet_potential_stress", "painn_potential_stress", "zbl", "zbl_backward", "zbl_forces", "gated_mlp",
+                           "schnet_potential_stress", "painn_potential_stress", "zbl", "zbl_backward", "zbl_forces", "gated_mlp", "electronic_embedding",
                            "dipole_moment", "polarizability", "coulomb", "coulomb_backward", "ewald_recip", "ewald_recip_backward",
                            "real_sph_harm", "real_sph_harm_backward", "so3_conv", "so3_conv_backward", "so3_product", "so3_product_backward", "so3_list_ok"})
     m.impl(name, torch::CppFunction::makeFromBoxedFunction<&no_cpu_boxed>());
@@ -2607,6 +2648,7 @@ TORCH_LIBRARY_IMPL(spk_hip, Meta, m) {
   m.impl("so3_product_backward", so3_product_backward_meta);
   m.impl("so3_list_ok", so3_list_ok_meta);
   m.impl("gated_mlp", gated_mlp_meta);
+  m.impl("electronic_embedding", electronic_embedding_meta);
   m.impl("dipole_moment", dipole_moment_meta);
   m.impl("polarizability", polarizability_meta);
   train_impl_meta(m);

@@ -147,7 +147,13 @@ def export_potential(model, path: Optional[str] = None) -> bytes:
     rbk, p0, p1 = rep.radial_basis.kernel_params()
     n_rbf, cutoff = int(rep.radial_basis.n_rbf), float(rep.cutoff_fn.cutoff_value())
     tensors: Dict[str, np.ndarray] = {}
-    tensors["embedding"] = _np(rep.embedding.weight)
+    if type(rep.embedding).__name__ == "NuclearEmbedding":      # its eval table: free rows + the linear map of the electron configuration
+        import torch
+        emb = rep.embedding
+        with torch.no_grad():
+            tensors["embedding"] = _np(emb.element_embedding + emb.config_linear(emb.electron_config))
+    else:
+        tensors["embedding"] = _np(rep.embedding.weight)
     tensors["rbf_p0"] = _np(p0).reshape(-1)
     tensors["rbf_p1"] = _np(p1).reshape(-1) if p1 is not None else np.zeros(int(n_rbf), np.float32)
     if kind_name == "SchNet":

@@ -177,6 +177,15 @@ def install(spk=None, verbose=False, fused_head=True, neighbor_lists=False, fuse
             _set(mod, name, getattr(S3, name), log)
     for mod in (getattr(spk, "representation", None), sub("representation.so3net")):
         _set(mod, "SO3net", R.SO3net, log)
+    # the nuclear / electronic embeddings and their residual blocks (when the reference has loaded them): same constructors, buffers and state_dict keys
+    for mod in (getattr(spk, "nn", None), sub("nn.embedding")):
+        _set(mod, "NuclearEmbedding", N.NuclearEmbedding, log)
+        _set(mod, "ElectronicEmbedding", N.ElectronicEmbedding, log)
+    for mod in (getattr(spk, "nn", None), sub("nn.blocks")):
+        for name in ("Residual", "ResidualStack", "ResidualMLP"):
+            _set(mod, name, getattr(N, name), log)
+    for mod in (sub("nn.embedding"),):      # (it did `from schnetpack.nn.blocks import ResidualMLP`)
+        _set(mod, "ResidualMLP", N.ResidualMLP, log)
     if fused_potential and fused_head:
         mb = sub("model.base")
         cls = getattr(mb, "NeuralNetworkPotential", None) if mb is not None else None

@@ -8,7 +8,7 @@ import torch.nn as nn
 from . import properties
 from .atomistic import (Aggregation, Atomwise, DipoleMoment, EnergyCoulomb, EnergyEwald, Forces, PairwiseDistances, Polarizability, Strain,
                         ZBLRepulsionEnergy)
-from .nn import CosineCutoff, GaussianRBF, BesselRBF
+from .nn import CosineCutoff, GaussianRBF, BesselRBF, NuclearEmbedding
 from .representation import PaiNN, SchNet
 
 __all__ = ["NeuralNetworkPotential", "build_model", "batch_to_inputs"]
@@ -180,6 +180,18 @@ def _zbl_add(zbl, inputs: Dict[str, torch.Tensor], n_mol: int, F: torch.Tensor, 
                                         inputs[properties.idx_m], n_mol, zbl.op_params(R), F, W)
 
 
+def embedding_table(rep) -> Optional[torch.Tensor]:
+    """The table that the force call looks the nuclear embedding rows up in, inside its first launch: the weight of a plain ``nn.Embedding`` or
+    the eval table of a ``NuclearEmbedding`` mirror in eval mode -- when there are no electronic embeddings.  None: the caller computes x0."""
+    if len(rep.electronic_embeddings) > 0:
+        return None
+    if type(rep.embedding) is nn.Embedding:
+        return rep.embedding.weight
+    if type(rep.embedding) is NuclearEmbedding and not rep.embedding.training:
+        return rep.embedding.embedding
+    return None
+
+
 def _potential_eval(model, inputs: Dict[str, torch.Tensor], layout: Optional[Tuple[int, int, int, int]], stress: bool) -> Dict[str, torch.Tensor]:
     """The eval body of modes 2 - 5: the one operator that the representation and ``stress`` select, the ZBL repulsion when a ``layout`` is given,
     stress = W / V under ``stress``, then the dict."""
@@ -192,11 +204,12 @@ def _potential_eval(model, inputs: Dict[str, torch.Tensor], layout: Optional[Tup
     n_mol = head._n_molecules(inputs, idx_m)
     kind, p0, p1 = rep.radial_basis.kernel_params()
     l0, l1 = head.outnet[0], head.outnet[1]
-    plain = type(rep.embedding) is nn.Embedding and len(rep.electronic_embeddings) == 0
+    table = embedding_table(rep)
+    plain = table is not None
     painn = isinstance(rep, PaiNN)
     op = getattr(torch.ops.spk_hip, ("painn" if painn else "schnet") + ("_potential_stress" if stress else "_potential_forces"))
     with torch.no_grad():
-        res = list(op(None if plain else rep.embed(inputs), rep.embedding.weight if plain else None, inputs[properties.Z], inputs[properties.R],
+        res = list(op(None if plain else rep.embed(inputs), table, inputs[properties.Z], inputs[properties.R],
                       inputs.get(properties.offsets), inputs[properties.idx_i], inputs[properties.idx_j], idx_m, n_mol, rep.interaction_weights(),
                       [l0.weight, l0.bias, l1.weight, l1.bias], *((rep.share_filters, rep.epsilon) if painn else (rep.n_filters,)), kind, p0, p1,
                       rep.cutoff_fn.cutoff_value(), head._head_act))

@@ -1,6 +1,7 @@
 from .activations import shifted_softplus
 from .base import Dense
-from .blocks import build_gated_equivariant_mlp, build_mlp
+from .blocks import Residual, ResidualMLP, ResidualStack, build_gated_equivariant_mlp, build_mlp
+from .embedding import ElectronicEmbedding, NuclearEmbedding
 from .equivariant import GatedEquivariantBlock
 from .cutoff import CosineCutoff, SwitchFunction, cosine_cutoff
 from .radial import BesselRBF, GaussianRBF, gaussian_rbf

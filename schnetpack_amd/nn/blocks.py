@@ -1,4 +1,5 @@
-"""Mirrors of ``schnetpack.nn.blocks.build_mlp`` (nn/blocks.py:12-76) and ``build_gated_equivariant_mlp`` (nn/blocks.py:79-156)."""
+"""Mirrors of ``schnetpack.nn.blocks.build_mlp`` (nn/blocks.py:12-76), ``build_gated_equivariant_mlp`` (nn/blocks.py:79-156) and the residual
+blocks ``Residual`` / ``ResidualStack`` / ``ResidualMLP`` (nn/blocks.py:159-296)."""
 from typing import Callable, Optional, Sequence, Tuple, Union
 
 import torch
@@ -8,7 +9,7 @@ from torch import nn
 from .base import Dense
 from .equivariant import GatedEquivariantBlock
 
-__all__ = ["build_mlp", "build_gated_equivariant_mlp"]
+__all__ = ["build_mlp", "build_gated_equivariant_mlp", "Residual", "ResidualStack", "ResidualMLP"]
 
 
 def build_mlp(n_in: int, n_out: int, n_hidden: Optional[Union[int, Sequence[int]]] = None,
@@ -68,3 +69,65 @@ def build_gated_equivariant_mlp(n_in: int, n_out: int, n_hidden: Optional[Union[
     layers.append(GatedEquivariantBlock(n_sin=sizes[-2], n_vin=sizes[-2], n_sout=sizes[-1], n_vout=sizes[-1], n_hidden=gating[-1],
                                         activation=activation, sactivation=None))
     return _GatedSequential(*layers)
+
+
+class Residual(nn.Module):
+    """Pre-activation residual block ``x + linear2(act(linear1(act(x))))``; ``linear1`` orthogonal, ``linear2`` zero (``zero_init``) or orthogonal,
+    biases zero.  Plain ATen: the block carries the weights, the electronic embedding's operator runs them (``nn/embedding.py``)."""
+
+    def __init__(self, num_features: int, activation: Union[Callable, nn.Module] = None, bias: bool = True, zero_init: bool = True) -> None:
+        super().__init__()
+        self.activation1 = activation
+        self.linear1 = nn.Linear(num_features, num_features, bias=bias)
+        self.activation2 = activation
+        self.linear2 = nn.Linear(num_features, num_features, bias=bias)
+        self.reset_parameters(bias, zero_init)
+
+    def reset_parameters(self, bias: bool = True, zero_init: bool = True) -> None:
+        nn.init.orthogonal_(self.linear1.weight)
+        if zero_init:
+            nn.init.zeros_(self.linear2.weight)
+        else:
+            nn.init.orthogonal_(self.linear2.weight)
+        if bias:
+            nn.init.zeros_(self.linear1.bias)
+            nn.init.zeros_(self.linear2.bias)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        return x + self.linear2(self.activation2(self.linear1(self.activation1(x))))
+
+
+class ResidualStack(nn.Module):
+    """``num_residual`` :class:`Residual` blocks in sequence (``stack``)."""
+
+    def __init__(self, num_features: int, num_residual: int, activation: Union[Callable, nn.Module], bias: bool = True, zero_init: bool = True) -> None:
+        super().__init__()
+        self.stack = nn.ModuleList([Residual(num_features, activation, bias, zero_init) for _ in range(num_residual)])
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        for residual in self.stack:
+            x = residual(x)
+        return x
+
+
+class ResidualMLP(nn.Module):
+    """``linear(act(residual(x)))``: a :class:`ResidualStack` (always zero-initialised, like the reference's) and an output layer that is
+    orthogonal or, with ``zero_init``, zero."""
+
+    def __init__(self, num_features: int, num_residual: int, activation: Union[Callable, nn.Module], bias: bool = True, zero_init: bool = False):
+        super().__init__()
+        self.residual = ResidualStack(num_features, num_residual, activation=activation, bias=bias, zero_init=True)
+        self.linear = nn.Linear(num_features, num_features, bias=bias)
+        self.activation = activation
+        self.reset_parameters(bias, zero_init)
+
+    def reset_parameters(self, bias: bool = True, zero_init: bool = False) -> None:
+        if zero_init:
+            nn.init.zeros_(self.linear.weight)
+        else:
+            nn.init.orthogonal_(self.linear.weight)
+        if bias:
+            nn.init.zeros_(self.linear.bias)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        return self.linear(self.activation(self.residual(x)))

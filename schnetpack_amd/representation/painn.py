@@ -17,6 +17,7 @@ from .. import properties
 from .. import torchops  # noqa: F401  (registers torch.ops.spk_hip)
 from ..nn import Dense, replicate_module, scatter_add
 from ..nn.base import activation_id
+from ..nn.embedding import embed_add
 from ..nn.fallback import note_fallback, use_aten
 
 __all__ = ["PaiNN", "PaiNNInteraction", "PaiNNMixing"]
@@ -186,7 +187,10 @@ class PaiNN(nn.Module):
     def embed(self, inputs: Dict[str, torch.Tensor]) -> torch.Tensor:
         q = self.embedding(inputs[properties.Z])
         for embedding in self.electronic_embeddings:
-            q = q + embedding(q, inputs)
+            if torch.jit.is_scripting():
+                q = q + embedding(q, inputs)
+            else:      # a mirror on its operator route adds q in the kernel's epilogue
+                q = embed_add(embedding, q, inputs)
         return q
 
     def forward(self, inputs: Dict[str, torch.Tensor]):
@@ -198,7 +202,10 @@ class PaiNN(nn.Module):
 
         q = self.embedding(atomic_numbers)
         for embedding in self.electronic_embeddings:
-            q = q + embedding(q, inputs)
+            if torch.jit.is_scripting():
+                q = q + embedding(q, inputs)
+            else:      # a mirror on its operator route adds q in the kernel's epilogue
+                q = embed_add(embedding, q, inputs)
 
         aten = use_aten(r_ij) or use_aten(q)
         if self._fused and not self.training and not aten:

@@ -22,6 +22,7 @@ from ..nn.fallback import note_fallback, use_aten
 from ..nn import replicate_module
 from ..nn.activations import shifted_softplus
 from ..nn.base import activation_id
+from ..nn.embedding import embed_add
 
 __all__ = ["SchNet", "SchNetInteraction"]
 
@@ -122,7 +123,10 @@ class SchNet(nn.Module):
         """x_0: nuclear embedding rows plus the electronic embeddings (schnet.py:160-165)."""
         x = self.embedding(inputs[properties.Z])
         for embedding in self.electronic_embeddings:
-            x = x + embedding(x, inputs)
+            if torch.jit.is_scripting():
+                x = x + embedding(x, inputs)
+            else:      # a mirror on its operator route adds x in the kernel's epilogue
+                x = embed_add(embedding, x, inputs)
         return x
 
     def interaction_weights(self) -> List[torch.Tensor]:

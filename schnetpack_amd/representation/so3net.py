@@ -17,6 +17,7 @@ from .. import properties
 from .. import torchops  # noqa: F401  (registers torch.ops.spk_hip)
 from ..nn import replicate_module
 from ..nn import so3
+from ..nn.embedding import embed_add
 from ..nn.fallback import use_aten
 
 __all__ = ["SO3net"]
@@ -54,6 +55,13 @@ class SO3net(nn.Module):
         self.gatings = replicate_module(lambda: so3.SO3ParametricGatedNonlinearity(n_atom_basis, lmax), self.n_interactions, shared_interactions)
         self.so3product = so3.SO3TensorProduct(lmax)
 
+    def embed(self, inputs: Dict[str, torch.Tensor]) -> torch.Tensor:
+        """x_0: nuclear embedding rows plus the electronic embeddings (so3net.py:130-132)."""
+        x0 = self.embedding(inputs[properties.Z])
+        for embedding in self.electronic_embeddings:      # a mirror on its operator route adds x0 in the kernel's epilogue
+            x0 = embed_add(embedding, x0, inputs)
+        return x0
+
     def forward(self, inputs: Dict[str, torch.Tensor]):
         atomic_numbers = inputs[properties.Z]
         r_ij = inputs[properties.Rij]
@@ -71,10 +79,7 @@ class SO3net(nn.Module):
         radial_ij = self.radial_basis(d_ij)
         cutoff_ij = self.cutoff_fn(d_ij)[..., None]
 
-        x0 = self.embedding(atomic_numbers)
-        for embedding in self.electronic_embeddings:
-            x0 = x0 + embedding(x0, inputs)
-        x0 = x0.unsqueeze(1)
+        x0 = self.embed(inputs).unsqueeze(1)
 
         x = so3.scalar2rsh(x0, int(self.lmax))
         for so3conv, mixing1, mixing2, gating, mixing3 in zip(self.so3convs, self.mixings1, self.mixings2, self.gatings, self.mixings3):

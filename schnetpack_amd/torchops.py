@@ -41,7 +41,7 @@ ops = load()
 
 OPERATORS = ["scatter_add", "gather", "pairwise", "pairwise_backward", "dense", "radial_cutoff", "schnet", "painn", "atomwise",
              "dense_forward", "dense_backward_input", "radial_cutoff_backward", "schnet_forward", "schnet_backward", "painn_forward",
-             "painn_backward", "atomwise_forward", "atomwise_backward", "schnet_potential", "schnet_potential_forward", "schnet_potential_backward", "schnet_potential_forces", "painn_potential_forces", "schnet_potential_stress", "painn_potential_stress", "eval_guard", "zbl", "zbl_backward", "zbl_forces", "coulomb", "coulomb_backward", "ewald_recip", "ewald_recip_backward", "real_sph_harm", "real_sph_harm_backward", "so3_conv", "so3_conv_backward", "so3_product", "so3_product_backward", "so3_list_ok", "gated_mlp", "dipole_moment", "polarizability", "potential_plan", "edge_plan", "edge_plan_install", "static_new", "static_release", "weights_changed", "static_declare", "static_declare_range", "static_refresh", "static_enable",
+             "painn_backward", "atomwise_forward", "atomwise_backward", "schnet_potential", "schnet_potential_forward", "schnet_potential_backward", "schnet_potential_forces", "painn_potential_forces", "schnet_potential_stress", "painn_potential_stress", "eval_guard", "zbl", "zbl_backward", "zbl_forces", "coulomb", "coulomb_backward", "ewald_recip", "ewald_recip_backward", "real_sph_harm", "real_sph_harm_backward", "so3_conv", "so3_conv_backward", "so3_product", "so3_product_backward", "so3_list_ok", "gated_mlp", "electronic_embedding", "dipole_moment", "polarizability", "potential_plan", "edge_plan", "edge_plan_install", "static_new", "static_release", "weights_changed", "static_declare", "static_declare_range", "static_refresh", "static_enable",
              "static_check", "static_clear", "clear_caches",
              # training regime: operators closed under differentiation (csrc/spk_torch_train.h)
              "act_mul", "linear", "matmul_nn", "matmul_tn", "cfconv", "edge_mul", "radial_d", "radial_c", "rowscale", "rowdot", "edge_norm", "vec3", "gemm_pair",
