@@ -19,6 +19,7 @@
 // On a symmetric neighbour list W_e == W_{e'} for the reversed edge, so gh is again a row-local
 // segmented reduction (gather gy of the neighbours); otherwise float atomics on gh[j].
 #include "spk_common.h"
+#include "spk_cfconv.h"
 #include "spk_split.h"
 #include "spk_filter_split.h"
 
@@ -1696,19 +1697,12 @@ int64_t spk_cfconv_gsave_floats(const spk_graph_t* g, const spk_radial_t* rb, in
   return tiles * 32 * (int64_t)nf;
 }
 
-// EXPERIMENT (spk_tabfilter.hip): layers with a registered filter table run the table-driven row kernels
-bool spk_filter_table_lookup(const float* key, const float** table, int* n_knots, float* d_max);
-extern "C" int spk_cfconv_tab_f32(const spk_graph_t* g, const float* r_ij, const float* h, const float* table, int32_t n_knots, float d_max,
-                                  float cutoff, int32_t nf, float* y, void* stream);
-int spk_cfconv_tab_bwd_internal(const spk_graph_t* g, const float* r_ij, const float* h, const float* gy, const float* table, int n_knots, float d_max,
-                                float cutoff, float* gh, float* gr, bool gr_assign, hipStream_t stream);
-
 int spk_cfconv_fwd_internal(const spk_graph_t* g, const spk_radial_t* rb, const float* h,
                             const float* r_ij, const float* w1, const float* b1, const float* w2,
                             const float* b2, int nf, float* y, hipStream_t stream, bool pre_zeroed,
                             float* gsave) {
   const char* who = "spk_schnet_cfconv_fwd_f32";
-  {
+  {  // EXPERIMENT (spk_tabfilter.hip): layers with a registered filter table run the table-driven row kernels
     const float* tab; int nk; float dmax;
     if (g && rb && nf == 128 && g->n_atoms > 0 && g->sorted && g->rowptr && h && r_ij && y && spk_filter_table_lookup(w2, &tab, &nk, &dmax))
       return spk_cfconv_tab_f32(g, r_ij, h, tab, nk, dmax, rb->cutoff, nf, y, stream);
@@ -1719,7 +1713,7 @@ int spk_cfconv_fwd_internal(const spk_graph_t* g, const spk_radial_t* rb, const 
   SPK_CHECK_ARG(nf >= 1 && nf % 4 == 0, "%s: n_filters=%d must be a multiple of 4", who, nf);
   if (g->n_atoms == 0) return SPK_OK;
   SPK_CHECK_ARG(y != nullptr, "%s: null output", who);
-  if (!pre_zeroed) { int _zr = spk_zero_async(y, (size_t)g->n_atoms * nf * sizeof(float), stream); if (_zr) return _zr; }
+  if (!pre_zeroed) SPK_TRY(spk_zero_async(y, (size_t)g->n_atoms * nf * sizeof(float), stream));
   if (g->n_edges == 0) return SPK_OK;
   SPK_CHECK_ARG(h && r_ij && w1 && b1 && w2 && b2, "%s: null pointer", who);
   CfArgs a;
@@ -1749,7 +1743,7 @@ int spk_cfconv_bwd_internal(const spk_graph_t* g, const spk_radial_t* rb, const 
   SPK_CHECK_ARG(nf >= 1 && nf % 4 == 0, "%s: n_filters=%d must be a multiple of 4", who, nf);
   if (g->n_atoms == 0) return SPK_OK;
   SPK_CHECK_ARG(gh != nullptr, "%s: null output", who);
-  if (!pre_zeroed) { int _zr = spk_zero_async(gh, (size_t)g->n_atoms * nf * sizeof(float), stream); if (_zr) return _zr; }
+  if (!pre_zeroed) SPK_TRY(spk_zero_async(gh, (size_t)g->n_atoms * nf * sizeof(float), stream));
   if (g->n_edges == 0) return SPK_OK;
   SPK_CHECK_ARG(h && gy && r_ij && w1 && b1 && w2 && b2 && gr, "%s: null pointer", who);
   CfArgs a;

@@ -12,6 +12,7 @@
 // (backward chains).  The kernel can also zero a buffer for the following edge kernel, which
 // replaces a separate memset launch.
 #include "spk_common.h"
+#include "spk_dense.h"
 #include "spk_split.h"
 
 #define CH_MAXL 3
@@ -523,18 +524,6 @@ __global__ __launch_bounds__(256, 2) void k_dense_chain_sp(ChainArgs a, int ld0,
   }
 }
 
-// Split images of the chain that is about to be launched: spk_apply_pack (spk_pack.h) notes, per layer, the split image that belongs to the packed fp32
-// image it put into the chain; spk_dense_chain_f32 -- called next on the same host thread -- takes them only if every layer's `w` is exactly the noted
-// packed pointer, and forgets them on the way out.  (Not a global pointer map: a chain handed to the C ABI with its own packed buffer must never meet the
-// split image of a freed model whose buffer address it happens to reuse.)
-struct ChainSplitNote { const float* packed[CH_MAXL]; const float* split[CH_MAXL]; int n; };
-static thread_local ChainSplitNote g_split_note = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}, 0};
-void spk_note_split_images(const float* const* packed, const float* const* split, int n) {
-  g_split_note.n = n > CH_MAXL ? 0 : n;
-  for (int l = 0; l < g_split_note.n; ++l) { g_split_note.packed[l] = packed[l]; g_split_note.split[l] = split[l]; }
-}
-struct ChainSplitNoteClear { ~ChainSplitNoteClear() { g_split_note.n = 0; } };
-
 // ---- packed weight image ------------------------------------------------------------------
 // w is a Linear weight [n_out, k_in].  transposed == 0: the layer y = x W^T (A[i][kk] = W[i][kk], contraction
 // over k_in); transposed == 1: the input-gradient layer gx = gy W (A[i][kk] = W[kk][i], contraction over n_out).
@@ -587,7 +576,6 @@ int spk_pack_weight_split_internal(const float* w, int n_out, int k_in, int tran
   return SPK_OK;
 }
 
-int spk_pack_weight_internal(const float* w, int n_out, int k_in, int transposed, float* packed, hipStream_t stream);
 extern "C" int spk_pack_weight_f32(const float* w, int32_t n_out, int32_t k_in, int32_t transposed, float* packed, void* stream_) {
   return spk_pack_weight_internal(w, n_out, k_in, transposed, packed, (hipStream_t)stream_);
 }
@@ -608,10 +596,6 @@ extern "C" void spk_chain_set_rows(int rows) { g_chain_rows = (rows == 16 || row
 // ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
-int spk_dense_internal(const float* in, const float* pre_in, const float* w, const float* b,
-                       const float* res, float* out, float* pre_out, int64_t M, int KC, int NW,
-                       int act, bool trans, int pro, hipStream_t stream);
-
 static bool al16(const void* p) { return p == nullptr || ((uintptr_t)p % 16) == 0; }
 
 // true if the fused kernel can run this chain
@@ -630,9 +614,7 @@ static bool chain_supported(const spk_chain_t* c) {
   return true;
 }
 
-extern "C" int spk_dense_chain_f32(const spk_chain_t* c, void* stream_) {
-  ChainSplitNoteClear forget_note_on_exit;
-  hipStream_t stream = (hipStream_t)stream_;
+int spk_dense_chain_launch(const spk_chain_t* c, const float* const* w_split, hipStream_t stream) {
   const char* who = "spk_dense_chain_f32";
   SPK_CHECK_ARG(c != nullptr && c->n_layers >= 1 && c->n_layers <= CH_MAXL, "%s: 1..%d layers", who, CH_MAXL);
   SPK_CHECK_ARG(c->m >= 0, "%s: negative row count", who);
@@ -670,15 +652,11 @@ extern "C" int spk_dense_chain_f32(const spk_chain_t* c, void* stream_) {
     const int64_t ntiles32 = (c->m + 31) / 32;
     const bool rows16 = g_chain_rows ? (g_chain_rows == 16) : (ntiles32 < 2 * (int64_t)spk_num_cus());
     SpkProfScope prof(c->n_layers == 1 ? "chain1" : (c->n_layers == 2 ? "chain2" : "chain3"), stream);
-    bool split = !rows16 && spk_get_split() != 0 && g_split_note.n == c->n_layers;
-    const float* wsp[CH_MAXL] = {nullptr, nullptr, nullptr};
-    for (int l = 0; l < c->n_layers && split; ++l) {
-      wsp[l] = (c->layers[l].k % 64 == 0 && g_split_note.packed[l] == c->layers[l].w) ? g_split_note.split[l] : nullptr;
-      if (!wsp[l]) split = false;
-    }
+    bool split = !rows16 && spk_get_split() != 0 && w_split != nullptr;
+    for (int l = 0; l < c->n_layers && split; ++l) split = w_split[l] != nullptr && c->layers[l].k % 64 == 0;
     if (split) {
       // split-precision form (round 6): same launch geometry, activations as fp16 (high, low) images in LDS
-      for (int l = 0; l < c->n_layers; ++l) a.L[l].w = wsp[l];
+      for (int l = 0; l < c->n_layers; ++l) a.L[l].w = w_split[l];
       const int ldh0 = w0 + 8, ldh1 = w1 + 8;
       static SpkPerDevice attr_sp;
       int attr_sp_dev;
@@ -705,7 +683,7 @@ extern "C" int spk_dense_chain_f32(const spk_chain_t* c, void* stream_) {
   // general path: layer by layer on the single-layer kernels (any shape)
   for (int l = 0; l < c->n_layers; ++l)
     SPK_CHECK_ARG(c->layers[l].trans != 2, "%s: packed weights (trans == 2) need k %% 128 == 0, n_out %% 32 == 0, widths <= %d, 16-byte aligned buffers and a variant other than 'simple'", who, CH_MAXW);
-  if (c->zero_ptr && c->zero_count > 0) { int _zr = spk_zero_async(c->zero_ptr, (size_t)c->zero_count * sizeof(float), stream); if (_zr) return _zr; }
+  if (c->zero_ptr && c->zero_count > 0) SPK_TRY(spk_zero_async(c->zero_ptr, (size_t)c->zero_count * sizeof(float), stream));
   if (c->m == 0) return SPK_OK;
   SPK_CHECK_ARG(c->in != nullptr, "%s: null input", who);
   const float* cur = c->in;
@@ -719,11 +697,13 @@ extern "C" int spk_dense_chain_f32(const spk_chain_t* c, void* stream_) {
       SPK_CHECK_ARG(!last && c->tmp[l & 1] != nullptr, "%s: layer %d needs an output or a temporary buffer", who, l);
       dst = c->tmp[l & 1];
     }
-    int rc = spk_dense_internal(cur, cur_pre, S.w, S.b, S.res, dst, S.pre_out, c->m, S.k, S.n_out, S.act, S.trans != 0, cur_act, stream);
-    if (rc) return rc;
+    SPK_TRY(spk_dense_internal(cur, cur_pre, S.w, S.b, S.res, dst, S.pre_out, c->m, S.k, S.n_out, S.act, S.trans != 0, cur_act, stream));
     cur = dst;
     cur_pre = S.post_pre;
     cur_act = S.post_pre ? S.post_act : SPK_ACT_NONE;
   }
   return SPK_OK;
 }
+
+// a chain handed to the C ABI carries no split images: it runs the fp32 kernels
+extern "C" int spk_dense_chain_f32(const spk_chain_t* c, void* stream) { return spk_dense_chain_launch(c, nullptr, (hipStream_t)stream); }

@@ -37,6 +37,9 @@ void spk_set_error(const char* fmt, ...);
 
 #define SPK_LAUNCH_CHECK() SPK_HIP_TRY(hipGetLastError())
 
+// pass a non-zero status of a library call on to the caller
+#define SPK_TRY(expr) do { int _rc = (expr); if (_rc) return _rc; } while (0)
+
 static inline int spk_grid_for(int64_t work_items, int per_block, int max_blocks) {
   int64_t b = (work_items + per_block - 1) / per_block;
   if (b < 1) b = 1;

@@ -21,8 +21,6 @@
 #include <math.h>
 #include "spk_common.h"
 
-#define SPK_TRY(expr) do { int _rc = (expr); if (_rc) return _rc; } while (0)
-
 namespace {
 
 constexpr int kCoulLanes = 16;

@@ -13,6 +13,7 @@
 //   accumulator tile can be fed straight back as the B operand of the next layer (chained GEMMs
 //   without leaving registers) -- used by the fused cfconv kernels.
 #include "spk_common.h"
+#include "spk_dense.h"
 #include "spk_gemm_tn.h"
 
 // One chunk = 8 k-blocks (64 contraction indices): 8 A + 8 B 16-byte operands per lane.  All loads
@@ -390,7 +391,6 @@ extern "C" int spk_dense_bwd_input_f32(const float* dy, const float* pre, const 
                         (hipStream_t)stream, "spk_dense_bwd_input_f32");
 }
 
-extern "C" int spk_gemm_tn_plan(int64_t n, int32_t O, int32_t K, int32_t* n_slices, int64_t* ws_floats, int32_t* n_tiles);
 // out [m, n_out] = a w^T (trans = 0: a [m, k], w [n_out, k]) or out [m, k] = a w (trans = 1: a [m, n_out], w [n_out, k]),
 // and G [O, K] = U^T X, gb [O] = column sums of U (U [n, O], X [n, K]) -- both in one launch.  Returns SPK_ERR_ARG when the
 // first product does not fit the MFMA tiles (widths that are not multiples of 4): call the two entry points separately then.
@@ -697,7 +697,7 @@ extern "C" int spk_atomwise_fwd_f32(const float* x, const float* w1, const float
   SPK_CHECK_ARG(spk_atomwise_supported(n_in, n_hidden, act), "spk_atomwise_fwd_f32: head %d -> %d -> 1 (act %d) not supported by the fused kernel", n_in, n_hidden, act);
   SPK_CHECK_ARG((E == nullptr) == (idx_m == nullptr), "spk_atomwise_fwd_f32: E and idx_m go together");
   SPK_CHECK_ARG(E != nullptr || y_atom != nullptr, "spk_atomwise_fwd_f32: no output requested");
-  if (E && n_mol > 0) { int _zr = spk_zero_async(E, (size_t)n_mol * sizeof(float), stream); if (_zr) return _zr; }
+  if (E && n_mol > 0) SPK_TRY(spk_zero_async(E, (size_t)n_mol * sizeof(float), stream));
   if (n_atoms == 0) return SPK_OK;
   SPK_CHECK_ARG(x && w1 && w2, "spk_atomwise_fwd_f32: null pointer");
   SPK_CHECK_ARG(aligned16(x) && aligned16(w1) && aligned16(w2) && aligned16(pre), "spk_atomwise_fwd_f32: 16-byte alignment required");

@@ -8,7 +8,6 @@ constexpr int kMaxChain = 16;
 
 struct YsSteps { float dt[kMaxOrder]; };
 
-#define SPK_TRY(expr) do { int _rc = (expr); if (_rc) return _rc; } while (0)
 
 __device__ __forceinline__ void spk_philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t (&out)[4]) {
 #pragma unroll

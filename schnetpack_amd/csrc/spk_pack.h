@@ -1,11 +1,12 @@
 // Packed weight images of a whole model (see spk_pack_weight_f32 in spk_chain.hip): the drivers of the
 // fused representations keep, next to every Linear weight W [n_out, k_in], the packed image of the
 // forward layer (A = W) and of the input-gradient layer (A = W^T) in ONE caller-owned buffer `wpack`,
-// laid out in the order of the table built here.  spk_apply_pack() rewrites the layers of a chain to the
-// packed images when every layer has one.
+// laid out in the order of the table built here.  spk_chain_run() launches a chain on the packed images
+// when every layer has one.
 #pragma once
 #include <vector>
 #include "spk_common.h"
+#include "spk_dense.h"
 
 struct SpkPackEntry {
   const float* raw;    // W [n_out, k_in]
@@ -43,9 +44,6 @@ struct SpkPackTable {
   }
 };
 
-int spk_pack_weight_internal(const float* w, int n_out, int k_in, int transposed, float* packed, hipStream_t stream);
-int spk_pack_weight_split_internal(const float* w, int n_out, int k_in, int transposed, float* packed, hipStream_t stream);
-
 static inline int spk_pack_all(const SpkPackTable& T, float* wpack, hipStream_t stream) {
   for (const SpkPackEntry& x : T.e) {
     int rc = spk_pack_weight_internal(x.raw, x.n_out, x.k_in, 0, wpack + x.off_fwd, stream);
@@ -77,11 +75,10 @@ static inline const float* spk_packed_split_of(const SpkPackTable& T, const floa
   return nullptr;
 }
 
-// (spk_chain.hip) split images of the chain that is launched next on this host thread: the launcher takes the split-precision kernel when every layer has one
-void spk_note_split_images(const float* const* packed, const float* const* split, int n);
-
-static inline void spk_apply_pack(spk_chain_t& c, const SpkPackTable& T) {
-  if (!T.base || spk_get_variant() == SPK_VARIANT_SIMPLE) return;
+// Runs the chain `c` (spk_dense_chain_launch): when every layer has a packed image in the table, the layers are rewritten to the images
+// (trans = 2) and the launcher is handed the split-precision images that belong to them.
+static inline int spk_chain_run(spk_chain_t& c, const SpkPackTable& T, hipStream_t stream) {
+  if (!T.base || spk_get_variant() == SPK_VARIANT_SIMPLE) return spk_dense_chain_launch(&c, nullptr, stream);
   const float* repl[3] = {nullptr, nullptr, nullptr};
   const float* repl_s[3] = {nullptr, nullptr, nullptr};
   for (int l = 0; l < c.n_layers; ++l) {
@@ -92,9 +89,8 @@ static inline void spk_apply_pack(spk_chain_t& c, const SpkPackTable& T) {
       else if (L.trans == 1 && L.w == x.raw && L.k == x.n_out && L.n_out == x.k_in) { repl[l] = T.base + x.off_bwd; repl_s[l] = x.off_bwd_s >= 0 ? T.base + x.off_bwd_s : nullptr; }
       if (repl[l]) break;
     }
-    if (!repl[l]) return;
+    if (!repl[l]) return spk_dense_chain_launch(&c, nullptr, stream);
   }
-  bool all_split = true;
-  for (int l = 0; l < c.n_layers; ++l) { c.layers[l].w = repl[l]; c.layers[l].trans = 2; if (!repl_s[l]) all_split = false; }
-  if (all_split) spk_note_split_images(repl, repl_s, c.n_layers);
+  for (int l = 0; l < c.n_layers; ++l) { c.layers[l].w = repl[l]; c.layers[l].trans = 2; }
+  return spk_dense_chain_launch(&c, repl_s, stream);
 }

@@ -8,11 +8,7 @@
 // Phi_e = (phi(d_e) Wf^T + bf) fcut(d_e) is recomputed per edge from register-resident weights
 // (n_rbf <= NRBF FMAs per channel); the reference's [E, 3F n_int] filter tensor never exists.
 #include "spk_common.h"
-
-int spk_dense_internal(const float* in, const float* pre_in, const float* w, const float* b,
-                       const float* res, float* out, float* pre_out, int64_t M, int KC, int NW,
-                       int act, bool trans, int pro, hipStream_t stream);
-
+#include "spk_cfconv.h"
 #include "spk_painn_msg.h"
 #include "spk_painn_blk.h"
 
@@ -420,7 +416,6 @@ static int check_msg(const spk_graph_t* g, const spk_radial_t* rb, int F, const 
 }
 
 // EXPERIMENT (spk_tabfilter.hip): filter tables attached to an interaction by the address of its filter rows
-bool spk_filter_table_lookup(const float* key, const float** table, int* n_knots, float* d_max);
 
 static int g_row_table = -1;     // -1: rule (large lists), 0 / 1: never / whenever the shape has the instance
 extern "C" void spk_painn_set_row_table(int32_t mode) { g_row_table = mode; }
@@ -504,7 +499,7 @@ static int msg_dispatch(const MsgArgs& a_in, bool row_ok, hipStream_t stream, co
     SPK_HIP_TRY(hipMemcpyAsync(a.q_out, a.q, nf * sizeof(float), hipMemcpyDeviceToDevice, stream));
     SPK_HIP_TRY(hipMemcpyAsync(a.mu_out, a.mu, 3 * nf * sizeof(float), hipMemcpyDeviceToDevice, stream));
   } else {
-    { int _zr = spk_zero_async(a.gc, 3 * nf * sizeof(float), stream); if (_zr) return _zr; }
+    SPK_TRY(spk_zero_async(a.gc, 3 * nf * sizeof(float), stream));
     SPK_HIP_TRY(hipMemcpyAsync(a.gmu, a.gmu_out, 3 * nf * sizeof(float), hipMemcpyDeviceToDevice, stream));
   }
   if (a.E == 0) return SPK_OK;
@@ -1532,8 +1527,6 @@ extern "C" int spk_painn_mix_ctx_bwd_f32(const float* mix, const float* g_ctx, c
 // ------------------------------------------------------------------------------------------
 // whole-representation drivers (representation/painn.py:207-256), eval-mode force path
 // ------------------------------------------------------------------------------------------
-#define SPK_TRY(expr) do { int _rc = (expr); if (_rc) return _rc; } while (0)
-
 #include "spk_pack.h"
 // order of the packed images in spk_painn_t::wpack: per interaction ctx.0, ctx.1, mu_channel_mix, intra ctx.0, intra ctx.1
 static bool painn_pack_shapes_ok(const spk_painn_t* m) { return m->n_atom_basis == 128; }   // widths F, 2F, 3F <= 384, all % 128
@@ -1558,20 +1551,6 @@ extern "C" int64_t spk_painn_packed_floats(const spk_painn_t* m) {
 extern "C" int spk_painn_pack_weights_f32(const spk_painn_t* m, float* wpack, void* stream) {
   SPK_CHECK_ARG(m && wpack && spk_painn_packed_floats(m) > 0, "spk_painn_pack_weights_f32: model shapes have no packed form (see spk_painn_packed_floats)");
   return spk_pack_all(painn_pack_table(m), wpack, (hipStream_t)stream);
-}
-
-static spk_chain_layer_t mk_layer(const float* w, const float* b, const float* res, float* out, float* pre_out,
-                                  const float* post_pre, int k, int n_out, int act, int trans, int post_act) {
-  spk_chain_layer_t L;
-  L.w = w; L.b = b; L.res = res; L.out = out; L.pre_out = pre_out; L.post_pre = post_pre;
-  L.k = k; L.n_out = n_out; L.act = act; L.trans = trans; L.post_act = post_act;
-  return L;
-}
-
-static spk_chain_layer_t mk_fwd(const float* w, const float* wT, const float* b, float* out, float* pre_out,
-                                int k, int n_out, int act) {
-  return wT ? mk_layer(wT, b, nullptr, out, pre_out, nullptr, k, n_out, act, 1, 0)
-            : mk_layer(w, b, nullptr, out, pre_out, nullptr, k, n_out, act, 0, 0);
 }
 
 // molecule-resident kernels (spk_painn_mol.hip): block-diagonal lists with <= 32 atoms per block, F = 128
@@ -1619,7 +1598,7 @@ extern "C" int spk_painn_forward_f32(const spk_painn_t* m, const spk_graph_t* g,
   const size_t nf = (size_t)N * F;
   if (L == 0) {
     SPK_HIP_TRY(hipMemcpyAsync(q_out, q0, nf * sizeof(float), hipMemcpyDeviceToDevice, stream));
-    { int _zr = spk_zero_async(mu_out, 3 * nf * sizeof(float), stream); if (_zr) return _zr; }
+    SPK_TRY(spk_zero_async(mu_out, 3 * nf * sizeof(float), stream));
     return SPK_OK;
   }
   if (ptab.base && r_ij && !getenv("SPK_NO_PAINN_MOL_FWD") && !painn_tabulated(m) && spk_painn_mol_eligible(m, g, rb))      // batches of small molecules: the whole forward is ONE launch
@@ -1632,7 +1611,7 @@ extern "C" int spk_painn_forward_f32(const spk_painn_t* m, const spk_graph_t* g,
   const int64_t per = painn_saved_per_atom(F) * N;
   const bool blk = painn_blocks_prepare(g, rb, r_ij, F, false, stream);     // per-call edge tables of the block kernels, once for all interactions
   // mu entering the first interaction is zero (painn.py:246)
-  { int _zr = spk_zero_async(saved + 4 * nf, 3 * nf * sizeof(float), stream); if (_zr) return _zr; }
+  SPK_TRY(spk_zero_async(saved + 4 * nf, 3 * nf * sizeof(float), stream));
   for (int l = 0; l < L; ++l) {
     const spk_painn_layer_t& P = m->layers[l];
     float* S = saved + l * per;
@@ -1642,10 +1621,9 @@ extern "C" int spk_painn_forward_f32(const spk_painn_t* m, const spk_graph_t* g,
     {  // c = ctx_w2 silu(ctx_w1 q + b1) + b2   (one launch)
       spk_chain_t ch = {};
       ch.n_layers = 2; ch.m = N; ch.in = qin; ch.tmp[0] = c1; ch.tmp[1] = a1;
-      ch.layers[0] = mk_fwd(P.ctx_w1, P.ctx_w1T, P.ctx_b1, nullptr, preA, F, F, SPK_ACT_SILU);
-      ch.layers[1] = mk_fwd(P.ctx_w2, P.ctx_w2T, P.ctx_b2, c, nullptr, F, 3 * F, SPK_ACT_NONE);
-      spk_apply_pack(ch, ptab);
-      SPK_TRY(spk_dense_chain_f32(&ch, stream));
+      ch.layers[0] = spk_chain_fwd_layer(P.ctx_w1, P.ctx_w1T, P.ctx_b1, nullptr, nullptr, preA, F, F, SPK_ACT_SILU);
+      ch.layers[1] = spk_chain_fwd_layer(P.ctx_w2, P.ctx_w2T, P.ctx_b2, nullptr, c, nullptr, F, 3 * F, SPK_ACT_NONE);
+      SPK_TRY(spk_chain_run(ch, ptab, stream));
     }
     SPK_TRY(spk_painn_message_fwd_internal(g, rb, c, qin, mu_in, r_ij, P.filt_w, P.filt_b, F, q1, mu1, stream, l == 0, blk));   // mu_in == 0 for l == 0
     float* mu_next = (l == L - 1) ? mu_out : (saved + (l + 1) * per + 4 * nf);
@@ -1663,18 +1641,16 @@ extern "C" int spk_painn_forward_f32(const spk_painn_t* m, const spk_graph_t* g,
     {  // mix = mu1 W_mix^T over [3N, F]
       spk_chain_t ch = {};
       ch.n_layers = 1; ch.m = 3 * N; ch.in = mu1;
-      ch.layers[0] = mk_fwd(P.mix_w, P.mix_wT, nullptr, mix, nullptr, F, 2 * F, SPK_ACT_NONE);
-      spk_apply_pack(ch, ptab);
-      SPK_TRY(spk_dense_chain_f32(&ch, stream));
+      ch.layers[0] = spk_chain_fwd_layer(P.mix_w, P.mix_wT, nullptr, nullptr, mix, nullptr, F, 2 * F, SPK_ACT_NONE);
+      SPK_TRY(spk_chain_run(ch, ptab, stream));
     }
     SPK_TRY(spk_painn_mix_ctx_f32(q1, mix, N, F, m->epsilon, ctx, stream));
     {  // a = ictx_w2 silu(ictx_w1 ctx + b1) + b2
       spk_chain_t ch = {};
       ch.n_layers = 2; ch.m = N; ch.in = ctx; ch.tmp[0] = c1; ch.tmp[1] = a1;
-      ch.layers[0] = mk_fwd(P.ictx_w1, P.ictx_w1T, P.ictx_b1, nullptr, preB, 2 * F, F, SPK_ACT_SILU);
-      ch.layers[1] = mk_fwd(P.ictx_w2, P.ictx_w2T, P.ictx_b2, av, nullptr, F, 3 * F, SPK_ACT_NONE);
-      spk_apply_pack(ch, ptab);
-      SPK_TRY(spk_dense_chain_f32(&ch, stream));
+      ch.layers[0] = spk_chain_fwd_layer(P.ictx_w1, P.ictx_w1T, P.ictx_b1, nullptr, nullptr, preB, 2 * F, F, SPK_ACT_SILU);
+      ch.layers[1] = spk_chain_fwd_layer(P.ictx_w2, P.ictx_w2T, P.ictx_b2, nullptr, av, nullptr, F, 3 * F, SPK_ACT_NONE);
+      SPK_TRY(spk_chain_run(ch, ptab, stream));
     }
     SPK_TRY(spk_painn_mix_update_f32(q1, mu1, mix, av, N, F, q_out, mu_next, stream));
   }
@@ -1695,7 +1671,7 @@ extern "C" int spk_painn_backward_f32(const spk_painn_t* m, const spk_graph_t* g
     return spk_painn_mol_backward(m, g, rb, ptab, gq_out, gmu_out, r_ij, saved, scratch, gr, gq0, stream);      // ONE launch, every gr entry written once
   if (E > 0) {
     SPK_CHECK_ARG(gr != nullptr, "%s: null gr", who);
-    { int _zr = spk_zero_async(gr, (size_t)E * 3 * sizeof(float), stream); if (_zr) return _zr; }
+    SPK_TRY(spk_zero_async(gr, (size_t)E * 3 * sizeof(float), stream));
   }
   if (N == 0) return SPK_OK;
   SPK_CHECK_ARG((gq_out || gmu_out) && (L == 0 || (saved && scratch)), "%s: null buffer", who);
@@ -1712,9 +1688,9 @@ extern "C" int spk_painn_backward_f32(const spk_painn_t* m, const spk_graph_t* g
   float* gq = gc1 + nf;            // [N,F]   running dL/dq
   float* gmu = gq + nf;            // [N,3F]  running dL/dmu
   if (gq_out) SPK_HIP_TRY(hipMemcpyAsync(gq, gq_out, nf * sizeof(float), hipMemcpyDeviceToDevice, stream));
-  else { int _zr = spk_zero_async(gq, nf * sizeof(float), stream); if (_zr) return _zr; }
+  else SPK_TRY(spk_zero_async(gq, nf * sizeof(float), stream));
   if (gmu_out) SPK_HIP_TRY(hipMemcpyAsync(gmu, gmu_out, 3 * nf * sizeof(float), hipMemcpyDeviceToDevice, stream));
-  else { int _zr = spk_zero_async(gmu, 3 * nf * sizeof(float), stream); if (_zr) return _zr; }
+  else SPK_TRY(spk_zero_async(gmu, 3 * nf * sizeof(float), stream));
   const int64_t per = painn_saved_per_atom(F) * N;
   const bool blk = painn_blocks_prepare(g, rb, r_ij, F, true, stream);
   for (int l = L - 1; l >= 0; --l) {
@@ -1737,19 +1713,17 @@ extern "C" int spk_painn_backward_f32(const spk_painn_t* m, const spk_graph_t* g
     {  // g_ctx = ((ga W_d) * silu'(preB)) W_c
       spk_chain_t ch = {};
       ch.n_layers = 2; ch.m = N; ch.in = ga; ch.tmp[0] = ga1; ch.tmp[1] = gc1;
-      ch.layers[0] = mk_layer(P.ictx_w2, nullptr, nullptr, nullptr, nullptr, preB, 3 * F, F, SPK_ACT_NONE, 1, SPK_ACT_SILU);
-      ch.layers[1] = mk_layer(P.ictx_w1, nullptr, nullptr, gctx, nullptr, nullptr, F, 2 * F, SPK_ACT_NONE, 1, 0);
-      spk_apply_pack(ch, ptab);
-      SPK_TRY(spk_dense_chain_f32(&ch, stream));
+      ch.layers[0] = spk_chain_layer(P.ictx_w2, nullptr, nullptr, nullptr, nullptr, preB, 3 * F, F, SPK_ACT_NONE, 1, SPK_ACT_SILU);
+      ch.layers[1] = spk_chain_layer(P.ictx_w1, nullptr, nullptr, gctx, nullptr, nullptr, F, 2 * F, SPK_ACT_NONE, 1, 0);
+      SPK_TRY(spk_chain_run(ch, ptab, stream));
     }
     SPK_TRY(spk_painn_mix_ctx_bwd_f32(mix, gctx, gq, N, F, m->epsilon, gmix, gq1, stream));
     }
     {  // mu1 -> mix is a bias-free Dense over [3N, F]; residual path adds gmu
       spk_chain_t ch = {};
       ch.n_layers = 1; ch.m = 3 * N; ch.in = gmix;
-      ch.layers[0] = mk_layer(P.mix_w, nullptr, gmu, gmu1, nullptr, nullptr, 2 * F, F, SPK_ACT_NONE, 1, 0);
-      spk_apply_pack(ch, ptab);
-      SPK_TRY(spk_dense_chain_f32(&ch, stream));
+      ch.layers[0] = spk_chain_layer(P.mix_w, nullptr, gmu, gmu1, nullptr, nullptr, 2 * F, F, SPK_ACT_NONE, 1, 0);
+      SPK_TRY(spk_chain_run(ch, ptab, stream));
     }
     // ---- message backward: gc, gmu (incl. residual), gr +=
     // (first interaction without dL/dq0, the eval path: only the geometry gradient is formed and the context-net
@@ -1761,10 +1735,9 @@ extern "C" int spk_painn_backward_f32(const spk_painn_t* m, const spk_graph_t* g
       float* out = (l == 0 && gq0) ? gq0 : gq;
       spk_chain_t ch = {};
       ch.n_layers = 2; ch.m = N; ch.in = gc; ch.tmp[0] = ga1; ch.tmp[1] = gc1;
-      ch.layers[0] = mk_layer(P.ctx_w2, nullptr, nullptr, nullptr, nullptr, preA, 3 * F, F, SPK_ACT_NONE, 1, SPK_ACT_SILU);
-      ch.layers[1] = mk_layer(P.ctx_w1, nullptr, gq1, out, nullptr, nullptr, F, F, SPK_ACT_NONE, 1, 0);
-      spk_apply_pack(ch, ptab);
-      SPK_TRY(spk_dense_chain_f32(&ch, stream));
+      ch.layers[0] = spk_chain_layer(P.ctx_w2, nullptr, nullptr, nullptr, nullptr, preA, 3 * F, F, SPK_ACT_NONE, 1, SPK_ACT_SILU);
+      ch.layers[1] = spk_chain_layer(P.ctx_w1, nullptr, gq1, out, nullptr, nullptr, F, F, SPK_ACT_NONE, 1, 0);
+      SPK_TRY(spk_chain_run(ch, ptab, stream));
     }
   }
   return SPK_OK;
@@ -1799,7 +1772,7 @@ static int painn_potential_forces(const spk_painn_t* m, const spk_head_t* head, 
   SPK_CHECK_ARG(painn_potential_ok(m, head, g, rb), "%s: model / list not covered by the fused potential (see spk_painn_potential_supported)", who);
   SPK_CHECK_ARG(n_mol >= 0 && (n_mol == 0 || E), "%s: null energy buffer", who);
   SPK_CHECK_ARG(q0 || (emb && Z && n_types > 0), "%s: neither features nor an embedding table", who);
-  if (n_mol > 0 && !all_inside) { int zr = spk_zero_async(E, (size_t)n_mol * sizeof(float), stream); if (zr) return zr; }
+  if (n_mol > 0 && !all_inside) SPK_TRY(spk_zero_async(E, (size_t)n_mol * sizeof(float), stream));
   if (g->n_atoms == 0) return SPK_OK;
   SPK_CHECK_ARG(R && idx_m && q_out && mu_out && (F || gr) && pre_h && saved && scratch, "%s: null buffer", who);
   PmHeadDev h;

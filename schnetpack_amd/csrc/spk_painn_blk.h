@@ -2,10 +2,6 @@
 #pragma once
 #include "spk_painn_msg.h"
 
-#ifndef SPK_TRY
-#define SPK_TRY(expr) do { int _rc = (expr); if (_rc) return _rc; } while (0)
-#endif
-
 // true if the block kernels cover this shape / list (a usable plan hangs on the graph, F % 16 == 0, n_rbf <= 32, ...)
 bool spk_painn_blk_ok(const MsgArgs& a, bool bwd);
 // per-call edge tables (A, A', records) from r_ij: once per force call (the drivers) or per message call (a.blocks_prepared == 0)

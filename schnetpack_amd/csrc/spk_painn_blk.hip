@@ -747,7 +747,7 @@ extern "C" int spk_blocks_build(const spk_graph_t* g, int32_t n_rbf, int32_t cap
   out->n_groups = ng; out->cap = cap; out->ks = n_rbf <= 20 ? 5 : 8; out->ok = 0; out->max_unique = 0; out->n_tiles = 0; out->n_blocks = 0;
   host_stats[0] = host_stats[1] = host_stats[2] = host_stats[3] = 0;
   if (N == 0) { out->ok = 1; return SPK_OK; }
-  { int zr = spk_zero_async(dev_stats, 4 * sizeof(int32_t), stream); if (zr) return zr; }
+  SPK_TRY(spk_zero_async(dev_stats, 4 * sizeof(int32_t), stream));
   hipLaunchKernelGGL(k_blk_plan, dim3(ng), dim3(256), 0, stream, g->idx_j, g->rowptr, N, cap, (int32_t*)out->sub_n, (int32_t*)out->sub_u, (int32_t*)out->uniq,
                      (uint16_t*)out->jl, dev_stats);
   SPK_LAUNCH_CHECK();

@@ -4,20 +4,11 @@
 // (f2out.0 -> f2out.1 + residual -> next in2f; resp. their transposes in the backward), which also
 // clears the accumulation buffer of the next edge kernel.
 #include "spk_common.h"
-
-int spk_cfconv_fwd_internal(const spk_graph_t* g, const spk_radial_t* rb, const float* h,
-                            const float* r_ij, const float* w1, const float* b1, const float* w2,
-                            const float* b2, int nf, float* y, hipStream_t stream, bool pre_zeroed,
-                            float* gsave);
-int64_t spk_cfconv_gsave_floats(const spk_graph_t* g, const spk_radial_t* rb, int nf);
-int spk_cfconv_bwd_internal(const spk_graph_t* g, const spk_radial_t* rb, const float* h,
-                            const float* gy, const float* r_ij, const float* w1, const float* b1,
-                            const float* w2, const float* b2, int nf, float* gh, float* gr,
-                            hipStream_t stream, bool pre_zeroed, const float* gload, bool gr_assign, bool want_gh);
+#include "spk_cfconv.h"
+#include "spk_schnet_mol.h"
 
 // EXPERIMENT (spk_tabfilter.hip): a model whose first interaction has a registered filter table runs the general driver with the
 // table-driven cfconv kernels (the molecule-resident launches evaluate the filter network themselves)
-bool spk_filter_table_lookup(const float* key, const float** table, int* n_knots, float* d_max);
 static bool schnet_tabulated(const spk_schnet_t* m) {
   const float* tab; int nk; float dmax;
   return m && m->layers && m->n_interactions > 0 && spk_filter_table_lookup(m->layers[0].fn_w2, &tab, &nk, &dmax);
@@ -35,9 +26,6 @@ extern "C" int64_t spk_schnet_saved_floats(const spk_schnet_t* m, int64_t n_atom
   if (!m) return 0;
   return (int64_t)m->n_interactions * n_atoms * (m->n_filters + m->n_atom_basis);
 }
-int64_t spk_active_pairs_floats(int64_t n_half);
-int spk_active_pairs_internal(const spk_graph_t* g, const float* r_ij, float cutoff, float* ws, hipStream_t stream,
-                              const int32_t** half_out, const int32_t** count_out);
 // the per-call compacted pair list lives behind the saved filters (only when the pair kernels run)
 static bool schnet_filter_on(const spk_schnet_t* m, const spk_graph_t* g, const spk_radial_t* rb) {
   // (the experimental group-local kernels address `half` through per-group offsets: no compaction there)
@@ -54,7 +42,6 @@ static int64_t schnet_saved_floats_before_records(const spk_schnet_t* m, const s
 // condition under which the forward compacts its pair tiles.  *off: first float of the region, rounded up to a multiple of four
 // (16-byte records); *floats: what spk_schnet_saved_floats_graph() grows by = that padding + 8 n_half + n_groups
 // (records 4 n_half | pair vectors 3 n_half | record index per list position n_half | records per group n_groups).
-bool spk_schnet_mol_bwd_eligible(const spk_schnet_t* m, const spk_graph_t* g, const spk_radial_t* rb);
 bool spk_schnet_mol_records_region(const spk_schnet_t* m, const spk_graph_t* g, const spk_radial_t* rb, int64_t* off, int64_t* floats) {
   *off = 0; *floats = 0;
   if (!m || !g || !rb || (m->reserved & 3) != 3 || !m->layers || m->n_interactions <= 0) return false;
@@ -82,33 +69,6 @@ extern "C" int64_t spk_schnet_scratch_floats(const spk_schnet_t* m, int64_t n_at
   return n_atoms * (3 * (int64_t)m->n_filters + (int64_t)m->n_atom_basis + 2 * mx);
 }
 
-#define SPK_TRY(expr) do { int _rc = (expr); if (_rc) return _rc; } while (0)
-
-#include "spk_pack.h"
-// molecule-resident path (spk_schnet_mol.hip): block-diagonal lists with <= 32 atoms per group
-bool spk_schnet_mol_eligible(const spk_schnet_t* m, const spk_graph_t* g, const spk_radial_t* rb);
-int spk_schnet_mol_forward(const spk_schnet_t* m, const spk_graph_t* g, const spk_radial_t* rb, const SpkPackTable& ptab,
-                           const float* x0, const float* r_ij, float* x_out, float* saved, int64_t gsz, hipStream_t stream);
-bool spk_schnet_mol_bwd_eligible(const spk_schnet_t* m, const spk_graph_t* g, const spk_radial_t* rb);
-int spk_schnet_mol_bwd_records_mode();      // spk_schnet_mol_set_bwd_records()
-int spk_schnet_mol_backward(const spk_schnet_t* m, const spk_graph_t* g, const spk_radial_t* rb, const SpkPackTable& ptab,
-                            const float* gx_out, const float* r_ij, const float* saved, int64_t gsz, float* gr, float* gx0,
-                            hipStream_t stream);
-struct MolHeadDev {      // (layout shared with spk_schnet_mol.hip)
-  const float *w1, *w1t, *b1, *w2, *b2;
-  int H, act;
-  const int64_t* idx_m;
-  float* E;
-  float* pre_h;
-  const float* gE;
-  int direct_store, negate;
-};
-int spk_schnet_mol_forward_ex(const spk_schnet_t* m, const spk_graph_t* g, const spk_radial_t* rb, const SpkPackTable& ptab,
-                              const float* x0, const float* r_ij, const float* R, const float* offsets, const MolHeadDev* head, float* x_out,
-                              float* saved, int64_t gsz, hipStream_t stream, const float* emb = nullptr, const int64_t* Z = nullptr, int n_types = 0);
-int spk_schnet_mol_backward_ex(const spk_schnet_t* m, const spk_graph_t* g, const spk_radial_t* rb, const SpkPackTable& ptab,
-                               const float* gx_out, const float* r_ij, const float* R, const float* offsets, const MolHeadDev* head,
-                               const float* saved, int64_t gsz, float* gr, float* gR, float* gx0, hipStream_t stream);
 // order of the packed images in spk_schnet_t::wpack: per interaction in2f, f2out.0, f2out.1 (forward, transposed each)
 static bool schnet_pack_shapes_ok(const spk_schnet_t* m) { return m->n_atom_basis % 128 == 0 && m->n_filters % 128 == 0 && m->n_atom_basis <= 384 && m->n_filters <= 384; }
 static SpkPackTable schnet_pack_table(const spk_schnet_t* m) {
@@ -126,7 +86,6 @@ static SpkPackTable schnet_pack_table(const spk_schnet_t* m) {
   T.base = m->wpack;
   return T;
 }
-int spk_schnet_mol_pack_w2(const float* w2, float* image, hipStream_t stream);
 extern "C" int64_t spk_schnet_packed_floats(const spk_schnet_t* m) {
   if (!m || !m->layers || m->n_interactions <= 0 || !schnet_pack_shapes_ok(m)) return 0;
   return schnet_pack_table(m).total;
@@ -140,24 +99,6 @@ extern "C" int spk_schnet_pack_weights_f32(const spk_schnet_t* m, float* wpack, 
     rc = spk_schnet_mol_pack_w2(q.raw, wpack + q.off, (hipStream_t)stream);
   }
   return rc;
-}
-
-// forward layer from either the [out,in] weight or its transposed copy (coalesced reads)
-static spk_chain_layer_t mk_fwd(const float* w, const float* wT, const float* b, const float* res, float* out,
-                                float* pre_out, int k, int n_out, int act);
-
-static spk_chain_layer_t mk_layer(const float* w, const float* b, const float* res, float* out, float* pre_out,
-                                  const float* post_pre, int k, int n_out, int act, int trans, int post_act) {
-  spk_chain_layer_t L;
-  L.w = w; L.b = b; L.res = res; L.out = out; L.pre_out = pre_out; L.post_pre = post_pre;
-  L.k = k; L.n_out = n_out; L.act = act; L.trans = trans; L.post_act = post_act;
-  return L;
-}
-
-static spk_chain_layer_t mk_fwd(const float* w, const float* wT, const float* b, const float* res, float* out,
-                                float* pre_out, int k, int n_out, int act) {
-  return wT ? mk_layer(wT, b, res, out, pre_out, nullptr, k, n_out, act, 1, 0)
-            : mk_layer(w, b, res, out, pre_out, nullptr, k, n_out, act, 0, 0);
 }
 
 extern "C" int spk_schnet_forward_f32(const spk_schnet_t* m, const spk_graph_t* g,
@@ -199,9 +140,8 @@ extern "C" int spk_schnet_forward_f32(const spk_schnet_t* m, const spk_graph_t* 
     spk_chain_t c = {};
     c.n_layers = 1; c.m = N; c.in = x0; c.zero_ptr = ybuf[0]; c.zero_count = N * (int64_t)NF;
     c.tmp[0] = tmp0; c.tmp[1] = tmp1;
-    c.layers[0] = mk_fwd(m->layers[0].in2f_w, m->layers[0].in2f_wT, nullptr, nullptr, hbuf(0), nullptr, F, NF, SPK_ACT_NONE);
-    spk_apply_pack(c, ptab);
-    SPK_TRY(spk_dense_chain_f32(&c, stream));
+    c.layers[0] = spk_chain_fwd_layer(m->layers[0].in2f_w, m->layers[0].in2f_wT, nullptr, nullptr, hbuf(0), nullptr, F, NF, SPK_ACT_NONE);
+    SPK_TRY(spk_chain_run(c, ptab, stream));
   }
   for (int l = 0; l < L; ++l) {
     const spk_schnet_layer_t& P = m->layers[l];
@@ -213,16 +153,15 @@ extern "C" int spk_schnet_forward_f32(const spk_schnet_t* m, const spk_graph_t* 
                                     gsz > 0 ? gbase + l * gsz : nullptr));
     spk_chain_t c = {};
     c.m = N; c.in = y; c.tmp[0] = tmp0; c.tmp[1] = tmp1;
-    c.layers[0] = mk_fwd(P.f2out_w1, P.f2out_w1T, P.f2out_b1, nullptr, nullptr, pre3, NF, F, SPK_ACT_SSP);
-    c.layers[1] = mk_fwd(P.f2out_w2, P.f2out_w2T, P.f2out_b2, xin, x_out, nullptr, F, F, SPK_ACT_NONE);
+    c.layers[0] = spk_chain_fwd_layer(P.f2out_w1, P.f2out_w1T, P.f2out_b1, nullptr, nullptr, pre3, NF, F, SPK_ACT_SSP);
+    c.layers[1] = spk_chain_fwd_layer(P.f2out_w2, P.f2out_w2T, P.f2out_b2, xin, x_out, nullptr, F, F, SPK_ACT_NONE);
     c.n_layers = 2;
     if (l + 1 < L) {
-      c.layers[2] = mk_fwd(m->layers[l + 1].in2f_w, m->layers[l + 1].in2f_wT, nullptr, nullptr, hbuf(l + 1), nullptr, F, NF, SPK_ACT_NONE);
+      c.layers[2] = spk_chain_fwd_layer(m->layers[l + 1].in2f_w, m->layers[l + 1].in2f_wT, nullptr, nullptr, hbuf(l + 1), nullptr, F, NF, SPK_ACT_NONE);
       c.n_layers = 3;
       c.zero_ptr = ybuf[(l + 1) & 1]; c.zero_count = N * (int64_t)NF;
     }
-    spk_apply_pack(c, ptab);
-    SPK_TRY(spk_dense_chain_f32(&c, stream));
+    SPK_TRY(spk_chain_run(c, ptab, stream));
   }
   return SPK_OK;
 }
@@ -250,7 +189,7 @@ extern "C" int spk_schnet_backward_f32(const spk_schnet_t* m, const spk_graph_t*
                          (!schnet_filter_on(m, g, rb) || (ptab.base && spk_schnet_mol_eligible(m, g, rb)));
   if (E > 0) {
     SPK_CHECK_ARG(gr != nullptr, "%s: null gr", who);
-    if (!gr_assign) { int _zr = spk_zero_async(gr, (size_t)E * 3 * sizeof(float), stream); if (_zr) return _zr; }
+    if (!gr_assign) SPK_TRY(spk_zero_async(gr, (size_t)E * 3 * sizeof(float), stream));
   }
   if (N == 0) return SPK_OK;
   SPK_CHECK_ARG(gx_out && (L == 0 || (saved && scratch)), "%s: null buffer", who);
@@ -283,10 +222,9 @@ extern "C" int spk_schnet_backward_f32(const spk_schnet_t* m, const spk_graph_t*
     spk_chain_t c = {};
     c.n_layers = 2; c.m = N; c.in = gx_out; c.zero_ptr = ghbuf[(L - 1) & 1]; c.zero_count = N * (int64_t)NF;
     c.tmp[0] = tmp0; c.tmp[1] = tmp1;
-    c.layers[0] = mk_layer(P.f2out_w2, nullptr, nullptr, nullptr, nullptr, pre3(L - 1), F, F, SPK_ACT_NONE, 1, SPK_ACT_SSP);
-    c.layers[1] = mk_layer(P.f2out_w1, nullptr, nullptr, gy, nullptr, nullptr, F, NF, SPK_ACT_NONE, 1, 0);
-    spk_apply_pack(c, ptab);
-    SPK_TRY(spk_dense_chain_f32(&c, stream));
+    c.layers[0] = spk_chain_layer(P.f2out_w2, nullptr, nullptr, nullptr, nullptr, pre3(L - 1), F, F, SPK_ACT_NONE, 1, SPK_ACT_SSP);
+    c.layers[1] = spk_chain_layer(P.f2out_w1, nullptr, nullptr, gy, nullptr, nullptr, F, NF, SPK_ACT_NONE, 1, 0);
+    SPK_TRY(spk_chain_run(c, ptab, stream));
   }
   const float* gx = gx_out;
   for (int l = L - 1; l >= 0; --l) {
@@ -300,18 +238,17 @@ extern "C" int spk_schnet_backward_f32(const spk_schnet_t* m, const spk_graph_t*
     spk_chain_t c = {};
     c.m = N; c.in = gh; c.tmp[0] = tmp0; c.tmp[1] = tmp1;
     // in2f: h = x W_in^T ; residual path adds gx
-    c.layers[0] = mk_layer(P.in2f_w, nullptr, gx, out, nullptr, nullptr, NF, F, SPK_ACT_NONE, 1, 0);
+    c.layers[0] = spk_chain_layer(P.in2f_w, nullptr, gx, out, nullptr, nullptr, NF, F, SPK_ACT_NONE, 1, 0);
     c.n_layers = 1;
     if (l > 0) {
       const spk_schnet_layer_t& Q = m->layers[l - 1];
       c.layers[0].post_pre = nullptr;
-      c.layers[1] = mk_layer(Q.f2out_w2, nullptr, nullptr, nullptr, nullptr, pre3(l - 1), F, F, SPK_ACT_NONE, 1, SPK_ACT_SSP);
-      c.layers[2] = mk_layer(Q.f2out_w1, nullptr, nullptr, gy, nullptr, nullptr, F, NF, SPK_ACT_NONE, 1, 0);
+      c.layers[1] = spk_chain_layer(Q.f2out_w2, nullptr, nullptr, nullptr, nullptr, pre3(l - 1), F, F, SPK_ACT_NONE, 1, SPK_ACT_SSP);
+      c.layers[2] = spk_chain_layer(Q.f2out_w1, nullptr, nullptr, gy, nullptr, nullptr, F, NF, SPK_ACT_NONE, 1, 0);
       c.n_layers = 3;
       c.zero_ptr = ghbuf[(l - 1) & 1]; c.zero_count = N * (int64_t)NF;
     }
-    spk_apply_pack(c, ptab);
-    SPK_TRY(spk_dense_chain_f32(&c, stream));
+    SPK_TRY(spk_chain_run(c, ptab, stream));
     gx = out;
   }
   return SPK_OK;
@@ -341,7 +278,7 @@ extern "C" int spk_schnet_potential_forward_f32(const spk_schnet_t* m, const spk
   SPK_TRY(check_model(m, who));
   SPK_CHECK_ARG(potential_ok(m, head, g, rb), "%s: model / list not covered by the fused potential (see spk_schnet_potential_supported)", who);
   SPK_CHECK_ARG(n_mol >= 0 && (n_mol == 0 || E), "%s: null energy buffer", who);
-  if (n_mol > 0) { int zr = spk_zero_async(E, (size_t)n_mol * sizeof(float), stream); if (zr) return zr; }
+  if (n_mol > 0) SPK_TRY(spk_zero_async(E, (size_t)n_mol * sizeof(float), stream));
   if (g->n_atoms == 0) return SPK_OK;
   SPK_CHECK_ARG(x0 && R && idx_m && x_out && pre_h && saved, "%s: null buffer", who);
   MolHeadDev h;
@@ -380,7 +317,7 @@ static int schnet_potential_forces(const spk_schnet_t* m, const spk_head_t* head
   SPK_CHECK_ARG(potential_ok(m, head, g, rb), "%s: model / list not covered by the fused potential (see spk_schnet_potential_supported)", who);
   SPK_CHECK_ARG(n_mol >= 0 && (n_mol == 0 || E), "%s: null energy buffer", who);
   SPK_CHECK_ARG(x0 || (emb && Z && n_types > 0), "%s: neither features nor an embedding table", who);
-  if (n_mol > 0 && !all_inside) { int zr = spk_zero_async(E, (size_t)n_mol * sizeof(float), stream); if (zr) return zr; }
+  if (n_mol > 0 && !all_inside) SPK_TRY(spk_zero_async(E, (size_t)n_mol * sizeof(float), stream));
   if (g->n_atoms == 0) return SPK_OK;
   SPK_CHECK_ARG(R && idx_m && x_out && F && pre_h && saved, "%s: null buffer", who);
   MolHeadDev h;

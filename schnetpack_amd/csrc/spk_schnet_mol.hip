@@ -27,6 +27,7 @@
 // spk_set_split(0), on v_mfma_f32_32x32x2_f32 (the <KPB, false> instances).
 #include "spk_common.h"
 #include "spk_pack.h"
+#include "spk_schnet_mol.h"
 #include "spk_split.h"
 #include "spk_filter_split.h"
 
@@ -35,8 +36,6 @@
 #define ML_MAXPAIRS 384    // pairs per group (28 fully connected atoms; LDS budget of the backward)
 #define ML_MAXEDGES 768
 #define ML_MFMA(A, B, C) __builtin_amdgcn_mfma_f32_32x32x2f32((A), (B), (C), 0, 0, 0)
-
-bool spk_schnet_mol_bwd_eligible(const spk_schnet_t* m, const spk_graph_t* g, const spk_radial_t* rb);
 
 struct MolPair;
 // The records region of `saved` (spk_schnet_mol_records_region()): what ml_pair_records() of the forward computed, as the backward's
@@ -49,25 +48,6 @@ struct MolLayerDev {
   const float *w1, *b1, *w2, *b2;       // filter network, raw state_dict tensors
   const float* w2_img;                  // split-precision LDS image of w2 (wpack), or null: made from w2 while staging
   const float *o1_p, *o1_b, *o2_p, *o2_b;  // packed forward images of f2out.0 / f2out.1 and their biases
-};
-
-// The callers either side of the representation, folded into the two launches when the model is the standard potential
-// (PairwiseDistances -> SchNet -> Atomwise(sum) -> Forces; atomistic/distances.py:14-26, atomwise.py:69-88, response.py:59-76):
-// r_ij is formed from the positions, the default 2-layer energy head runs on the atom tile that is still in LDS, and the
-// backward starts from dE/dE_mol and ends at dE/dR.
-struct MolHeadDev {
-  const float* w1;        // outnet.0.weight [H, F]   (null: no head)
-  const float* w1t;       // its transpose   [F, H]   (backward)
-  const float* b1;        // [H]
-  const float* w2;        // outnet.1.weight [H]
-  const float* b2;        // [1]
-  int H, act;
-  const int64_t* idx_m;   // [N]
-  float* E;               // forward: [n_mol], accumulated with one atomic per (group, molecule): cleared by the caller ...
-  float* pre_h;           // [N, H] pre-activation of the head's hidden layer (saved for the backward)
-  const float* gE;        // backward: dL/dE [n_mol]; null = ones (forces of the summed energy)
-  int direct_store;       // ... unless every molecule lies inside one group: plain stores, nothing to clear
-  int negate;             // backward: write -dL/dR (= the forces when gE is ones)
 };
 
 struct MolFwdArgs {
@@ -1030,8 +1010,7 @@ extern "C" void spk_schnet_mol_set_bwd_task_split(int split) { g_mol_bwd_task_sp
 static int g_mol_bwd_records = 0;
 extern "C" void spk_schnet_mol_set_bwd_records(int mode) { g_mol_bwd_records = (mode == 1 || mode == 2) ? mode : 0; }
 int spk_schnet_mol_bwd_records_mode() { return g_mol_bwd_records; }
-// the region inside `saved` (spk_schnet.hip; one predicate for the sizing function and both launchers), as device pointers
-bool spk_schnet_mol_records_region(const spk_schnet_t* m, const spk_graph_t* g, const spk_radial_t* rb, int64_t* off, int64_t* floats);
+// the records region inside `saved` (spk_schnet_mol_records_region) as device pointers
 static MolHandoff mol_handoff(const spk_schnet_t* m, const spk_graph_t* g, const spk_radial_t* rb, int64_t gsz, const float* saved) {
   MolHandoff h = {nullptr, nullptr, nullptr, nullptr};
   int64_t off = 0, floats = 0;
@@ -1096,9 +1075,6 @@ static int launch_mol_fwd_sp(const MolFwdArgs& a, hipStream_t stream) {
 // pair kernels would compact) the space of the per-call pair list, which these launches leave alone, then -- model word bit 1, lists
 // the molecule-resident backward covers -- the records region: per record of a group its MolPair, per list position the pair vector
 // and the record index, per group the number of records (MolHandoff; spk_schnet_mol_records_region()).
-int spk_schnet_mol_forward_ex(const spk_schnet_t* m, const spk_graph_t* g, const spk_radial_t* rb, const SpkPackTable& ptab,
-                              const float* x0, const float* r_ij, const float* R, const float* offsets, const MolHeadDev* head, float* x_out,
-                              float* saved, int64_t gsz, hipStream_t stream, const float* emb = nullptr, const int64_t* Z = nullptr, int n_types = 0);
 int spk_schnet_mol_forward(const spk_schnet_t* m, const spk_graph_t* g, const spk_radial_t* rb, const SpkPackTable& ptab,
                            const float* x0, const float* r_ij, float* x_out, float* saved, int64_t gsz, hipStream_t stream) {
   return spk_schnet_mol_forward_ex(m, g, rb, ptab, x0, r_ij, nullptr, nullptr, nullptr, x_out, saved, gsz, stream);
@@ -1785,9 +1761,6 @@ bool spk_schnet_mol_bwd_eligible(const spk_schnet_t* m, const spk_graph_t* g, co
   return spk_schnet_mol_eligible(m, g, rb) && (rb->n_rbf + 7) / 8 <= 3 && !getenv("SPK_NO_MOL_BWD");
 }
 
-int spk_schnet_mol_backward_ex(const spk_schnet_t* m, const spk_graph_t* g, const spk_radial_t* rb, const SpkPackTable& ptab,
-                               const float* gx_out, const float* r_ij, const float* R, const float* offsets, const MolHeadDev* head,
-                               const float* saved, int64_t gsz, float* gr, float* gR, float* gx0, hipStream_t stream);
 int spk_schnet_mol_backward(const spk_schnet_t* m, const spk_graph_t* g, const spk_radial_t* rb, const SpkPackTable& ptab,
                             const float* gx_out, const float* r_ij, const float* saved, int64_t gsz, float* gr, float* gx0,
                             hipStream_t stream) {

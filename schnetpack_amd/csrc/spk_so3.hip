@@ -25,8 +25,6 @@
 #include "spk_common.h"
 #include "spk_so3_tables.h"
 
-#define SPK_TRY(expr) do { int _rc = (expr); if (_rc) return _rc; } while (0)
-
 namespace {
 
 constexpr int kSo3MaxF = 256;

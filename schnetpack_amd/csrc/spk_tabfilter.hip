@@ -13,6 +13,7 @@
 // centre atom (CSR row, sorted idx_i), a lane owns two channels: a table row is one coalesced 1-KB burst, the neighbour row
 // 512 bytes; no atomics; row sums in registers.  Bound: L2 / HBM gather bandwidth (2.5 KB per edge).
 #include "spk_common.h"
+#include "spk_cfconv.h"
 
 typedef float tf2 __attribute__((ext_vector_type(2)));
 

@@ -239,7 +239,7 @@ extern "C" int spk_edge_plan(const int64_t* idx_i, const int64_t* idx_j, const f
                 "spk_edge_plan: sizes out of range (N=%lld E=%lld)", (long long)N, (long long)E);
   SPK_CHECK_ARG(rowptr && scratch && host_flags, "spk_edge_plan: null pointer");
   SPK_CHECK_ARG(E == 0 || (idx_i && idx_j), "spk_edge_plan: null index arrays");
-  { int _zr = spk_zero_async(scratch, 4 * sizeof(int32_t), stream); if (_zr) return _zr; }
+  SPK_TRY(spk_zero_async(scratch, 4 * sizeof(int32_t), stream));
   int32_t f[4] = {0, 0, 0, 0};
   if (E > 0) {
     int grid = spk_grid_for(E, 256, 4096);
@@ -357,7 +357,7 @@ extern "C" int spk_scatter_add_f32(const float* x, const int64_t* idx, const int
   int64_t out_elems = outer * N * inner;
   if (out_elems == 0) return SPK_OK;
   SPK_CHECK_ARG(y != nullptr, "spk_scatter_add_f32: null output");
-  if (E == 0) { { int _zr = spk_zero_async(y, out_elems * sizeof(float), stream); if (_zr) return _zr; } return SPK_OK; }
+  if (E == 0) { SPK_TRY(spk_zero_async(y, out_elems * sizeof(float), stream)); return SPK_OK; }
   SPK_CHECK_ARG(x != nullptr && (idx != nullptr || rowptr != nullptr), "spk_scatter_add_f32: null input");
   const int maxb = spk_num_cus() * 16;
   if (rowptr) {
@@ -377,7 +377,7 @@ extern "C" int spk_scatter_add_f32(const float* x, const int64_t* idx, const int
     }
     SPK_LAUNCH_CHECK();
   } else {
-    { int _zr = spk_zero_async(y, out_elems * sizeof(float), stream); if (_zr) return _zr; }
+    SPK_TRY(spk_zero_async(y, out_elems * sizeof(float), stream));
     int grid = spk_grid_for(outer * E * inner, 256, maxb);
     hipLaunchKernelGGL(k_scatter_atomic, dim3(grid), dim3(256), 0, stream, x, idx, outer, E, inner, N, y);
     SPK_LAUNCH_CHECK();
@@ -613,7 +613,7 @@ extern "C" int spk_pairwise_bwd_f32(const float* gr, const int64_t* idx_i, const
   hipStream_t stream = (hipStream_t)stream_;
   if (N == 0) return SPK_OK;
   SPK_CHECK_ARG(gR != nullptr && N > 0 && E >= 0, "spk_pairwise_bwd_f32: bad input");
-  { int _zr = spk_zero_async(gR, (size_t)N * 3 * sizeof(float), stream); if (_zr) return _zr; }
+  SPK_TRY(spk_zero_async(gR, (size_t)N * 3 * sizeof(float), stream));
   if (E == 0) return SPK_OK;
   SPK_CHECK_ARG(gr && idx_i && idx_j, "spk_pairwise_bwd_f32: null pointer");
   hipLaunchKernelGGL(k_pairwise_bwd, dim3(spk_grid_for(E, 256, spk_num_cus() * 16)), dim3(256), 0, stream, gr, idx_i, idx_j, E, N, gR);

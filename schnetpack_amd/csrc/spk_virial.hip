@@ -12,8 +12,6 @@
 //                       butterfly -> W [n_mol, 9].  A molecule of 32 k atoms (a periodic box) is 500 partials, not one serial loop.
 #include "spk_common.h"
 
-#define SPK_TRY(expr) do { int _rc = (expr); if (_rc) return _rc; } while (0)
-
 namespace {
 
 constexpr int kVirChunk = 64;

@@ -18,8 +18,6 @@
 #include <math.h>
 #include "spk_common.h"
 
-#define SPK_TRY(expr) do { int _rc = (expr); if (_rc) return _rc; } while (0)
-
 namespace {
 
 constexpr int kZblTable = 128;   // atomic numbers [0, 128): beyond it the outputs of the atom are NaN
