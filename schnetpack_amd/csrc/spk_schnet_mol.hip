@@ -561,7 +561,15 @@ __global__ __launch_bounds__(512) void k_schnet_mol_fwd(MolFwdArgs a) {
                                    nullptr, a.ho.rec ? &a.ho : nullptr, grp);
     const int ntile = (np + 31) / 32;
     if constexpr (SP) {      // (each thread its own record; the barrier at the top of the first interaction publishes them)
-      if (tid < np) sP[tid] = ml_fwd_pair(sP[tid]);
+      // The last tile is PADDED here, once per group: entries [np, 32 ntile) are the last pair's record with f_c = 0, so the tile
+      // blocks below read sP at constant offsets and need neither a row count nor a select.  A padding entry and record np - 1 lie
+      // in the same aligned block of 32 -- the same wave, whose LDS reads complete in order before its writes.
+      static_assert(ML_MAXPAIRS % 32 == 0, "the padded last tile must fit sP");
+      if (tid < 32 * ntile) {
+        MolPair q = ml_fwd_pair(sP[tid < np ? tid : np - 1]);
+        if (tid >= np) q.fc = 0.f;
+        sP[tid] = q;
+      }
     }
     // (W2 of the first interaction -- first read by GEMM 2 of the first tile -- is staged by team 0 behind its first hidden tile,
     // while team 1 is still busy with in2f)
@@ -605,7 +613,8 @@ __global__ __launch_bounds__(512) void k_schnet_mol_fwd(MolFwdArgs a) {
           }
         } else if (active) {
           // ---- this wave's quarter of the hidden layer: z[pairs][32t : 32t+32] = ssp(W1 phi + b1)
-          const float d = sP[pfirst + (el < nvalid ? el : (nvalid - 1))].d;      // lanes 32..63 mirror lanes 0..31
+          // lanes 32..63 mirror lanes 0..31; a padding lane takes the last pair's distance (split form: from the padded records)
+          const float d = SP ? sP[pfirst + el].d : sP[pfirst + (el < nvalid ? el : (nvalid - 1))].d;
           f32x16 zc;
 #pragma unroll
           for (int r = 0; r < 16; ++r) zc[r] = sb1[32 * t + ml_row(r, hi)];
@@ -723,10 +732,10 @@ __global__ __launch_bounds__(512) void k_schnet_mol_fwd(MolFwdArgs a) {
           if constexpr (SP) {
             // incidence product on the f16 matrix instruction: A (0 / 1, exact) carries the weight 2^-11 of the low parts itself, so
             // the accumulator that lives across the tiles stays ONE
-            // Branch-free: a padding row (pr >= nvalid) takes the record of the tile's last pair.  The hidden layer mirrored that pair's
-            // distance into the padded lanes, so the row of g is that pair's row bit for bit and the store below writes the same value
-            // to the same address again (tests/test_gpu_mol_fwd_operands.py); its weight is zero.
-            const MolPair* sQ = sP + pfirst;             // forward-side records: ml_fwd_pair()
+            // Branch-free: a padding row carries the record of the tile's last pair with f_c = 0 (padded once per group, above).  The
+            // hidden layer took that pair's distance for the padded lanes, so the row of g is that pair's row bit for bit and the store
+            // below writes the same value to the same address again (tests/test_gpu_mol_fwd_operands.py); its weight is zero.
+            const MolPair* sQ = sP + pfirst + 4 * hi;    // forward-side records: ml_fwd_pair(); row ml_row(r, hi) = ml_row(r, 0) + 4 hi
             const char* hcol = (const char*)(sH + c0);
             const int own = el * (ML_LD * 4);
 #pragma unroll
@@ -736,12 +745,10 @@ __global__ __launch_bounds__(512) void k_schnet_mol_fwd(MolFwdArgs a) {
 #pragma unroll
               for (int e = 0; e < 8; ++e) {
                 const int r = 8 * s2 + e;
-                const int pr = ml_row(r, hi);
-                const bool ok = pr < nvalid;
-                const MolPair rec = sQ[ok ? pr : nvalid - 1];
+                const MolPair rec = sQ[ml_row(r, 0)];
                 const int oi = rec.ij & 0xFFFF, oj = rec.ij >> 16;
                 ml_st<float>(gt, (unsigned)(__float_as_int(rec.dfc) + el * 4), g[r]);
-                const float W = g[r] * (ok ? rec.fc : 0.f);
+                const float W = g[r] * rec.fc;
                 tI[e] = W * *(const float*)(hcol + oj); tJ[e] = W * *(const float*)(hcol + oi);
                 ai[e] = oi == own ? (_Float16)1.0f : (_Float16)0.0f;
                 aj[e] = oj == own ? (_Float16)1.0f : (_Float16)0.0f;
