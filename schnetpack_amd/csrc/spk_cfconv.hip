@@ -5,7 +5,7 @@
 //   y_i = sum_{e -> i} h_{j(e)} * W_e
 //
 // MFMA kernel: one wavefront owns a tile of 32 consecutive edges (lanes 0..31 and 32..63 both map
-// to edge l & 31).  The filter MLP runs as two chained T-GEMMs (see spk_dense.hip) with the
+// to edge l & 31).  The filter MLP runs as two chained T-GEMMs (see spk_mfma_tile.h) with the
 // packed filter weights staged once per workgroup in LDS; the [32 edge x nf] filter tile lives
 // only in registers.  Modulation gathers h[j] as 16-byte pieces, the per-centre-atom reduction goes
 // through a small per-wave LDS transposition buffer, and each (segment, feature) is flushed with
@@ -20,6 +20,7 @@
 // segmented reduction (gather gy of the neighbours); otherwise float atomics on gh[j].
 #include "spk_common.h"
 #include "spk_cfconv.h"
+#include "spk_mfma_tile.h"
 #include "spk_split.h"
 #include "spk_filter_split.h"
 
@@ -134,8 +135,7 @@ __global__ void k_cfconv_simple(CfArgs a, int NF, int sym) {
 // ------------------------------------------------------------------------------------------
 // MFMA kernels
 // ------------------------------------------------------------------------------------------
-// Packed LDS image of a weight matrix W[NOUT][K] (row-major, K padded with zeros to 8*KB):
-//   P[((t * KB + ug) * 64 + lane) * 4 + v] = W[32 t + (lane & 31)][8 ug + 4 (lane >> 5) + v]
+// Packed LDS image of a weight matrix W[NOUT][K] (row-major, K padded with zeros to 8*KB; the layout of spk_mfma_tile.h),
 // so one ds_read_b128 per lane delivers the A operands of 4 consecutive k-steps, conflict-free.
 // All global loads of a thread are issued before the first LDS store (latency paid once).
 template <int NTHREADS, int SLOTS>
@@ -170,8 +170,6 @@ __device__ __forceinline__ void stage_packed(float* dst, const float* __restrict
     if (s < SLOTS) *(f32x4*)(dst + (int64_t)s * 4) = v[p];
   }
 }
-
-#define SPK_MFMA(A, B, C) __builtin_amdgcn_mfma_f32_32x32x2f32((A), (B), (C), 0, 0, 0)
 
 // Row stride (floats) of the per-wave transposition buffer: two 32-channel tiles + 4 pad floats
 // => conflict-free ds_write_b128 (8-lane groups hit 8 distinct 4-bank groups) and ds_read_b32.
@@ -256,7 +254,7 @@ __global__ __launch_bounds__(NWAVES * 64) void k_cfconv_mfma(CfArgs a) {
 #pragma unroll
       for (int c = 0; c < NT; ++c) {
 #pragma unroll
-        for (int r = 0; r < 16; ++r) z[c][r] = sb1[32 * c + (r & 3) + 8 * (r >> 2) + 4 * hi];
+        for (int r = 0; r < 16; ++r) z[c][r] = sb1[32 * c + spk_acc_row(r, hi)];
         if (BWD) {
 #pragma unroll
           for (int r = 0; r < 16; ++r) zp[BWD ? c : 0][r] = 0.f;
@@ -309,7 +307,7 @@ __global__ __launch_bounds__(NWAVES * 64) void k_cfconv_mfma(CfArgs a) {
       }
       f32x16 g, gp;
 #pragma unroll
-      for (int r = 0; r < 16; ++r) { g[r] = sb2[32 * t + (r & 3) + 8 * (r >> 2) + 4 * hi]; gp[r] = 0.f; }
+      for (int r = 0; r < 16; ++r) { g[r] = sb2[32 * t + spk_acc_row(r, hi)]; gp[r] = 0.f; }
       {
         const float* wbase = sW2 + ((int64_t)t * KB2 * 64 + lane) * 4;
         f32x4 wq = *(const f32x4*)wbase;
@@ -418,8 +416,7 @@ __global__ __launch_bounds__(NWAVES * 64) void k_cfconv_mfma(CfArgs a) {
 // ------------------------------------------------------------------------------------------
 struct __attribute__((aligned(16))) EdgeRec { int i; int j; float fc; float dfc; };
 
-// register r of the half hi holds pair (r & 3) + 8 (r >> 2) + 4 hi of the tile
-__device__ __forceinline__ int pair_of(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }
+// (register r of the half hi holds pair spk_acc_row(r, hi) of the tile: spk_mfma_tile.h)
 
 template <int NF, int KPB, int NWAVES, bool BWD, bool GS, bool MOL>
 __global__ __launch_bounds__(NWAVES * 64) void k_cfconv_pair(CfArgs a) {
@@ -507,7 +504,7 @@ __global__ __launch_bounds__(NWAVES * 64) void k_cfconv_pair(CfArgs a) {
         for (int c = 0; c < NT; ++c) {
           f32x16 zc, zq;
 #pragma unroll
-          for (int r = 0; r < 16; ++r) { zc[r] = sb1[32 * c + pair_of(r, hi)]; zq[r] = 0.f; }
+          for (int r = 0; r < 16; ++r) { zc[r] = sb1[32 * c + spk_acc_row(r, hi)]; zq[r] = 0.f; }
 #pragma unroll
           for (int u = 0; u < KPB; ++u) {
             const int nxt = c * KPB + u + 1;
@@ -540,10 +537,10 @@ __global__ __launch_bounds__(NWAVES * 64) void k_cfconv_pair(CfArgs a) {
       // run structure of this lane's 16 pairs: bit r set <=> the centre atom changes after register r
       unsigned runmask = 0x8000u;
       {
-        int prev = myE[pair_of(0, hi)].i;
+        int prev = myE[spk_acc_row(0, hi)].i;
 #pragma unroll
         for (int r = 1; r < 16; ++r) {
-          const int cur = myE[pair_of(r, hi)].i;
+          const int cur = myE[spk_acc_row(r, hi)].i;
           if (cur != prev) runmask |= 1u << (r - 1);
           prev = cur;
         }
@@ -565,7 +562,7 @@ __global__ __launch_bounds__(NWAVES * 64) void k_cfconv_pair(CfArgs a) {
         if (!LATE) {
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
-            const EdgeRec er = myE[pair_of(r, hi)];
+            const EdgeRec er = myE[spk_acc_row(r, hi)];
             // 32-bit element offsets (n_atoms * nf < 2^31, checked by the launcher): one VGPR per address
             const unsigned oi = (unsigned)(er.i + ga0) * NF + c0, oj = (unsigned)(er.j + ga0) * NF + c0;
             hj[LATE ? 0 : r] = a.h[oj];
@@ -606,7 +603,7 @@ __global__ __launch_bounds__(NWAVES * 64) void k_cfconv_pair(CfArgs a) {
         if (!BWD && a.gsave) {
           float* gts = a.gsave + gtile * 32 * NF;   // this tile's filters, saved for the backward
 #pragma unroll
-          for (int r = 0; r < 16; ++r) gts[(unsigned)pair_of(r, hi) * NF + c0] = g[r];
+          for (int r = 0; r < 16; ++r) gts[(unsigned)spk_acc_row(r, hi) * NF + c0] = g[r];
         }
         // lane = channel c0: running sum over this lane's pairs for the centre atoms, one add per pair
         // for the neighbours
@@ -619,17 +616,17 @@ __global__ __launch_bounds__(NWAVES * 64) void k_cfconv_pair(CfArgs a) {
             const float* gtp = a.gload + gtile * 32 * NF;
 #pragma unroll
             for (int rr = 0; rr < RG; ++rr) {
-              const EdgeRec er = myE[pair_of(r0 + rr, hi)];
+              const EdgeRec er = myE[spk_acc_row(r0 + rr, hi)];
               const unsigned oi = (unsigned)(er.i + ga0) * NF + c0, oj = (unsigned)(er.j + ga0) * NF + c0;
               hj[rr] = a.h[oj]; hc[rr] = a.h[oi];
               gyi[BWD ? rr : 0] = a.gy[oi]; gyj[BWD ? rr : 0] = a.gy[oj];
-              gl[LATE ? rr : 0] = gtp[(unsigned)pair_of(r0 + rr, hi) * NF + c0];
+              gl[LATE ? rr : 0] = gtp[(unsigned)spk_acc_row(r0 + rr, hi) * NF + c0];
             }
           }
 #pragma unroll
           for (int rr = 0; rr < RG; ++rr) {
             const int r = r0 + rr;
-            const EdgeRec er = myE[pair_of(r, hi)];
+            const EdgeRec er = myE[spk_acc_row(r, hi)];
             const float gv = LATE ? gl[LATE ? rr : 0] : g[r];
             const float W = gv * er.fc;
             float toI, toJ;
@@ -638,7 +635,7 @@ __global__ __launch_bounds__(NWAVES * 64) void k_cfconv_pair(CfArgs a) {
               toJ = W * hc[rr];
             } else {
               const float D = gp[r] * er.fc + gv * er.dfc;
-              float* slot = myD + pair_of(r, hi) * 33 + el;
+              float* slot = myD + spk_acc_row(r, hi) * 33 + el;
               const float p1 = gyi[BWD ? rr : 0] * hj[rr] * D, p2 = gyj[BWD ? rr : 0] * hc[rr] * D;
               if (t == 0) { slot[0] = p1; slot[32 * 33] = p2; }
               else { slot[0] += p1; slot[32 * 33] += p2; }
@@ -758,7 +755,7 @@ __global__ __launch_bounds__(NWAVES * 64) void k_cfconv_pair_t(CfArgs a) {
 #pragma unroll
       for (int c = 0; c < NT; ++c) {
 #pragma unroll
-        for (int r = 0; r < 16; ++r) z[c][r] = sb1[32 * c + (r & 3) + 8 * (r >> 2) + 4 * hi];
+        for (int r = 0; r < 16; ++r) z[c][r] = sb1[32 * c + spk_acc_row(r, hi)];
         if (BWD) {
 #pragma unroll
           for (int r = 0; r < 16; ++r) zp[BWD ? c : 0][r] = 0.f;
@@ -812,7 +809,7 @@ __global__ __launch_bounds__(NWAVES * 64) void k_cfconv_pair_t(CfArgs a) {
       }
       f32x16 g, gp;
 #pragma unroll
-      for (int r = 0; r < 16; ++r) { g[r] = sb2[32 * t + (r & 3) + 8 * (r >> 2) + 4 * hi]; gp[r] = 0.f; }
+      for (int r = 0; r < 16; ++r) { g[r] = sb2[32 * t + spk_acc_row(r, hi)]; gp[r] = 0.f; }
       {
         const float* wbase = sW2 + ((int64_t)t * KB2 * 64 + lane) * 4;
         f32x4 wq = *(const f32x4*)wbase;
@@ -987,7 +984,7 @@ __global__ __launch_bounds__(NWAVES * 64) void k_cfconv_pair_sp(CfArgs a) {
       for (int c = 0; c < NT; ++c) {
         f32x16 zc, zx;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) { zc[r] = sb1[32 * c + pair_of(r, hi)]; zx[r] = 0.f; }
+        for (int r = 0; r < 16; ++r) { zc[r] = sb1[32 * c + spk_acc_row(r, hi)]; zx[r] = 0.f; }
 #pragma unroll
         for (int s = 0; s < (KPB > 2 ? 2 : 1); ++s) {
           h16x8 wh, wl;
@@ -1008,10 +1005,10 @@ __global__ __launch_bounds__(NWAVES * 64) void k_cfconv_pair_sp(CfArgs a) {
     spk_wave_lds_sync();   // myE visible to the whole wave
     unsigned runmask = 0x8000u;       // bit r set <=> the centre atom changes after register r
     {
-      int prev = myE[pair_of(0, hi)].i;
+      int prev = myE[spk_acc_row(0, hi)].i;
 #pragma unroll
       for (int r = 1; r < 16; ++r) {
-        const int cur = myE[pair_of(r, hi)].i;
+        const int cur = myE[spk_acc_row(r, hi)].i;
         if (cur != prev) runmask |= 1u << (r - 1);
         prev = cur;
       }
@@ -1023,7 +1020,7 @@ __global__ __launch_bounds__(NWAVES * 64) void k_cfconv_pair_sp(CfArgs a) {
       float hj[16], hc[16];
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const EdgeRec er = myE[pair_of(r, hi)];
+        const EdgeRec er = myE[spk_acc_row(r, hi)];
         const unsigned oi = (unsigned)er.i * NF + c0, oj = (unsigned)er.j * NF + c0;      // (n_atoms * nf < 2^31, checked by the launcher)
         hj[r] = a.h[oj];
         hc[r] = a.h[oi];
@@ -1048,12 +1045,12 @@ __global__ __launch_bounds__(NWAVES * 64) void k_cfconv_pair_sp(CfArgs a) {
       if (a.gsave) {
         float* gts = a.gsave + gtile * 32 * NF;   // this tile's filters, saved for the backward
 #pragma unroll
-        for (int r = 0; r < 16; ++r) gts[(unsigned)pair_of(r, hi) * NF + c0] = g[r];
+        for (int r = 0; r < 16; ++r) gts[(unsigned)spk_acc_row(r, hi) * NF + c0] = g[r];
       }
       float acc = 0.f;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const EdgeRec er = myE[pair_of(r, hi)];
+        const EdgeRec er = myE[spk_acc_row(r, hi)];
         const float W = g[r] * er.fc;
         acc += W * hj[r];
         unsafeAtomicAdd(a.y + ((unsigned)er.j * NF + c0), W * hc[r]);
@@ -1131,7 +1128,7 @@ __global__ __launch_bounds__(NWAVES * 64) void k_cfconv_pair_t_sp(CfArgs a) {
       for (int c = 0; c < NT; ++c) {
         f32x16 zc, zcx, zq, zqx;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) { zc[r] = sb1[32 * c + pair_of(r, hi)]; zcx[r] = 0.f; zq[r] = 0.f; zqx[r] = 0.f; }
+        for (int r = 0; r < 16; ++r) { zc[r] = sb1[32 * c + spk_acc_row(r, hi)]; zcx[r] = 0.f; zq[r] = 0.f; zqx[r] = 0.f; }
 #pragma unroll
         for (int s = 0; s < (KPB > 2 ? 2 : 1); ++s) {
           h16x8 wh, wl;
@@ -1375,7 +1372,7 @@ __global__ __launch_bounds__(NWAVES * 64) void k_cfconv_rowtile_fwd(CfArgs a) {
         for (int c = 0; c < NT; ++c) {
           f32x16 zc, zx;
 #pragma unroll
-          for (int r = 0; r < 16; ++r) { zc[r] = sb1[32 * c + pair_of(r, hi)]; zx[r] = 0.f; }
+          for (int r = 0; r < 16; ++r) { zc[r] = sb1[32 * c + spk_acc_row(r, hi)]; zx[r] = 0.f; }
 #pragma unroll
           for (int s = 0; s < (KPB > 2 ? 2 : 1); ++s) {
             h16x8 wh, wl;
@@ -1400,7 +1397,7 @@ __global__ __launch_bounds__(NWAVES * 64) void k_cfconv_rowtile_fwd(CfArgs a) {
         const int c0 = 32 * t + el;   // this lane's channel
         float hj[16];
 #pragma unroll
-        for (int r = 0; r < 16; ++r) hj[r] = *(const float*)((const char*)a.h + ((unsigned)myE[pair_of(r, hi)].j * NF + c0) * 4u);
+        for (int r = 0; r < 16; ++r) hj[r] = *(const float*)((const char*)a.h + ((unsigned)myE[spk_acc_row(r, hi)].j * NF + c0) * 4u);
         __builtin_amdgcn_sched_barrier(0);        // the 16 gathers of the block are requested before its GEMM
         f32x16 g, gx;
         const float bias2 = sb2[c0];
@@ -1422,7 +1419,7 @@ __global__ __launch_bounds__(NWAVES * 64) void k_cfconv_rowtile_fwd(CfArgs a) {
         float acc = 0.f;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const RtRec er = myE[pair_of(r, hi)];
+          const RtRec er = myE[spk_acc_row(r, hi)];
           if (a.gsave && er.pos >= 0) a.gsave[(size_t)er.pos * NF + c0] = g[r];     // raw filter of the canonical edge, for the pair backward
           acc = fmaf(g[r] * er.fc, hj[r], acc);
         }

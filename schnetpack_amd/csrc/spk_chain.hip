@@ -6,13 +6,14 @@
 // activations of the tile travel from layer to layer through LDS (two ping-pong buffers,
 // [32][K+4] floats, conflict-free for the 16-byte accesses used), every wave computes the 32x32
 // output tiles t = wave, wave+4, ... of a layer with the fp32 MFMA in the T-GEMM convention of
-// spk_dense.hip (A = weights straight from L2, prefetched in chunks; B = activations from LDS).
+// spk_mfma_tile.h (A = weights straight from L2, prefetched in chunks; B = activations from LDS).
 // Epilogue per layer: bias, activation, optional pre-activation store, optional residual add,
 // optional global store, optional "post" multiply by act'(pre) for the next layer's input
 // (backward chains).  The kernel can also zero a buffer for the following edge kernel, which
 // replaces a separate memset launch.
 #include "spk_common.h"
 #include "spk_dense.h"
+#include "spk_mfma_tile.h"
 #include "spk_split.h"
 
 #define CH_MAXL 3
@@ -72,10 +73,10 @@ __device__ __forceinline__ f32x16 chain_mfma(const f32x4 (&av)[CCH], int c, cons
   for (int u = 0; u < CCH; ++u) bv[u] = *(const f32x4*)(brow + 8 * (c * CCH + u) + 4 * hi);
 #pragma unroll
   for (int u = 0; u < CCH; ++u) {
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u].x, bv[u].x, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u].y, bv[u].y, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u].z, bv[u].z, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u].w, bv[u].w, acc, 0, 0, 0);
+    acc = SPK_MFMA(av[u].x, bv[u].x, acc);
+    acc = SPK_MFMA(av[u].y, bv[u].y, acc);
+    acc = SPK_MFMA(av[u].z, bv[u].z, acc);
+    acc = SPK_MFMA(av[u].w, bv[u].w, acc);
   }
   return acc;
 }
@@ -176,7 +177,7 @@ __global__ __launch_bounds__(256, 2) void k_dense_chain(ChainArgs a, int ld0, in
         }
         f32x16 acc;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = L.b ? L.b[32 * t + (r & 3) + 8 * (r >> 2) + 4 * hi] : 0.f;
+        for (int r = 0; r < 16; ++r) acc[r] = L.b ? L.b[spk_acc_row(r, hi, 32 * t)] : 0.f;
         for (int c = 0; c < nch; c += 2) {
           chain_load_a(a1, L.w, L.KC / 8, t, c + 1, lane);
           acc = chain_mfma(a0, c, brow, hi, acc);
@@ -484,7 +485,7 @@ __global__ __launch_bounds__(256, 2) void k_dense_chain_sp(ChainArgs a, int ld0,
         }
         f32x16 acc, cross;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) { acc[r] = L.b ? L.b[32 * t + (r & 3) + 8 * (r >> 2) + 4 * hi] : 0.f; cross[r] = 0.f; }
+        for (int r = 0; r < 16; ++r) { acc[r] = L.b ? L.b[spk_acc_row(r, hi, 32 * t)] : 0.f; cross[r] = 0.f; }
         for (int c = 0; c < nch; c += 2) {
           chain_load_a(a1, L.w, L.KC / 8, t, c + 1, lane);
           chain_mfma_sp(a0, c, bh, bl, hi, acc, cross);

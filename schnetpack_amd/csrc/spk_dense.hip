@@ -1,19 +1,10 @@
 // Dense layers (nn/base.py:52-55) on the fp32 matrix cores of gfx950.
 //
-// "T-GEMM" convention used by every MFMA kernel of this library (v_mfma_f32_32x32x2_f32,
-// exact fp32, 64 lanes):
-//   the wave computes a 32x32 tile of OUT^T:  rows = output features i, columns = samples m.
-//   A operand (weights):  lane l holds A[i = i0 + (l & 31)][kk],
-//   B operand (samples):  lane l holds B[kk][m = m0 + (l & 31)] = in[m][kk],
-//   where for k-step s = 4u + v the lane half hi = l >> 5 supplies kk = 8u + 4hi + v
-//   (any bijection between (step, half) and kk is legal as long as A and B agree; this one lets
-//   each lane fetch 4 consecutive kk with one 16-byte load),
-//   C/D accumulator:      acc[r] <-> row i = i0 + (r & 3) + 8 (r >> 2) + 4 hi, column m0 + (l & 31).
-//   Because the accumulator rows use the same (r>>2, r&3, hi) -> index map as the k-steps, an
-//   accumulator tile can be fed straight back as the B operand of the next layer (chained GEMMs
-//   without leaving registers) -- used by the fused cfconv kernels.
+// The "T-GEMM" convention that every MFMA kernel of this library follows (operand and accumulator layout, packed weight
+// image) is described in spk_mfma_tile.h.
 #include "spk_common.h"
 #include "spk_dense.h"
+#include "spk_mfma_tile.h"
 #include "spk_gemm_tn.h"
 
 // One chunk = 8 k-blocks (64 contraction indices): 8 A + 8 B 16-byte operands per lane.  All loads
@@ -62,10 +53,10 @@ __device__ __forceinline__ f32x16 dense_mfma_chunk(const f32x4 (&av)[CH], const 
 #pragma unroll
   for (int u = 0; u < CH; ++u) {
     if (c * CH + u < nug) {
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u].x, bv[u].x, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u].y, bv[u].y, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u].z, bv[u].z, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u].w, bv[u].w, acc, 0, 0, 0);
+      acc = SPK_MFMA(av[u].x, bv[u].x, acc);
+      acc = SPK_MFMA(av[u].y, bv[u].y, acc);
+      acc = SPK_MFMA(av[u].z, bv[u].z, acc);
+      acc = SPK_MFMA(av[u].w, bv[u].w, acc);
     }
   }
   return acc;
@@ -103,7 +94,7 @@ __device__ __forceinline__ void dense_tiles(
     f32x16 acc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int col = 32 * t + (r & 3) + 8 * (r >> 2) + 4 * hi;
+      const int col = 32 * t + spk_acc_row(r, hi);
       acc[r] = (b && col < NW) ? b[col] : 0.f;
     }
     for (int c = 0; c < nch; c += 2) {
@@ -181,7 +172,7 @@ __global__ __launch_bounds__(256) void k_dense_mfma_splitk(const float* __restri
   }
   if (wv > 0) {
 #pragma unroll
-    for (int r = 0; r < 16; ++r) red[wv - 1][(r & 3) + 8 * (r >> 2) + 4 * hi][el] = acc[r];
+    for (int r = 0; r < 16; ++r) red[wv - 1][spk_acc_row(r, hi)][el] = acc[r];
   }
   __syncthreads();
   if (wv == 0 && valid) {
@@ -192,7 +183,7 @@ __global__ __launch_bounds__(256) void k_dense_mfma_splitk(const float* __restri
       f32x4 o;
 #pragma unroll
       for (int v = 0; v < 4; ++v) {
-        const int r = 4 * q + v, rr = (r & 3) + 8 * (r >> 2) + 4 * hi;
+        const int r = 4 * q + v, rr = spk_acc_row(r, hi);
         o[v] = ((acc[r] + red[0][rr][el]) + red[1][rr][el]) + red[2][rr][el] + (b ? b[col + v] : 0.f);
       }
       *(f32x4*)(out + m * NW + col) = o;
@@ -242,7 +233,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_dense_mfma_sk(const float* __res
     if (c + WAVES < nch) acc = dense_mfma_chunk(a1, b1, c + WAVES, nug, acc);
   }
 #pragma unroll
-  for (int r = 0; r < 16; ++r) red[wv][(r & 3) + 8 * (r >> 2) + 4 * hi][el] = acc[r];
+  for (int r = 0; r < 16; ++r) red[wv][spk_acc_row(r, hi)][el] = acc[r];
   __syncthreads();
   if (!fin) return;
   f32x4 o;
@@ -458,7 +449,7 @@ __global__ __launch_bounds__(256) void k_atomwise_fwd(
         dense_load_chunk<false, SPK_ACT_NONE>(a0, b0, 0, nug, inrow, nullptr, w1, KC, H, t, el, hi);
         f32x16 acc;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = b1 ? b1[32 * t + (r & 3) + 8 * (r >> 2) + 4 * hi] : 0.f;
+        for (int r = 0; r < 16; ++r) acc[r] = b1 ? b1[32 * t + spk_acc_row(r, hi)] : 0.f;
         for (int c = 0; c < nch; c += 2) {
           if (c + 1 < nch) dense_load_chunk<false, SPK_ACT_NONE>(a1, b1v, c + 1, nug, inrow, nullptr, w1, KC, H, t, el, hi);
           acc = dense_mfma_chunk(a0, b0, c, nug, acc);
@@ -664,10 +655,10 @@ __global__ __launch_bounds__(256) void k_atomwise_bwd(
 #pragma unroll
       for (int u = 0; u < DCH; ++u) {
         if (ug0 + u < nug) {
-          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u].x, bv[u].x, acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u].y, bv[u].y, acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u].z, bv[u].z, acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u].w, bv[u].w, acc, 0, 0, 0);
+          acc = SPK_MFMA(av[u].x, bv[u].x, acc);
+          acc = SPK_MFMA(av[u].y, bv[u].y, acc);
+          acc = SPK_MFMA(av[u].z, bv[u].z, acc);
+          acc = SPK_MFMA(av[u].w, bv[u].w, acc);
         }
       }
     }
@@ -866,7 +857,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_dense_dual_sk(DenseDualArgs a) {
     if (wv >= 4) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int rr = (r & 3) + 8 * (r >> 2) + 4 * hi;
+        const int rr = spk_acc_row(r, hi);
         red[0][wv - 4][rr][el] = acc_t[r];
         if (dual) red[1][wv - 4][rr][el] = acc_v[r];
       }
@@ -875,7 +866,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_dense_dual_sk(DenseDualArgs a) {
     if (wv < 4) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int rr = (r & 3) + 8 * (r >> 2) + 4 * hi;
+        const int rr = spk_acc_row(r, hi);
         acc_t[r] += red[0][wv][rr][el];
         if (dual) acc_v[r] += red[1][wv][rr][el];
       }
@@ -885,7 +876,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_dense_dual_sk(DenseDualArgs a) {
   if (wv < 4) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int rr = (r & 3) + 8 * (r >> 2) + 4 * hi;
+      const int rr = spk_acc_row(r, hi);
       red[0][wv][rr][el] = acc_t[r];
       if (dual) red[1][wv][rr][el] = acc_v[r];
     }
@@ -953,7 +944,7 @@ __global__ __launch_bounds__(256) void k_dense_dual_tiles(DenseDualArgs a, int64
     f32x16 acc_v, acc_t;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int col = 32 * t + (r & 3) + 8 * (r >> 2) + 4 * hi;
+      const int col = 32 * t + spk_acc_row(r, hi);
       acc_v[r] = (a.b && col < NW) ? a.b[col] : 0.f;
       acc_t[r] = 0.f;
     }

@@ -24,6 +24,7 @@
 // whose range holds a foreign atom receive NaN.  A molecule without atoms writes nothing.  psi = 0 gives exact zeros.
 #include <math.h>
 #include "spk_common.h"
+#include "spk_mfma_tile.h"
 
 namespace {
 
@@ -218,17 +219,16 @@ __device__ __forceinline__ void ee_mm(const float* A, int lda, const float* __re
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const f32x4 x = *(const f32x4*)(arow + kb + 8 * u);
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(x.x, b[u].x, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(x.y, b[u].y, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(x.z, b[u].z, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(x.w, b[u].w, acc, 0, 0, 0);
+      acc = SPK_MFMA(x.x, b[u].x, acc);
+      acc = SPK_MFMA(x.y, b[u].y, acc);
+      acc = SPK_MFMA(x.z, b[u].z, acc);
+      acc = SPK_MFMA(x.w, b[u].w, acc);
     }
 #pragma unroll
     for (int u = 0; u < 4; ++u) b[u] = bn[u];
   }
 }
-// row (atom of the tile) of accumulator register r in lane half hi; the column is lane & 31
-__device__ __forceinline__ int ee_row(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }
+// (spk_acc_row(r, hi): row = atom of the tile of accumulator register r in lane half hi; the column is lane & 31)
 
 // NT: column tiles per wave (F <= 128 NT: 1, else 2)
 template <int NT, int ACT>
@@ -297,7 +297,7 @@ __global__ __launch_bounds__(64 * kEeWaves) void k_ee_stack(EeArgs a) {
       const int ct = wave + kEeWaves * t;
       if (ct < nct) {
 #pragma unroll
-        for (int r = 0; r < 16; ++r) B[ee_row(r, hi) * ld + 32 * ct + col] = ee_act<ACT>(acc[t][r]);
+        for (int r = 0; r < 16; ++r) B[spk_acc_row(r, hi) * ld + 32 * ct + col] = ee_act<ACT>(acc[t][r]);
       }
     }
     __syncthreads();
@@ -316,7 +316,7 @@ __global__ __launch_bounds__(64 * kEeWaves) void k_ee_stack(EeArgs a) {
       if (ct < nct) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int o = ee_row(r, hi) * ld + 32 * ct + col;
+          const int o = spk_acc_row(r, hi) * ld + 32 * ct + col;
           const float y = Y[o] + acc[t][r];
           Y[o] = y;
           B[o] = ee_act<ACT>(y);
@@ -336,7 +336,7 @@ __global__ __launch_bounds__(64 * kEeWaves) void k_ee_stack(EeArgs a) {
       ee_mm(B, ld, a.wl + (size_t)(32 * ct) * F, F, acc[t]);
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int row = ee_row(r, hi);
+        const int row = spk_acc_row(r, hi);
         const int64_t g = atom0 + row;
         if (g < a.N) {
           const int kind = rowk[row];

@@ -32,6 +32,7 @@
 // kernel per chain (descriptor in SGPRs, one barrier per stage, operands resident in LDS, a store wave): profiles/r05_row_chains.md.
 #pragma once
 #include "spk_fm_kernels.h"
+#include "spk_mfma_tile.h"
 
 #define FM_CHAIN_ATOMS 4          // atoms per workgroup
 #define FM_CHAIN_MAX_STAGES 12
@@ -148,9 +149,8 @@ struct FmChainItem {
 // owner, and every global value a later stage of the SAME chain reads (X of a Dense stage, residuals, saved pre-activations, the operands of the
 // element-wise kernels -- whose item (i, f) touches columns f, F + f, 2 F + f of rows of atom i, with F a multiple of 128) is read by its
 // owner: a store followed by a load of the same address in ONE thread needs no fence.  What waves exchange goes through LDS (the X tile, the
-// partial products), behind LDS-only barriers -- `__syncthreads()` would drain the vector-memory counter, i.e. wait ~2 us per stage for the
+// partial products), behind LDS-only barriers (SPK_LDS_BARRIER, spk_mfma_tile.h) -- `__syncthreads()` would drain the vector-memory counter, i.e. wait ~2 us per stage for the
 // stores of the saved tensors to be acknowledged (first version of this kernel: 3.7 us per stage; spk_painn_mol.hip found the same).
-#define FM_CHAIN_LDS_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 #define FM_CHAIN_STAMP(dbgp, slot)                                                                    \
   do {                                                                                                \
     if ((dbgp) && blockIdx.x == 0 && threadIdx.x == 0) (dbgp)[slot] = __builtin_readcyclecounter();    \
@@ -211,7 +211,7 @@ __device__ __forceinline__ int fm_chain_gemm_stage(const FmGemmStage& g, int64_t
     }
   }
   FM_CHAIN_STAMP(dbg, 0);
-  FM_CHAIN_LDS_BARRIER();
+  SPK_LDS_BARRIER();
   FM_CHAIN_STAMP(dbg, 1);
   // ---- partial products
   for (int it = wv; it < n_items; it += nw) {
@@ -232,7 +232,7 @@ __device__ __forceinline__ int fm_chain_gemm_stage(const FmGemmStage& g, int64_t
 #undef FM_CHAIN_RUN
   }
   FM_CHAIN_STAMP(dbg, 2);
-  FM_CHAIN_LDS_BARRIER();
+  SPK_LDS_BARRIER();
   FM_CHAIN_STAMP(dbg, 3);
   // ---- epilogue, by owner: sum of the partial tiles -> global (and back into the first partial tile when the next stage reads Y from LDS).
   // ROLLED loops and an out-of-line activation on purpose: the unrolled two-phase form of this epilogue (all operand loads, the next stage's
@@ -289,7 +289,7 @@ __device__ __forceinline__ int fm_chain_gemm_stage(const FmGemmStage& g, int64_t
     }
   }
   FM_CHAIN_STAMP(dbg, 5);
-  FM_CHAIN_LDS_BARRIER();       // Y in LDS (when kept) is complete; the partial tiles may be overwritten by the stage after the next
+  SPK_LDS_BARRIER();       // Y in LDS (when kept) is complete; the partial tiles may be overwritten by the stage after the next
   FM_CHAIN_STAMP(dbg, 6);
   return ldp;
 }

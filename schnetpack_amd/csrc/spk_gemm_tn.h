@@ -1,6 +1,7 @@
 // G = U^T X with column sums of U: the workgroup body shared by k_gemm_tn (spk_train.hip) and k_gemm_pair (spk_dense.hip).
 #pragma once
 #include "spk_common.h"
+#include "spk_mfma_tile.h"
 
 #define TN_BATCH 16
 #define TN_WAVES 8
@@ -57,7 +58,7 @@ __device__ __forceinline__ void gemm_tn_block(const GemmTnArgs& a, int tile, int
   }
 #define SPK_TN_MMA(AV, BV, WITH_BIAS)                                                       \
   _Pragma("unroll") for (int q = 0; q < TN_BATCH; ++q) {                                    \
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(AV[q], BV[q], acc, 0, 0, 0);                 \
+    acc = SPK_MFMA(AV[q], BV[q], acc);                 \
     if (WITH_BIAS) usum += AV[q];                                                           \
   }
 #define SPK_TN_LOOP(RBEG, REND, WITH_BIAS)                                                  \
@@ -78,7 +79,7 @@ __device__ __forceinline__ void gemm_tn_block(const GemmTnArgs& a, int tile, int
 #undef SPK_TN_LOOP
   usum += __shfl_xor(usum, 32, 64);
 #pragma unroll
-  for (int r = 0; r < 16; ++r) red[wv][(r & 3) + 8 * (r >> 2) + 4 * hi][el] = acc[r];
+  for (int r = 0; r < 16; ++r) red[wv][spk_acc_row(r, hi)][el] = acc[r];
   if (hi == 0) redb[wv][el] = usum;
   __syncthreads();
   // thread t owns outputs (row t / 32 + 16 h, column t % 32), h = 0, 1

@@ -23,6 +23,7 @@
 #include "spk_common.h"
 #include "spk_pack.h"
 #include "spk_painn_mol.h"
+#include "spk_mfma_tile.h"
 #include "spk_split.h"
 
 #define PM_MAXL 6
@@ -30,7 +31,6 @@
 #define PM_TILE (32 * PM_LD)
 #define PM_MAXEDGES 768           // directed edges per group (= 2 x 384 pairs, the plan's bound)
 #define PM_NRBF 20                // register-resident filter weights: n_rbf <= 20
-#define PM_MFMA(A, B, C) __builtin_amdgcn_mfma_f32_32x32x2f32((A), (B), (C), 0, 0, 0)
 
 typedef float pm_f2 __attribute__((ext_vector_type(2)));
 
@@ -76,97 +76,13 @@ struct PmFwdArgs {
 // per directed edge of a group: local neighbour, unit vector, distance, cutoff value -- computed once per group
 struct __attribute__((aligned(8))) PmEdge { int jl; float ux, uy, uz, d, fc; };
 
-template <class T>
-__device__ __forceinline__ T pm_ld(const void* sbase, unsigned voff) { return *(const T*)((const char*)sbase + voff); }
-template <class T>
-__device__ __forceinline__ void pm_st(void* sbase, unsigned voff, T v) { *(T*)((char*)sbase + voff) = v; }
-// register r of the half hi of a 32x32 accumulator holds row (r & 3) + 8 (r >> 2) + 4 hi
-__device__ __forceinline__ int pm_row(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }
-
-// ---- T-GEMM pieces (convention of spk_dense.hip): A = packed weights straight from L2, B = activations [32][PM_LD] in LDS;
-// accumulator rows = output features 32 t + pm_row(r, hi), columns = atoms (lane & 31).
-// Packed image: P[((t * KB + ug) * 64 + lane) * 4 + v] = W[32 t + (lane & 31)][8 ug + 4 (lane >> 5) + v]; one k-block = 1024 bytes.
-__device__ __forceinline__ void pm_load8(f32x4 (&av)[8], const char* sb /* wave-uniform */, int lane) {
-#pragma unroll
-  for (int u = 0; u < 8; ++u) av[u] = pm_ld<f32x4>(sb, (unsigned)(lane * 16 + u * 1024));
-}
-// (B operands are requested four groups ahead: left alone the compiler issues each ds_read right in front of the four MFMAs
-//  that need it -- zero prefetch distance, the matrix pipe waits ~100 cycles per group of four)
-// SP (spk_split.h): `av` holds eight chunks of the SPLIT weight image (chunk 2 s = the high parts of k-step s, 2 s + 1 its 2^11-scaled low
-// parts; same bytes and offsets as the fp32 image, k_pack_weight_split), the activations are read as eight consecutive fp32 values
-// per k-step (brow is the fp32 form's address, lane row + 4 hi: 4 hi more make it row + 8 hi) and split in registers; three f16
-// instructions per 16 k instead of eight f32 ones, the cross terms in their own accumulator, folded in at the end of the block.
+// ---- T-GEMM pieces: Dense blocks of spk_mfma_tile.h on tiles [32][PM_LD] in LDS (global accesses through spk_ld / spk_st).
+// 8 k-blocks against the lane's row `brow` (spk_tile_brow<PM_LD>, k offset included) of an fp32 tile, on the fp32 or the split path;
+// the split block reads eight consecutive values per k-step: 4 hi more make the address row + 8 hi
 template <bool SP = false>
 __device__ __forceinline__ f32x16 pm_mma8(const f32x4 (&av)[8], const float* __restrict__ brow, f32x16 acc) {
-  if constexpr (SP) {
-    const float* b = brow + 4 * ((threadIdx.x >> 5) & 1);
-    f32x16 cx;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) cx[r] = 0.f;
-    f32x4 b0[4], b1[4];
-    b0[0] = *(const f32x4*)b; b1[0] = *(const f32x4*)(b + 4);
-    asm volatile("" ::: "memory");
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      if (s + 1 < 4) { b0[s + 1] = *(const f32x4*)(b + 16 * (s + 1)); b1[s + 1] = *(const f32x4*)(b + 16 * (s + 1) + 4); asm volatile("" ::: "memory"); }
-      h16x4 h0, l0, h1, l1;
-      sp_split4(b0[s], h0, l0);
-      sp_split4(b1[s], h1, l1);
-      SP_STEP(__builtin_bit_cast(h16x8, av[2 * s]), __builtin_bit_cast(h16x8, av[2 * s + 1]), sp_cat(h0, h1), sp_cat(l0, l1), acc, cx);
-    }
-    SP_FOLD(acc, cx);
-    return acc;
-  }
-  f32x4 bv[8];
-#pragma unroll
-  for (int u = 0; u < 4; ++u) bv[u] = *(const f32x4*)(brow + 8 * u);
-  asm volatile("" ::: "memory");
-#pragma unroll
-  for (int u = 0; u < 8; ++u) {
-    acc = PM_MFMA(av[u].x, bv[u].x, acc);
-    acc = PM_MFMA(av[u].y, bv[u].y, acc);
-    acc = PM_MFMA(av[u].z, bv[u].z, acc);
-    acc = PM_MFMA(av[u].w, bv[u].w, acc);
-    if (u + 4 < 8) {
-      bv[u + 4] = *(const f32x4*)(brow + 8 * (u + 4));
-      asm volatile("" ::: "memory");
-    }
-  }
-  return acc;
-}
-// 16 k-blocks (K = 128 of the image's row, starting at k-block kb0) against ONE LDS tile
-template <bool SP = false>
-__device__ __forceinline__ f32x16 pm_tile16(const float* __restrict__ wp, int KB, int t /* wave-uniform */, int kb0, const float* __restrict__ sB, int lane,
-                                            f32x16 acc) {
-  const char* sb = (const char*)wp + ((size_t)t * KB + kb0) * 1024;
-  const float* brow = sB + (lane & 31) * PM_LD + 4 * (lane >> 5);
-  f32x4 a0[8], a1[8];
-  pm_load8(a0, sb, lane);
-  pm_load8(a1, sb + 8 * 1024, lane);
-  acc = pm_mma8<SP>(a0, brow, acc);
-  acc = pm_mma8<SP>(a1, brow + 64, acc);
-  return acc;
-}
-// the same weights against the THREE component planes of mu (A operand shared: 96 MFMAs per 8 k-blocks)
-template <bool SP = false>
-__device__ __forceinline__ void pm_tile16x3(const float* __restrict__ wp, int t, const float* __restrict__ sB, int lane, f32x16& c0, f32x16& c1, f32x16& c2) {
-  const char* sb = (const char*)wp + (size_t)t * 16 * 1024;
-  const float* brow = sB + (lane & 31) * PM_LD + 4 * (lane >> 5);
-  f32x4 a0[8], a1[8];
-  pm_load8(a0, sb, lane);
-  pm_load8(a1, sb + 8 * 1024, lane);
-  c0 = pm_mma8<SP>(a0, brow, c0);
-  c1 = pm_mma8<SP>(a0, brow + PM_TILE, c1);
-  c2 = pm_mma8<SP>(a0, brow + 2 * PM_TILE, c2);
-  c0 = pm_mma8<SP>(a1, brow + 64, c0);
-  c1 = pm_mma8<SP>(a1, brow + PM_TILE + 64, c1);
-  c2 = pm_mma8<SP>(a1, brow + 2 * PM_TILE + 64, c2);
-}
-__device__ __forceinline__ f32x16 pm_bias_acc(const float* __restrict__ b, int t, int hi) {
-  f32x16 acc;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) acc[r] = b[32 * t + pm_row(r, hi)];
-  return acc;
+  if constexpr (SP) return spk_tile_mma_sp<4, 1>(av, brow + 4 * ((threadIdx.x >> 5) & 1), acc);
+  return spk_tile_mma(av, brow, acc);
 }
 __device__ __forceinline__ float pm_silu(float x) { return x * spk_sigmoid(x); }
 __device__ __forceinline__ float pm_silu_grad(float x);
@@ -182,26 +98,21 @@ __device__ __forceinline__ float pm_phi(int kind, float p0k, float p1k, float d)
   return d == 0.0f ? s : s / d;
 }
 
-// Workgroup barrier that waits for the LDS traffic of the wave only (like ck's block_sync_lds): __syncthreads() also drains
-// vmcnt, i.e. waits until the saved-for-backward STORES of the phase have been acknowledged by L2 (~5 k cycles each time) and
-// until the weight tiles prefetched for the next phase have arrived -- neither is needed at the barrier.
-#define PM_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
-
 // A feature tile of packed weights on its way from L2.  Only the FIRST eight k-blocks travel across a phase boundary (32
 // registers); the following chunks are requested when the tile is used, each one chunk (32 MFMAs = 2 k cycles) ahead of its use.
 // (Whole tiles held across a barrier -- 64 to 96 registers next to the accumulators -- were spilled by the register allocator
 // RIGHT BEHIND their loads: load, wait, store to scratch, one L2 round trip after the other.)
 struct PmW { f32x4 a0[8]; const char* sb; };
 __device__ __forceinline__ void pm_wload(PmW& W, const float* __restrict__ wp, int KB, int t /* wave-uniform */, int kb0, int lane) {
-  W.sb = (const char*)wp + ((size_t)t * KB + kb0) * 1024;
-  pm_load8(W.a0, W.sb, lane);
+  W.sb = spk_tile_base(wp, KB, t, kb0);
+  spk_tile_load(W.a0, W.sb, lane);
 }
 // 16 k-blocks against one LDS tile
 template <bool SP = false>
 __device__ __forceinline__ f32x16 pm_wmma(const PmW& W, const float* __restrict__ sB, int lane, f32x16 acc) {
-  const float* brow = sB + (lane & 31) * PM_LD + 4 * (lane >> 5);
+  const float* brow = spk_tile_brow<PM_LD>(sB, lane);
   f32x4 a1[8];
-  pm_load8(a1, W.sb + 8 * 1024, lane);
+  spk_tile_load(a1, W.sb + 8 * kSpkKBlockBytes, lane);
   acc = pm_mma8<SP>(W.a0, brow, acc);
   acc = pm_mma8<SP>(a1, brow + 64, acc);
   return acc;
@@ -209,9 +120,9 @@ __device__ __forceinline__ f32x16 pm_wmma(const PmW& W, const float* __restrict_
 // 16 k-blocks, the same weights against the three component planes of an LDS tensor
 template <bool SP = false>
 __device__ __forceinline__ void pm_wmma3(const PmW& W, const float* __restrict__ sB, int lane, f32x16& c0, f32x16& c1, f32x16& c2) {
-  const float* brow = sB + (lane & 31) * PM_LD + 4 * (lane >> 5);
+  const float* brow = spk_tile_brow<PM_LD>(sB, lane);
   f32x4 a1[8];
-  pm_load8(a1, W.sb + 8 * 1024, lane);
+  spk_tile_load(a1, W.sb + 8 * kSpkKBlockBytes, lane);
   c0 = pm_mma8<SP>(W.a0, brow, c0);
   c1 = pm_mma8<SP>(W.a0, brow + PM_TILE, c1);
   c2 = pm_mma8<SP>(W.a0, brow + 2 * PM_TILE, c2);
@@ -224,9 +135,9 @@ template <bool SP = false>
 __device__ __forceinline__ f32x16 pm_wmma_3chunks(const PmW& W, const float* __restrict__ b0, const float* __restrict__ b1, const float* __restrict__ b2, int lane,
                                                   f32x16 acc) {
   f32x4 a1[8], a2[8];
-  pm_load8(a1, W.sb + 8 * 1024, lane);
+  spk_tile_load(a1, W.sb + 8 * kSpkKBlockBytes, lane);
   acc = pm_mma8<SP>(W.a0, b0, acc);
-  pm_load8(a2, W.sb + 16 * 1024, lane);
+  spk_tile_load(a2, W.sb + 16 * kSpkKBlockBytes, lane);
   acc = pm_mma8<SP>(a1, b1, acc);
   acc = pm_mma8<SP>(a2, b2, acc);
   return acc;
@@ -234,13 +145,13 @@ __device__ __forceinline__ f32x16 pm_wmma_3chunks(const PmW& W, const float* __r
 // a whole tile in registers (the W_mix^T half tile that serves the three components of M4)
 struct PmWF { f32x4 a0[8], a1[8]; };
 __device__ __forceinline__ void pm_wfload(PmWF& W, const float* __restrict__ wp, int KB, int t, int kb0, int lane) {
-  const char* sb = (const char*)wp + ((size_t)t * KB + kb0) * 1024;
-  pm_load8(W.a0, sb, lane);
-  pm_load8(W.a1, sb + 8 * 1024, lane);
+  const char* sb = spk_tile_base(wp, KB, t, kb0);
+  spk_tile_load(W.a0, sb, lane);
+  spk_tile_load(W.a1, sb + 8 * kSpkKBlockBytes, lane);
 }
 template <bool SP = false>
 __device__ __forceinline__ f32x16 pm_wfmma(const PmWF& W, const float* __restrict__ sB, int lane, f32x16 acc) {
-  const float* brow = sB + (lane & 31) * PM_LD + 4 * (lane >> 5);
+  const float* brow = spk_tile_brow<PM_LD>(sB, lane);
   acc = pm_mma8<SP>(W.a0, brow, acc);
   acc = pm_mma8<SP>(W.a1, brow + 64, acc);
   return acc;
@@ -541,9 +452,9 @@ __device__ __forceinline__ void pm_message_tiled(const PmTW<K>& W, float* __rest
     for (int r = 0; r < 16; ++r) { F0[r] = 0.f; F1[r] = 0.f; F2[r] = 0.f; }
 #pragma unroll
     for (int kb = 0; kb < KB; ++kb) {
-      F0 = PM_MFMA(A[kb], W.b[0][kb], F0);
-      F1 = PM_MFMA(A[kb], W.b[1][kb], F1);
-      if (!MU0) F2 = PM_MFMA(A[kb], W.b[2][kb], F2);
+      F0 = SPK_MFMA(A[kb], W.b[0][kb], F0);
+      F1 = SPK_MFMA(A[kb], W.b[1][kb], F1);
+      if (!MU0) F2 = SPK_MFMA(A[kb], W.b[2][kb], F2);
     }
     // ---- products with the neighbour rows, summed over the 16 slots of the lane's half (= one centre atom), two slots per step.
     // Software-pipelined by hand: the LDS reads of step p + 1 are issued before the arithmetic of step p and PINNED there (left
@@ -583,10 +494,10 @@ __device__ __forceinline__ void pm_message_tiled(const PmTW<K>& W, float* __rest
 #pragma unroll
     for (int r = 0; r < 16; r += 4) {
       issue(r + 2, S1);
-      asm volatile("" ::: "memory");
+      SPK_PIN();
       compute(r, S0);
       if (r + 4 < 16) issue(r + 4, S0);
-      asm volatile("" ::: "memory");
+      SPK_PIN();
       compute(r + 2, S1);
     }
     float dq = q2.x + q2.y, d0 = m0.x + m0.y, d1 = m1.x + m1.y, d2 = m2.x + m2.y;
@@ -666,7 +577,7 @@ __global__ __launch_bounds__(512) void k_painn_mol_fwd(PmFwdArgs a) {
   for (int grp = blockIdx.x; grp < a.n_groups; grp += gridDim.x) {
     const int a0 = a.grp_atom0[grp], na = a.grp_atom0[grp + 1] - a0;
     const int e0 = a.rowptr[a0], ne = a.rowptr[a0 + na] - e0;
-    PM_BARRIER();      // the previous group is done with every LDS buffer
+    SPK_LDS_BARRIER();      // the previous group is done with every LDS buffer
     PM_STAMP(0);
 
     // ---- group set-up: q rows, mu = 0 (painn.py:246), local CSR, edge geometry (shared by all interactions)
@@ -678,7 +589,7 @@ __global__ __launch_bounds__(512) void k_painn_mol_fwd(PmFwdArgs a) {
           const int64_t z = a.Z[a0 + row];
           if (z >= 0 && z < a.n_types) v = *(const f32x4*)(a.emb + (size_t)z * F + 4 * c4);
           else { const float qn = __builtin_nanf(""); v = f32x4{qn, qn, qn, qn}; }       // no row to read: loud, never out of bounds
-        } else v = pm_ld<f32x4>(a.q0 + (size_t)a0 * F, (unsigned)(s * 16));
+        } else v = spk_ld<f32x4>(a.q0 + (size_t)a0 * F, (unsigned)(s * 16));
       }
       *(f32x4*)(sQ + row * PM_LD + 4 * c4) = v;
     }
@@ -717,13 +628,13 @@ __global__ __launch_bounds__(512) void k_painn_mol_fwd(PmFwdArgs a) {
       if (TILED) { const int n = pm_build_tiles<K>(sRow, na, lane, a.rb, (int*)sPhi); if (lane == 0) sRow[33] = n; }      // (the row form uses sPhi per edge; the two are exclusive)
     }
     // mu entering the first interaction is zero: the backward reads it from the saved block
-    for (int s = tid; s < na * 96; s += 512) pm_st<f32x4>(a.saved + 4 * nf + (size_t)a0 * 3 * F, (unsigned)(s * 16), f32x4{0.f, 0.f, 0.f, 0.f});
+    for (int s = tid; s < na * 96; s += 512) spk_st<f32x4>(a.saved + 4 * nf + (size_t)a0 * 3 * F, (unsigned)(s * 16), f32x4{0.f, 0.f, 0.f, 0.f});
 
     if (team == 0) {
       // ======================================================================== team 0
       PmW Wt;            // the weight tile this wave needs next
       f32x16 bz;         // ... and its bias
-      pm_wload(Wt, a.L[0].ctx1_p, 16, t, 0, lane); bz = pm_bias_acc(a.L[0].ctx1_b, t, hi);
+      pm_wload(Wt, a.L[0].ctx1_p, 16, t, 0, lane); bz = spk_bias_acc(a.L[0].ctx1_b, t, hi);
       for (int l = 0; l < a.n_layers; ++l) {
         // (lane-derived LDS / global offsets are re-derived inside every interaction: hoisted out of the loop by the compiler they
         //  fill the prologue with dozens of live registers -- and their spills)
@@ -735,7 +646,7 @@ __global__ __launch_bounds__(512) void k_painn_mol_fwd(PmFwdArgs a) {
         float* S = a.saved + (int64_t)l * per;
         const bool last = (l + 1 == a.n_layers);
         float* mu_next_g = last ? a.mu_out : (a.saved + (int64_t)(l + 1) * per + 4 * nf);
-        PM_BARRIER();
+        SPK_LDS_BARRIER();
         PM_STAMP(1 + 8 * l);
         const int nT = sRow[33];
         constexpr bool tiled = TILED;
@@ -743,16 +654,16 @@ __global__ __launch_bounds__(512) void k_painn_mol_fwd(PmFwdArgs a) {
         // ---- P1: pre_a = W_a1 q + b (saved), silu -> sH
         {
           f32x16 acc = pm_wmma<SP>(Wt, sQ, lane, bz);
-          pm_wload(Wt, P.ctx2_p, 16, t, 0, lane); bz = pm_bias_acc(P.ctx2_b, t, hi);
+          pm_wload(Wt, P.ctx2_p, 16, t, 0, lane); bz = spk_bias_acc(P.ctx2_b, t, hi);
           float* preA_g = S;
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
             const f32x4 pv = {acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]};
             *(f32x4*)(sH + el * PM_LD + 32 * t + 8 * q + 4 * hi) = f32x4{pm_silu(pv.x), pm_silu(pv.y), pm_silu(pv.z), pm_silu(pv.w)};
-            if (el < na) pm_st<f32x4>(preA_g + (size_t)a0 * F + 32 * t, (unsigned)((el * F + 8 * q + 4 * hi) * 4), pv);
+            if (el < na) spk_st<f32x4>(preA_g + (size_t)a0 * F + 32 * t, (unsigned)((el * F + 8 * q + 4 * hi) * 4), pv);
           }
         }
-        PM_BARRIER();
+        SPK_LDS_BARRIER();
         PM_STAMP(2 + 8 * l);
         // ---- P2: c = W_a2 silu(pre_a) + b, tiles t and 8 + t (saved, LDS planes)
         PmFilt<K> Wf;
@@ -760,12 +671,12 @@ __global__ __launch_bounds__(512) void k_painn_mol_fwd(PmFwdArgs a) {
         {
           float* c_g = S + nf;
           f32x16 acc = pm_wmma<SP>(Wt, sH, lane, bz);
-          pm_wload(Wt, P.ctx2_p, 16, 8 + t, 0, lane); bz = pm_bias_acc(P.ctx2_b, 8 + t, hi);
+          pm_wload(Wt, P.ctx2_p, 16, 8 + t, 0, lane); bz = spk_bias_acc(P.ctx2_b, 8 + t, hi);
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
             const f32x4 cv = {acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]};
             *(f32x4*)(sC + el * PM_LD + 32 * t + 8 * q + 4 * hi) = cv;
-            if (el < na) pm_st<f32x4>(c_g + (size_t)a0 * 3 * F + 32 * t, (unsigned)((el * 3 * F + 8 * q + 4 * hi) * 4), cv);
+            if (el < na) spk_st<f32x4>(c_g + (size_t)a0 * 3 * F + 32 * t, (unsigned)((el * 3 * F + 8 * q + 4 * hi) * 4), cv);
           }
           if (tiled) pm_tw_load<K>(TW, P.wf, P.bf, t, lane, l == 0);
           else pm_filt_load<K>(Wf, P.wf, P.bf, lane, l == 0);
@@ -774,10 +685,10 @@ __global__ __launch_bounds__(512) void k_painn_mol_fwd(PmFwdArgs a) {
           for (int q = 0; q < 4; ++q) {
             const f32x4 cv = {acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]};
             *(f32x4*)(sC + 2 * PM_TILE + el * PM_LD + 32 * t + 8 * q + 4 * hi) = cv;
-            if (el < na) pm_st<f32x4>(c_g + (size_t)a0 * 3 * F + 32 * (8 + t), (unsigned)((el * 3 * F + 8 * q + 4 * hi) * 4), cv);
+            if (el < na) spk_st<f32x4>(c_g + (size_t)a0 * 3 * F + 32 * (8 + t), (unsigned)((el * 3 * F + 8 * q + 4 * hi) * 4), cv);
           }
         }
-        PM_BARRIER();
+        SPK_LDS_BARRIER();
         PM_STAMP(3 + 8 * l);
         // ---- P3: message
         if (tiled) {
@@ -787,7 +698,7 @@ __global__ __launch_bounds__(512) void k_painn_mol_fwd(PmFwdArgs a) {
           else pm_message_tiled<K, false>(TW, sQ, sMu, sC, pm_edge_arrays(sE), sTile, nT, 0, t, cutoff, lane, dm, ovf);
           pm_wload(Wt, P.mix_p, 16, t, 0, lane);
           PM_STAMP(4 + 8 * l);
-          PM_BARRIER();       // every wave has read its neighbours' rows: mu can be replaced
+          SPK_LDS_BARRIER();       // every wave has read its neighbours' rows: mu can be replaced
           pm_message_tiled_write(sMu, sTile, nT, 0, t, lane, dm, ovf);
         } else {
           pm_f2 rm[4][3];
@@ -798,10 +709,10 @@ __global__ __launch_bounds__(512) void k_painn_mol_fwd(PmFwdArgs a) {
           else pm_message<K, false>(Wf, P.bf, sQ, sMu, sC, sE, sRow, dyn ? sAsg : myAsg, myPhi, a.rb.kind, p0k, p1k, cutoff, lane, rm, ats, ctr, na, dyn);
           pm_wload(Wt, P.mix_p, 16, t, 0, lane);
           PM_STAMP(4 + 8 * l);
-          PM_BARRIER();       // every wave has read its neighbours' rows: mu can be replaced
+          SPK_LDS_BARRIER();       // every wave has read its neighbours' rows: mu can be replaced
           pm_message_write(sMu, ats, lane, rm);
         }
-        PM_BARRIER();
+        SPK_LDS_BARRIER();
         PM_STAMP(5 + 8 * l);
         // ---- P4: V = mu W_mix^T[:F] for the three components (feature tile t); |V| -> LDS (read by team 1 in P5); V saved
         f32x16 W0, W1, W2, sVW;
@@ -822,12 +733,12 @@ __global__ __launch_bounds__(512) void k_painn_mol_fwd(PmFwdArgs a) {
             *(f32x4*)(sN + el * PM_LD + 32 * t + 8 * q + 4 * hi) = nv;
           }
         }
-        PM_BARRIER();
+        SPK_LDS_BARRIER();
         PM_STAMP(6 + 8 * l);
         // ---- P5: W = mu W_mix^T[F:] (beside team 1's pre_b on the same SIMD); sum_x V W; mix saved
         {
           pm_wmma3<SP>(Wt, sMu, lane, W0, W1, W2);
-          pm_wload(Wt, P.ic2_p, 16, 8 + t, 0, lane); bz = pm_bias_acc(P.ic2_b, 8 + t, hi);
+          pm_wload(Wt, P.ic2_p, 16, 8 + t, 0, lane); bz = spk_bias_acc(P.ic2_b, 8 + t, hi);
 #pragma unroll
           for (int r = 0; r < 16; ++r) sVW[r] = V0[r] * W0[r] + V1[r] * W1[r] + V2[r] * W2[r];
           if (el < na) {
@@ -835,31 +746,31 @@ __global__ __launch_bounds__(512) void k_painn_mol_fwd(PmFwdArgs a) {
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
               const unsigned o = (unsigned)((el * 6 * F + 8 * q + 4 * hi) * 4);
-              pm_st<f32x4>(mg, o, f32x4{V0[4 * q], V0[4 * q + 1], V0[4 * q + 2], V0[4 * q + 3]});
-              pm_st<f32x4>(mg, o + 2 * F * 4, f32x4{V1[4 * q], V1[4 * q + 1], V1[4 * q + 2], V1[4 * q + 3]});
-              pm_st<f32x4>(mg, o + 4 * F * 4, f32x4{V2[4 * q], V2[4 * q + 1], V2[4 * q + 2], V2[4 * q + 3]});
-              pm_st<f32x4>(mg, o + F * 4, f32x4{W0[4 * q], W0[4 * q + 1], W0[4 * q + 2], W0[4 * q + 3]});
-              pm_st<f32x4>(mg, o + 3 * F * 4, f32x4{W1[4 * q], W1[4 * q + 1], W1[4 * q + 2], W1[4 * q + 3]});
-              pm_st<f32x4>(mg, o + 5 * F * 4, f32x4{W2[4 * q], W2[4 * q + 1], W2[4 * q + 2], W2[4 * q + 3]});
+              spk_st<f32x4>(mg, o, f32x4{V0[4 * q], V0[4 * q + 1], V0[4 * q + 2], V0[4 * q + 3]});
+              spk_st<f32x4>(mg, o + 2 * F * 4, f32x4{V1[4 * q], V1[4 * q + 1], V1[4 * q + 2], V1[4 * q + 3]});
+              spk_st<f32x4>(mg, o + 4 * F * 4, f32x4{V2[4 * q], V2[4 * q + 1], V2[4 * q + 2], V2[4 * q + 3]});
+              spk_st<f32x4>(mg, o + F * 4, f32x4{W0[4 * q], W0[4 * q + 1], W0[4 * q + 2], W0[4 * q + 3]});
+              spk_st<f32x4>(mg, o + 3 * F * 4, f32x4{W1[4 * q], W1[4 * q + 1], W1[4 * q + 2], W1[4 * q + 3]});
+              spk_st<f32x4>(mg, o + 5 * F * 4, f32x4{W2[4 * q], W2[4 * q + 1], W2[4 * q + 2], W2[4 * q + 3]});
             }
           }
         }
-        PM_BARRIER();
+        SPK_LDS_BARRIER();
         PM_STAMP(7 + 8 * l);
         // ---- P6: a = W_b2 silu(pre_b) + b (saved);  q += a_q + a_qmu sum_x V W;  mu += a_mu W      (painn.py:110-116)
         {
           float* ag = S + 14 * nf + (size_t)a0 * 3 * F + 32 * t;
           f32x16 tq = pm_wmma<SP>(Wt, sH, lane, bz);                       // a_qmu
-          pm_wload(Wt, P.ic2_p, 16, t, 0, lane); bz = pm_bias_acc(P.ic2_b, t, hi);
+          pm_wload(Wt, P.ic2_p, 16, t, 0, lane); bz = spk_bias_acc(P.ic2_b, t, hi);
           if (el < na) {
 #pragma unroll
             for (int q = 0; q < 4; ++q)
-              pm_st<f32x4>(ag, (unsigned)((el * 3 * F + 2 * F + 8 * q + 4 * hi) * 4), f32x4{tq[4 * q], tq[4 * q + 1], tq[4 * q + 2], tq[4 * q + 3]});
+              spk_st<f32x4>(ag, (unsigned)((el * 3 * F + 2 * F + 8 * q + 4 * hi) * 4), f32x4{tq[4 * q], tq[4 * q + 1], tq[4 * q + 2], tq[4 * q + 3]});
           }
 #pragma unroll
           for (int r = 0; r < 16; ++r) tq[r] *= sVW[r];
           f32x16 aq = pm_wmma<SP>(Wt, sH, lane, bz);                       // a_q
-          pm_wload(Wt, P.ic2_p, 16, 4 + t, 0, lane); bz = pm_bias_acc(P.ic2_b, 4 + t, hi);
+          pm_wload(Wt, P.ic2_p, 16, 4 + t, 0, lane); bz = spk_bias_acc(P.ic2_b, 4 + t, hi);
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
             float* qp = sQ + el * PM_LD + 32 * t + 8 * q + 4 * hi;
@@ -869,12 +780,12 @@ __global__ __launch_bounds__(512) void k_painn_mol_fwd(PmFwdArgs a) {
             if (el >= na) qv = f32x4{0.f, 0.f, 0.f, 0.f};
             *(f32x4*)qp = qv;
             if (el < na) {
-              pm_st<f32x4>(ag, (unsigned)((el * 3 * F + 8 * q + 4 * hi) * 4), av);
-              if (last) pm_st<f32x4>(a.q_out + (size_t)a0 * F + 32 * t, (unsigned)((el * F + 8 * q + 4 * hi) * 4), qv);
+              spk_st<f32x4>(ag, (unsigned)((el * 3 * F + 8 * q + 4 * hi) * 4), av);
+              if (last) spk_st<f32x4>(a.q_out + (size_t)a0 * F + 32 * t, (unsigned)((el * F + 8 * q + 4 * hi) * 4), qv);
             }
           }
           f32x16 am = pm_wmma<SP>(Wt, sH, lane, bz);                       // a_mu
-          if (!last) { pm_wload(Wt, a.L[l + 1].ctx1_p, 16, t, 0, lane); bz = pm_bias_acc(a.L[l + 1].ctx1_b, t, hi); }
+          if (!last) { pm_wload(Wt, a.L[l + 1].ctx1_p, 16, t, 0, lane); bz = spk_bias_acc(a.L[l + 1].ctx1_b, t, hi); }
           float* mn = mu_next_g + (size_t)a0 * 3 * F + 32 * t;
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
@@ -888,10 +799,10 @@ __global__ __launch_bounds__(512) void k_painn_mol_fwd(PmFwdArgs a) {
             *(f32x4*)mp = m0; *(f32x4*)(mp + PM_TILE) = m1; *(f32x4*)(mp + 2 * PM_TILE) = m2;
             if (el < na) {
               const unsigned o = (unsigned)((el * 3 * F + 8 * q + 4 * hi) * 4);
-              pm_st<f32x4>(ag, (unsigned)((el * 3 * F + F + 8 * q + 4 * hi) * 4), av);
-              pm_st<f32x4>(mn, o, m0);
-              pm_st<f32x4>(mn, o + F * 4, m1);
-              pm_st<f32x4>(mn, o + 2 * F * 4, m2);
+              spk_st<f32x4>(ag, (unsigned)((el * 3 * F + F + 8 * q + 4 * hi) * 4), av);
+              spk_st<f32x4>(mn, o, m0);
+              spk_st<f32x4>(mn, o + F * 4, m1);
+              spk_st<f32x4>(mn, o + 2 * F * 4, m2);
             }
           }
         }
@@ -911,13 +822,13 @@ __global__ __launch_bounds__(512) void k_painn_mol_fwd(PmFwdArgs a) {
         float* S = a.saved + (int64_t)l * per;
         PmW Wt;
         f32x16 bz;
-        PM_BARRIER();
+        SPK_LDS_BARRIER();
         const int nT = sRow[33];
         constexpr bool tiled = TILED;
         const int* sTile = (const int*)sPhi;
         // ---- P1: (team 0: pre_a) -- request the tile of P2
-        pm_wload(Wt, P.ctx2_p, 16, 4 + t, 0, lane); bz = pm_bias_acc(P.ctx2_b, 4 + t, hi);
-        PM_BARRIER();
+        pm_wload(Wt, P.ctx2_p, 16, 4 + t, 0, lane); bz = spk_bias_acc(P.ctx2_b, 4 + t, hi);
+        SPK_LDS_BARRIER();
         // ---- P2: c tile 4 + t (the R part)
         PmFilt<K> Wf;
         PmTW<K> TW;
@@ -930,17 +841,17 @@ __global__ __launch_bounds__(512) void k_painn_mol_fwd(PmFwdArgs a) {
           for (int q = 0; q < 4; ++q) {
             const f32x4 cv = {acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]};
             *(f32x4*)(sC + PM_TILE + el * PM_LD + 32 * t + 8 * q + 4 * hi) = cv;
-            if (el < na) pm_st<f32x4>(c_g + (size_t)a0 * 3 * F + 32 * (4 + t), (unsigned)((el * 3 * F + 8 * q + 4 * hi) * 4), cv);
+            if (el < na) spk_st<f32x4>(c_g + (size_t)a0 * 3 * F + 32 * (4 + t), (unsigned)((el * 3 * F + 8 * q + 4 * hi) * 4), cv);
           }
         }
-        PM_BARRIER();
+        SPK_LDS_BARRIER();
         // ---- P3: message
         if (tiled) {
           pm_f8 dm[3];
           float* ovf = a.mu_out + (size_t)a0 * 3 * F;          // (written for good in P6 of the last interaction: free until then)
           if (l == 0) pm_message_tiled<K, true>(TW, sQ, sMu, sC, pm_edge_arrays(sE), sTile, nT, 1, t, cutoff, lane, dm, ovf);
           else pm_message_tiled<K, false>(TW, sQ, sMu, sC, pm_edge_arrays(sE), sTile, nT, 1, t, cutoff, lane, dm, ovf);
-          PM_BARRIER();
+          SPK_LDS_BARRIER();
           pm_message_tiled_write(sMu, sTile, nT, 1, t, lane, dm, ovf);
         } else {
           pm_f2 rm[4][3];
@@ -949,16 +860,16 @@ __global__ __launch_bounds__(512) void k_painn_mol_fwd(PmFwdArgs a) {
           if (tid == 0) sRow[34 + ((l + 1) & 1)] = 0;          // (the counter of the next interaction; everybody left it a barrier ago)
           if (l == 0) pm_message<K, true>(Wf, P.bf, sQ, sMu, sC, sE, sRow, dyn ? sAsg : myAsg, myPhi, a.rb.kind, p0k, p1k, cutoff, lane, rm, ats, ctr, na, dyn);
           else pm_message<K, false>(Wf, P.bf, sQ, sMu, sC, sE, sRow, dyn ? sAsg : myAsg, myPhi, a.rb.kind, p0k, p1k, cutoff, lane, rm, ats, ctr, na, dyn);
-          PM_BARRIER();
+          SPK_LDS_BARRIER();
           pm_message_write(sMu, ats, lane, rm);
         }
-        PM_BARRIER();
+        SPK_LDS_BARRIER();
         // ---- P4: (team 0: channel mix) -- request the K = 256 tile of P5
         PmW Wu;
         pm_wload(Wt, P.ic1_p, 32, t, 0, lane);
         pm_wload(Wu, P.ic1_p, 32, t, 16, lane);
-        bz = pm_bias_acc(P.ic1_b, t, hi);
-        PM_BARRIER();
+        bz = spk_bias_acc(P.ic1_b, t, hi);
+        SPK_LDS_BARRIER();
         // ---- P5: pre_b = W_b1 [q | |V|] + b (K = 256; saved), silu -> sH
         {
           float* preB_g = S + 13 * nf;
@@ -968,10 +879,10 @@ __global__ __launch_bounds__(512) void k_painn_mol_fwd(PmFwdArgs a) {
           for (int q = 0; q < 4; ++q) {
             const f32x4 pv = {acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]};
             *(f32x4*)(sH + el * PM_LD + 32 * t + 8 * q + 4 * hi) = f32x4{pm_silu(pv.x), pm_silu(pv.y), pm_silu(pv.z), pm_silu(pv.w)};
-            if (el < na) pm_st<f32x4>(preB_g + (size_t)a0 * F + 32 * t, (unsigned)((el * F + 8 * q + 4 * hi) * 4), pv);
+            if (el < na) spk_st<f32x4>(preB_g + (size_t)a0 * F + 32 * t, (unsigned)((el * F + 8 * q + 4 * hi) * 4), pv);
           }
         }
-        PM_BARRIER();
+        SPK_LDS_BARRIER();
         // ---- P6: (team 0: update)
       }
     }
@@ -980,14 +891,14 @@ __global__ __launch_bounds__(512) void k_painn_mol_fwd(PmFwdArgs a) {
       const PmHeadDev& Hd = a.head;
       long long my_mol = -1;
       if (wv == 1 && lane < 32) my_mol = lane < na ? Hd.idx_m[a0 + lane] : -2;      // wave 1: molecule id of atom `lane`
-      PM_BARRIER();                    // q_L is complete
+      SPK_LDS_BARRIER();                    // q_L is complete
       if (wv < 2) {                    // H = 64: two hidden tiles
         f32x4 av[16];
 #pragma unroll
-        for (int u = 0; u < 16; ++u) av[u] = pm_ld<f32x4>(Hd.w1 + (size_t)(32 * wv) * F, (unsigned)((el * F + 8 * u + 4 * hi) * 4));
+        for (int u = 0; u < 16; ++u) av[u] = spk_ld<f32x4>(Hd.w1 + (size_t)(32 * wv) * F, (unsigned)((el * F + 8 * u + 4 * hi) * 4));
         f32x16 acc;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = Hd.b1[32 * wv + pm_row(r, hi)];
+        for (int r = 0; r < 16; ++r) acc[r] = Hd.b1[32 * wv + spk_acc_row(r, hi)];
         const float* brow = sQ + el * PM_LD + 4 * hi;
         {
           f32x4 a0v[8], a1v[8];
@@ -1000,7 +911,7 @@ __global__ __launch_bounds__(512) void k_painn_mol_fwd(PmFwdArgs a) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           const f32x4 pv = {acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]};
-          if (el < na) pm_st<f32x4>(Hd.pre_h + (size_t)a0 * 64 + 32 * wv, (unsigned)((el * 64 + 8 * q + 4 * hi) * 4), pv);
+          if (el < na) spk_st<f32x4>(Hd.pre_h + (size_t)a0 * 64 + 32 * wv, (unsigned)((el * 64 + 8 * q + 4 * hi) * 4), pv);
           const f32x4 wv2 = *(const f32x4*)(Hd.w2 + 32 * wv + 8 * q + 4 * hi);
           if (Hd.act == SPK_ACT_SILU) part += pm_silu(pv.x) * wv2.x + pm_silu(pv.y) * wv2.y + pm_silu(pv.z) * wv2.z + pm_silu(pv.w) * wv2.w;
           else part += spk_ssp(pv.x) * wv2.x + spk_ssp(pv.y) * wv2.y + spk_ssp(pv.z) * wv2.z + spk_ssp(pv.w) * wv2.w;
@@ -1018,13 +929,13 @@ __global__ __launch_bounds__(512) void k_painn_mol_fwd(PmFwdArgs a) {
           *(f32x4*)(sC + PM_TILE + el * PM_LD + 32 * wv + 8 * q + 4 * hi) = gh;
         }
       }
-      PM_BARRIER();
+      SPK_LDS_BARRIER();
       // dE/dq_L = gh W1 (feature tile wv - 4 on waves 4..7, K = 64) -> global: the backward launch starts from it
       if (wv >= 4) {
         const int ft = wv - 4;
         f32x4 av[8];
 #pragma unroll
-        for (int u = 0; u < 8; ++u) av[u] = pm_ld<f32x4>(Hd.w1t + (size_t)(32 * ft) * 64, (unsigned)((el * 64 + 8 * u + 4 * hi) * 4));
+        for (int u = 0; u < 8; ++u) av[u] = spk_ld<f32x4>(Hd.w1t + (size_t)(32 * ft) * 64, (unsigned)((el * 64 + 8 * u + 4 * hi) * 4));
         f32x16 acc;
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[r] = 0.f;
@@ -1032,7 +943,7 @@ __global__ __launch_bounds__(512) void k_painn_mol_fwd(PmFwdArgs a) {
         if (el < na) {
 #pragma unroll
           for (int q = 0; q < 4; ++q)
-            pm_st<f32x4>(a.gq_out + (size_t)a0 * F + 32 * ft, (unsigned)((el * F + 8 * q + 4 * hi) * 4), f32x4{acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]});
+            spk_st<f32x4>(a.gq_out + (size_t)a0 * F + 32 * ft, (unsigned)((el * F + 8 * q + 4 * hi) * 4), f32x4{acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]});
         }
       }
       // wave 1 holds the molecule id of atom (lane) in my_mol: segment heads add their run, one atomic per (group, molecule)
@@ -1202,7 +1113,7 @@ __device__ __forceinline__ void pm_message_bwd(const PmFilt<K>& Wf, const float*
   int at = pm_next_atom(myAsg, ctr, na, 0, lane, dyn);
   if (at >= 0 && sRow[at] < sRow[at + 1]) {
     const unsigned co = (unsigned)__float_as_int(sEa[sRow[at]].x) * 1536u + lo;
-    cn0 = pm_ld<pm_f2>(c_g, co); cn1 = pm_ld<pm_f2>(c_g, co + 512u); cn2 = pm_ld<pm_f2>(c_g, co + 1024u);
+    cn0 = spk_ld<pm_f2>(c_g, co); cn1 = spk_ld<pm_f2>(c_g, co + 512u); cn2 = spk_ld<pm_f2>(c_g, co + 1024u);
   }
   // (a plain loop: one copy of the row code per instance instead of four -- and in the dynamic mode a wave may take more than four atoms)
   for (int it = 0; at >= 0; ++it) {
@@ -1225,7 +1136,7 @@ __device__ __forceinline__ void pm_message_bwd(const PmFilt<K>& Wf, const float*
         const pm_f2 cq = cn0, cR = cn1, cm = cn2;
         if (le + 1 < re) {
           const unsigned co = (unsigned)__float_as_int(sEa[le + 1].x) * 1536u + lo;
-          cn0 = pm_ld<pm_f2>(c_g, co); cn1 = pm_ld<pm_f2>(c_g, co + 512u); cn2 = pm_ld<pm_f2>(c_g, co + 1024u);
+          cn0 = spk_ld<pm_f2>(c_g, co); cn1 = spk_ld<pm_f2>(c_g, co + 512u); cn2 = spk_ld<pm_f2>(c_g, co + 1024u);
         }
         const float fc = myFc[le - rs], dfc = myFc[64 + le - rs];
         if (fc == 0.f && dfc == 0.f) continue;          // pairs at / beyond the cutoff contribute exactly zero
@@ -1280,12 +1191,12 @@ __device__ __forceinline__ void pm_message_bwd(const PmFilt<K>& Wf, const float*
       // the first context row of the wave's NEXT atom is requested BEFORE the result rows of this one are stored: behind the stores
       // the wait for it is a wait for their acknowledgement by L2
       pm_f2 cma = zero2;
-      if (!geom && !mu0) cma = pm_ld<pm_f2>(c_g, (unsigned)at * 1536u + 1024u + lo);
+      if (!geom && !mu0) cma = spk_ld<pm_f2>(c_g, (unsigned)at * 1536u + 1024u + lo);
       {
         at_next = pm_next_atom(myAsg, ctr, na, it + 1, lane, dyn);
         if (at_next >= 0 && sRow[at_next] < sRow[at_next + 1]) {
           const unsigned co = (unsigned)__float_as_int(sEa[sRow[at_next]].x) * 1536u + lo;
-          cn0 = pm_ld<pm_f2>(c_g, co); cn1 = pm_ld<pm_f2>(c_g, co + 512u); cn2 = pm_ld<pm_f2>(c_g, co + 1024u);
+          cn0 = spk_ld<pm_f2>(c_g, co); cn1 = spk_ld<pm_f2>(c_g, co + 512u); cn2 = spk_ld<pm_f2>(c_g, co + 1024u);
         }
       }
       if (!geom) {
@@ -1293,9 +1204,9 @@ __device__ __forceinline__ void pm_message_bwd(const PmFilt<K>& Wf, const float*
         pm_f2 gcm = zero2;
         if (!mu0) gcm = *(const pm_f2*)(sMuIn + io) * av0 + *(const pm_f2*)(sMuIn + PM_TILE + io) * av1 + *(const pm_f2*)(sMuIn + 2 * PM_TILE + io) * av2;
         const unsigned go = (unsigned)at * 1536u + lo;
-        pm_st<pm_f2>(gc_g, go, accq); pm_st<pm_f2>(gc_g, go + 512u, accR); pm_st<pm_f2>(gc_g, go + 1024u, gcm);
+        spk_st<pm_f2>(gc_g, go, accq); spk_st<pm_f2>(gc_g, go + 512u, accR); spk_st<pm_f2>(gc_g, go + 1024u, gcm);
         gma0 += cma * av0; gma1 += cma * av1; gma2 += cma * av2;
-        pm_st<pm_f2>(gmu_g, go, gma0); pm_st<pm_f2>(gmu_g, go + 512u, gma1); pm_st<pm_f2>(gmu_g, go + 1024u, gma2);
+        spk_st<pm_f2>(gmu_g, go, gma0); spk_st<pm_f2>(gmu_g, go + 512u, gma1); spk_st<pm_f2>(gmu_g, go + 1024u, gma2);
       }
       PM_MSTAMP(3 + 3 * (it < 4 ? it : 3));
     }
@@ -1320,7 +1231,7 @@ __device__ __forceinline__ void pm_split_send(float* __restrict__ X, const f32x1
 template <int Q0>
 __device__ __forceinline__ void pm_split_load_pre(f32x4 (&pre)[2], const float* __restrict__ pre_g /* + 32 t */, int el, int na, int hi) {
 #pragma unroll
-  for (int qq = 0; qq < 2; ++qq) pre[qq] = pm_ld<f32x4>(pre_g, (unsigned)(((el < na ? el : 0) * 128 + 8 * (Q0 + qq) + 4 * hi) * 4));
+  for (int qq = 0; qq < 2; ++qq) pre[qq] = spk_ld<f32x4>(pre_g, (unsigned)(((el < na ? el : 0) * 128 + 8 * (Q0 + qq) + 4 * hi) * 4));
 }
 template <int Q0>
 __device__ __forceinline__ void pm_split_finish(float* __restrict__ X, const f32x16& acc, const f32x4 (&pre)[2], int el, int na, int t, int hi) {
@@ -1383,7 +1294,7 @@ __global__ __launch_bounds__(512) void k_painn_mol_bwd(PmBwdArgs a) {
   for (int grp = blockIdx.x; grp < a.n_groups; grp += gridDim.x) {
     const int a0 = a.grp_atom0[grp], na = a.grp_atom0[grp + 1] - a0;
     const int e0 = a.rowptr[a0], ne = a.rowptr[a0 + na] - e0;
-    PM_BARRIER();
+    SPK_LDS_BARRIER();
     PM_BSTAMP(0);
     // ---- group set-up: incoming gradients, per-edge sums, local CSR and the wave -> atoms map of the message phase
     if (a.gq_out) pm_fill_tiles<2, false>(sGq, tid, na, [&](int, int r) { return a.gq_out + (size_t)(a0 + r) * F; });
@@ -1417,7 +1328,7 @@ __global__ __launch_bounds__(512) void k_painn_mol_bwd(PmBwdArgs a) {
       const float* a_g = S + 14 * nf + (size_t)a0 * 3 * F;
       const bool mu0 = (l == 0);
       const bool geom = (l == 0 && a.gq0 == nullptr);
-      PM_BARRIER();
+      SPK_LDS_BARRIER();
       PM_BSTAMP(1 + 12 * (a.n_layers - 1 - l));
 
       // ================= M1: ga_mu -> X0, ga_qmu -> X1, U = gq a_qmu -> X3                 (weights of M2 requested meanwhile)
@@ -1453,7 +1364,7 @@ __global__ __launch_bounds__(512) void k_painn_mol_bwd(PmBwdArgs a) {
           *(f32x4*)(X3 + row * PM_LD + 4 * c4) = live ? gq * aqm[rep] : z4;
         }
       }
-      PM_BARRIER();
+      SPK_LDS_BARRIER();
       PM_BSTAMP(2 + 12 * (a.n_layers - 1 - l));
 
       // ================= M2: g_hid = ([gq | ga_mu | ga_qmu] W_b2) silu'(pre_b) -> X2; team 0: k-blocks 0..23, team 1: 24..47
@@ -1474,13 +1385,13 @@ __global__ __launch_bounds__(512) void k_painn_mol_bwd(PmBwdArgs a) {
         if (a.dbg && blockIdx.x == 0 && lane == 0 && l == a.n_layers - 1) { asm volatile("s_nop 0" :: "v"(acc[0])); a.dbg[64 + 44 + wv] = (long long)__builtin_readcyclecounter(); }
         if (team == 0) pm_split_send<0>(X2, acc, el, t, hi);
         else pm_split_send<2>(X2, acc, el, t, hi);
-        PM_BARRIER();
+        SPK_LDS_BARRIER();
         if (l == a.n_layers - 1) PM_BSTAMP(41);
         if (team == 0) pm_split_finish<0>(X2, acc, pb, el, na, t, hi);
         else pm_split_finish<2>(X2, acc, pb, el, na, t, hi);
       }
       if (l == a.n_layers - 1) PM_BSTAMP(42);
-      PM_BARRIER();
+      SPK_LDS_BARRIER();
       PM_BSTAMP(3 + 12 * (a.n_layers - 1 - l));
 
       // ================= M3: g_ctx = g_hid W_b1: tiles 0..3 (q part, team 0): gq += ; tiles 4..7 (|V| part, team 1): g_nv -> X0
@@ -1502,7 +1413,7 @@ __global__ __launch_bounds__(512) void k_painn_mol_bwd(PmBwdArgs a) {
           *(f32x4*)xp = v;
         }
       }
-      PM_BARRIER();
+      SPK_LDS_BARRIER();
       PM_BSTAMP(4 + 12 * (a.n_layers - 1 - l));
 
       // ================= M4: per component x: gV -> X1, gW -> X2; gmu_x += [gV | gW] W_mix  (K = 256 split over the teams)
@@ -1550,7 +1461,7 @@ __global__ __launch_bounds__(512) void k_painn_mol_bwd(PmBwdArgs a) {
             nV[rep] = *(const f32x4*)mp; nW[rep] = *(const f32x4*)(mp + F);
           }
         }
-        PM_BARRIER();
+        SPK_LDS_BARRIER();
         f32x16 acc;
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[r] = 0.f;
@@ -1559,7 +1470,7 @@ __global__ __launch_bounds__(512) void k_painn_mol_bwd(PmBwdArgs a) {
         //  half into gmu_x; two barriers per component instead of three, nobody idle in the epilogue)
         if (team == 0) pm_split_send<0>(X0, acc, el, t, hi);
         else pm_split_send<2>(X0, acc, el, t, hi);
-        PM_BARRIER();
+        SPK_LDS_BARRIER();
         {
           float* gp = sGmu + x * PM_TILE + el * PM_LD + 32 * t + 4 * hi;
           const float* pp = X0 + el * PM_LD + 32 * t + 4 * hi;
@@ -1573,7 +1484,7 @@ __global__ __launch_bounds__(512) void k_painn_mol_bwd(PmBwdArgs a) {
         }
         cV[0] = nV[0]; cV[1] = nV[1]; cW[0] = nW[0]; cW[1] = nW[1];
       }
-      PM_BARRIER();
+      SPK_LDS_BARRIER();
       PM_BSTAMP(5 + 12 * (a.n_layers - 1 - l));
 
       // ================= message backward: mu entering the interaction -> X0..X2, edge records -> X3
@@ -1588,7 +1499,7 @@ __global__ __launch_bounds__(512) void k_painn_mol_bwd(PmBwdArgs a) {
         sEd[le] = d;
       }
       pm_filt_load<K>(Wf, P.wf, P.bf, lane, mu0);      // (requested before the tile fill the 120 registers pushed the message loop into scratch reloads)
-      PM_BARRIER();
+      SPK_LDS_BARRIER();
       PM_BSTAMP(6 + 12 * (a.n_layers - 1 - l));
       {
         float* gcs_w = a.gc_scratch + (size_t)a0 * 3 * F;
@@ -1603,7 +1514,7 @@ __global__ __launch_bounds__(512) void k_painn_mol_bwd(PmBwdArgs a) {
         if (geom) break;          // (uniform over the workgroup: the first interaction of an eval-mode backward ends here)
         pm_wload(W3, P.ctx2T_p, 48, t, 24 * team, lane);      // (weights of the context GEMM: they arrive while the wave waits for the others)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the gc / gmu rows of this wave have reached L2
-        PM_BARRIER();
+        SPK_LDS_BARRIER();
       }
       // ================= context net backward: gc -> X0..X2 (part planes), gq += ((gc W_a2) silu'(pre_a)) W_a1
       {
@@ -1625,7 +1536,7 @@ __global__ __launch_bounds__(512) void k_painn_mol_bwd(PmBwdArgs a) {
           *(f32x4*)(sGmu + (it >> 1) * PM_TILE + row * PM_LD + 4 * c4) = row < na ? vm[it] : z4;
         }
       }
-      PM_BARRIER();
+      SPK_LDS_BARRIER();
       PM_BSTAMP(8 + 12 * (a.n_layers - 1 - l));
       {
         const float* b0 = team ? X1 + 64 : X0;
@@ -1641,11 +1552,11 @@ __global__ __launch_bounds__(512) void k_painn_mol_bwd(PmBwdArgs a) {
         acc = pm_wmma_3chunks<SP>(W3, b0 + bo, b1 + bo, b2 + bo, lane, acc);
         if (team == 0) pm_split_send<0>(X3, acc, el, t, hi);
         else pm_split_send<2>(X3, acc, el, t, hi);
-        PM_BARRIER();
+        SPK_LDS_BARRIER();
         if (team == 0) pm_split_finish<0>(X3, acc, pa, el, na, t, hi);
         else pm_split_finish<2>(X3, acc, pa, el, na, t, hi);
       }
-      PM_BARRIER();
+      SPK_LDS_BARRIER();
       PM_BSTAMP(9 + 12 * (a.n_layers - 1 - l));
       if (team == 0) {
         pm_wload(Wn, P.ctx1T_p, 16, t, 0, lane);
@@ -1659,13 +1570,13 @@ __global__ __launch_bounds__(512) void k_painn_mol_bwd(PmBwdArgs a) {
           f32x4 v = *(const f32x4*)xp;
           v += f32x4{acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]};
           *(f32x4*)xp = v;
-          if (l == 0 && a.gq0 && el < na) pm_st<f32x4>(a.gq0 + (size_t)a0 * F + 32 * t, (unsigned)((el * F + 8 * q + 4 * hi) * 4), v);
+          if (l == 0 && a.gq0 && el < na) spk_st<f32x4>(a.gq0 + (size_t)a0 * F + 32 * t, (unsigned)((el * F + 8 * q + 4 * hi) * 4), v);
         }
       }
       PM_BSTAMP(10 + 12 * (a.n_layers - 1 - l));
     }
     // ---- the geometry gradient of every edge of the group, written exactly once
-    PM_BARRIER();
+    SPK_LDS_BARRIER();
     if (POT) {
       pm_pot_forces(sG, sRow, sRev, a.forces, a0, na);
     } else {

@@ -17,16 +17,16 @@
 #ifndef SPK_RT_HOLLOW
 #define SPK_RT_HOLLOW 0     // timing aid of the row-tile backward: 1 = no channel-block loop, 2 = no gathers, 3 = no GEMMs (results are wrong)
 #endif
+#include "spk_mfma_tile.h"
 #include "spk_split.h"
 #include "spk_filter_split.h"
 
-#define SPK_MFMA(A, B, C) __builtin_amdgcn_mfma_f32_32x32x2f32((A), (B), (C), 0, 0, 0)
 
 namespace {
 
 struct __attribute__((aligned(16))) TileRec { int i; int j; float ux; float uy; float uz; float invd; float r0; float r1; };
 
-// packed (Wf | bf): P[((t * KPB + ug) * 64 + lane) * 4 + v] = W'[32 t + (lane & 31)][8 ug + 4 (lane >> 5) + v],
+// packed image (spk_mfma_tile.h) of (Wf | bf), KPB k-blocks per tile:
 // W'[row][k] = wf[row][k] (k < K), bf[row] (k == K), 0 beyond
 template <int NSLOT>
 __device__ __forceinline__ void stage_filter(float* dst, const float* __restrict__ wf, const float* __restrict__ bf, int K, int KPB) {

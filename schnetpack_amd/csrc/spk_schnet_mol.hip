@@ -28,6 +28,7 @@
 #include "spk_common.h"
 #include "spk_pack.h"
 #include "spk_schnet_mol.h"
+#include "spk_mfma_tile.h"
 #include "spk_split.h"
 #include "spk_filter_split.h"
 
@@ -35,7 +36,6 @@
 #define ML_LD 132          // row stride (floats) of the [32][128] activation tiles in LDS: conflict-free 16-byte accesses
 #define ML_MAXPAIRS 384    // pairs per group (28 fully connected atoms; LDS budget of the backward)
 #define ML_MAXEDGES 768
-#define ML_MFMA(A, B, C) __builtin_amdgcn_mfma_f32_32x32x2f32((A), (B), (C), 0, 0, 0)
 
 struct MolPair;
 // The records region of `saved` (spk_schnet_mol_records_region()): what ml_pair_records() of the forward computed, as the backward's
@@ -155,11 +155,7 @@ __device__ __forceinline__ int ml_pair_records(MolPair* sP, short* sMap, int* sS
   return total;
 }
 
-// register r of the half hi of a 32x32 accumulator holds row (r & 3) + 8 (r >> 2) + 4 hi
-__device__ __forceinline__ int ml_row(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }
-
-// Packed LDS image of a weight matrix W[NOUT][K] (row-major, K padded with zeros to 8*KB):
-//   P[((t * KB + ug) * 64 + lane) * 4 + v] = W[32 t + (lane & 31)][8 ug + 4 (lane >> 5) + v]
+// Packed LDS image of a weight matrix W[NOUT][K] (row-major, K padded with zeros to 8*KB; the layout of spk_mfma_tile.h)
 template <int NTHREADS, int SLOTS>
 __device__ __forceinline__ void ml_stage_packed(float* dst, const float* __restrict__ w, int K, int KB, int tid) {
   constexpr int PER = (SLOTS + NTHREADS - 1) / NTHREADS;
@@ -258,15 +254,6 @@ __device__ __forceinline__ void ml_head_w1_store(h16x8* __restrict__ dh, h16x8* 
     }
   }
 }
-// One 32-column output tile of a Dense layer over the 32 atom rows of the group, T-GEMM convention of spk_dense.hip:
-// A = packed weights straight from L2 (16 k-blocks of 8, all requested up front), B = activations [32][ML_LD] in LDS;
-// accumulator rows = output features 32 t + ml_row(r, hi), columns = atoms (lane & 31).
-// Global accesses as  wave-uniform base (SGPR pair) + 32-bit per-lane byte offset: one VGPR per address instead of a 64-bit
-// pair -- with 64-bit per-lane addresses the compiler hoists dozens of address pairs out of the loops and spills them.
-template <class T>
-__device__ __forceinline__ T ml_ld(const void* sbase, unsigned voff) { return *(const T*)((const char*)sbase + voff); }
-template <class T>
-__device__ __forceinline__ void ml_st(void* sbase, unsigned voff, T v) { *(T*)((char*)sbase + voff) = v; }
 
 // gh[at][c] = sum over the directed edges of the row of `at`:  sSrc[neighbour][c] * g[pair][c] * f_c(pair)   (the transpose of
 // the forward's row sum), as a task of one wavefront per atom.
@@ -296,7 +283,7 @@ __device__ __forceinline__ void ml_row_sums4(float* __restrict__ sDst, const flo
       if (idx >= re) rec[u].y = 0;                 // weight 0 beyond the row
     }
 #pragma unroll
-    for (int u = 0; u < RB; ++u) gv[u] = ml_ld<f32x4>(g_g, ((unsigned)((rec[u].x >> 8) & 0xFFFF) * 128u + c4) * 4u);
+    for (int u = 0; u < RB; ++u) gv[u] = spk_ld<f32x4>(g_g, ((unsigned)((rec[u].x >> 8) & 0xFFFF) * 128u + c4) * 4u);
 #pragma unroll
     for (int u = 0; u < RB; ++u) {
       const f32x4 sv = *(const f32x4*)(sSrc + (rec[u].x & 255) * ML_LD + c4);
@@ -314,24 +301,22 @@ __device__ __forceinline__ void ml_row_sums4(float* __restrict__ sDst, const flo
   if (hi == 0) *(f32x4*)(sDst + at * ML_LD + c4) = acc;
 }
 
-// (the weights do not depend on the data: ml_dense_load() is issued a phase EARLY -- before the barrier that completes the
-// activations -- so that a Dense phase pays no L2 round trip)
-__device__ __forceinline__ void ml_dense_load(f32x4 (&av)[16], const float* __restrict__ wp, int t /* wave-uniform */, int lane) {
-  const char* sb = (const char*)wp + (size_t)t * (16 * 64 * 16);
-#pragma unroll
-  for (int u = 0; u < 16; ++u) av[u] = ml_ld<f32x4>(sb, (unsigned)(lane * 16 + u * 1024));
+// One 32-column output tile of a Dense layer over the 32 atom rows of the group is a Dense block of spk_mfma_tile.h: A = packed
+// weights straight from L2 (16 k-blocks of 8), B = activations [32][ML_LD] in LDS.
+// The weights do not depend on the data: ml_dense_load() is issued a phase EARLY -- before the barrier that completes the
+// activations -- so that a Dense phase pays no L2 round trip.  A whole tile (NB = 16) or half `half` of it (NB = 8): the first half
+// is requested a phase early (32 VGPRs across the phase in between), the second half at the start of the phase -- its latency
+// hides behind the 32 MFMAs of the first half
+template <int NB>
+__device__ __forceinline__ void ml_dense_load(f32x4 (&av)[NB], const float* __restrict__ wp, int t /* wave-uniform */, int lane, int half = 0) {
+  spk_tile_load(av, spk_tile_base(wp, 16, t, 8 * half), lane);
 }
-// (B operands are requested four k-blocks ahead of their MFMAs and pinned there: left alone the compiler issues every ds_read
-//  right in front of the four MFMAs that need it and the matrix pipe waits ~100 cycles per group -- round 3, found on spk_painn_mol.hip)
-#define ML_PIN() asm volatile("" ::: "memory")
-// The pin keeps the LOADS where they are written, not the matrix instructions: in the split chains whose operands all come from LDS
+// The pin (SPK_PIN) keeps the LOADS where they are written, not the matrix instructions: in the split chains whose operands all come from LDS
 // the scheduler moved every k-step up to its reads ("ds_read x 4, wait, three matrix instructions") and the distance was gone.  The
-// fence stops the scheduler as well.  Decided chain by chain, not in ML_PIN(): a fence costs registers -- on all pins of this file the
+// fence stops the scheduler as well.  Decided chain by chain, not in SPK_PIN(): a fence costs registers -- on all pins of this file the
 // split forward goes from 68 to 252 B per lane of scratch (profiles/r12_mol_matrix_overlap.md).
-#define ML_FENCE() do { ML_PIN(); __builtin_amdgcn_sched_barrier(0); } while (0)
-// Split form of a Dense block (SP; spk_split.h): `av` then holds chunks of the SPLIT weight image (k_pack_weight_split: chunk 2 s = the high
-// parts of k-step s, chunk 2 s + 1 its low parts -- same bytes, same offsets as the fp32 image), the activations are read from LDS
-// as eight consecutive fp32 values per k-step and split in registers; three f16 instructions per 16 k instead of eight f32 ones.
+#define ML_FENCE() do { SPK_PIN(); __builtin_amdgcn_sched_barrier(0); } while (0)
+// Split form of a Dense block (SP; spk_tile_mma_sp): the activations are read from the fp32 tile and split in registers.
 // This on-the-fly form serves the tiles that must stay fp32 in LDS because something else reads or accumulates into them (x, the two
 // partial sums y, dL/dx, the row sums dL/dh); a tile that is ONLY a B operand is written as the split image instead and read by
 // ml_dense_mma_sp_pre below (phase C2 of the forward).  The Dense phases of the backward stay on this form: their length is set by
@@ -339,31 +324,11 @@ __device__ __forceinline__ void ml_dense_load(f32x4 (&av)[16], const float* __re
 #ifndef SP_AHEAD
 #define SP_AHEAD 1      // k-steps of LDS operands requested ahead of their use in the split Dense blocks
 #endif
-template <int NS>
-__device__ __forceinline__ f32x16 ml_dense_mma_sp(const f32x4* __restrict__ av, const float* __restrict__ brow /* lane's row + 8 hi + first k */, f32x16 acc) {
-  f32x16 cx;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) cx[r] = 0.f;
-  f32x4 b0[NS], b1[NS];
-#pragma unroll
-  for (int s = 0; s < SP_AHEAD && s < NS; ++s) { b0[s] = *(const f32x4*)(brow + 16 * s); b1[s] = *(const f32x4*)(brow + 16 * s + 4); }
-  ML_PIN();
-#pragma unroll
-  for (int s = 0; s < NS; ++s) {
-    if (s + SP_AHEAD < NS) { b0[s + SP_AHEAD] = *(const f32x4*)(brow + 16 * (s + SP_AHEAD)); b1[s + SP_AHEAD] = *(const f32x4*)(brow + 16 * (s + SP_AHEAD) + 4); ML_PIN(); }
-    h16x4 h0, l0, h1, l1;
-    sp_split4(b0[s], h0, l0);
-    sp_split4(b1[s], h1, l1);
-    SP_STEP(__builtin_bit_cast(h16x8, av[2 * s]), __builtin_bit_cast(h16x8, av[2 * s + 1]), sp_cat(h0, h1), sp_cat(l0, l1), acc, cx);
-  }
-  SP_FOLD(acc, cx);
-  return acc;
-}
 // Pre-split form: the activation tile lies in LDS as the SPLIT IMAGE its writer made -- row = atom, stride ML_LD * 4 bytes, bytes
 // [0, 256) the 128 high halves, [256, 512) the 128 low halves (the layout of the hidden tile of phase A).  A k-step is two 16-byte
 // reads and SP_STEP: no vector-unit work in the loop, so the operands are requested SP_PRE_AHEAD k-steps ahead (4 = all of a half
 // tile up front; phase C2 of the forward 3.9 k cycles on the fp32 tile, 2.9 k with 2 ahead, 2.5 k with 4:
-// profiles/r09_mol_dense_operands.md).  Same products in the same order as ml_dense_mma_sp on the fp32 tile: the writer splits the
+// profiles/r09_mol_dense_operands.md).  Same products in the same order as spk_tile_mma_sp on the fp32 tile: the writer splits the
 // same fp32 values with the same sp_split.
 #ifndef SP_PRE_AHEAD
 #define SP_PRE_AHEAD 4
@@ -376,10 +341,10 @@ __device__ __forceinline__ f32x16 ml_dense_mma_sp_pre(const f32x4* __restrict__ 
   h16x8 bh[NS], bl[NS];
 #pragma unroll
   for (int s = 0; s < SP_PRE_AHEAD && s < NS; ++s) { bh[s] = *(const h16x8*)(brow + 32 * s); bl[s] = *(const h16x8*)(brow + 256 + 32 * s); }
-  ML_PIN();
+  SPK_PIN();
 #pragma unroll
   for (int s = 0; s < NS; ++s) {
-    if (s + SP_PRE_AHEAD < NS) { bh[s + SP_PRE_AHEAD] = *(const h16x8*)(brow + 32 * (s + SP_PRE_AHEAD)); bl[s + SP_PRE_AHEAD] = *(const h16x8*)(brow + 256 + 32 * (s + SP_PRE_AHEAD)); ML_PIN(); }
+    if (s + SP_PRE_AHEAD < NS) { bh[s + SP_PRE_AHEAD] = *(const h16x8*)(brow + 32 * (s + SP_PRE_AHEAD)); bl[s + SP_PRE_AHEAD] = *(const h16x8*)(brow + 256 + 32 * (s + SP_PRE_AHEAD)); SPK_PIN(); }
     SP_STEP(__builtin_bit_cast(h16x8, av[2 * s]), __builtin_bit_cast(h16x8, av[2 * s + 1]), bh[s], bl[s], acc, cx);
   }
   SP_FOLD(acc, cx);
@@ -397,56 +362,11 @@ __device__ __forceinline__ void ml_store_split4(float* __restrict__ tile, int ro
   *(h16x4*)p = h;
   *(h16x4*)(p + 256) = l;
 }
-template <bool SP = false>
-__device__ __forceinline__ f32x16 ml_dense_mma(const f32x4 (&av)[16], const float* __restrict__ sIn, int lane, f32x16 acc) {
-  const int hi = lane >> 5, el = lane & 31;
-  if constexpr (SP) return ml_dense_mma_sp<8>(av, sIn + el * ML_LD + 8 * hi, acc);
-  const float* brow = sIn + el * ML_LD + 4 * hi;
-  f32x4 bv[16];
-#pragma unroll
-  for (int u = 0; u < 4; ++u) bv[u] = *(const f32x4*)(brow + 8 * u);
-  ML_PIN();
-#pragma unroll
-  for (int u = 0; u < 16; ++u) {
-    acc = ML_MFMA(av[u].x, bv[u].x, acc);
-    acc = ML_MFMA(av[u].y, bv[u].y, acc);
-    acc = ML_MFMA(av[u].z, bv[u].z, acc);
-    acc = ML_MFMA(av[u].w, bv[u].w, acc);
-    if (u + 4 < 16) { bv[u + 4] = *(const f32x4*)(brow + 8 * (u + 4)); ML_PIN(); }
-  }
-  return acc;
-}
-// the same in halves of 8 k-blocks: the first half is requested a phase early (32 VGPRs across the phase in between), the
-// second half at the start of the phase -- its latency hides behind the 32 MFMAs of the first half
-__device__ __forceinline__ void ml_dense_load8(f32x4 (&av)[8], const float* __restrict__ wp, int t /* wave-uniform */, int lane, int half) {
-  const char* sb = (const char*)wp + (size_t)t * (16 * 64 * 16) + (size_t)half * (8 * 1024);
-#pragma unroll
-  for (int u = 0; u < 8; ++u) av[u] = ml_ld<f32x4>(sb, (unsigned)(lane * 16 + u * 1024));
-}
-template <bool SP = false>
-__device__ __forceinline__ f32x16 ml_dense_mma8(const f32x4 (&av)[8], const float* __restrict__ sIn, int lane, int half, f32x16 acc) {
-  const int hi = lane >> 5, el = lane & 31;
-  if constexpr (SP) return ml_dense_mma_sp<4>(av, sIn + el * ML_LD + 8 * hi + 64 * half, acc);
-  const float* brow = sIn + el * ML_LD + 4 * hi + 64 * half;
-  f32x4 bv[8];
-#pragma unroll
-  for (int u = 0; u < 4; ++u) bv[u] = *(const f32x4*)(brow + 8 * u);
-  ML_PIN();
-#pragma unroll
-  for (int u = 0; u < 8; ++u) {
-    acc = ML_MFMA(av[u].x, bv[u].x, acc);
-    acc = ML_MFMA(av[u].y, bv[u].y, acc);
-    acc = ML_MFMA(av[u].z, bv[u].z, acc);
-    acc = ML_MFMA(av[u].w, bv[u].w, acc);
-    if (u + 4 < 8) { bv[u + 4] = *(const f32x4*)(brow + 8 * (u + 4)); ML_PIN(); }
-  }
-  return acc;
-}
-template <bool SP = false>
-__device__ __forceinline__ f32x16 ml_dense_tile(const float* __restrict__ wp, const float* __restrict__ sIn, int t, int lane, f32x16 acc) {
-  f32x4 av[16];
-  ml_dense_load(av, wp, t, lane);
-  return ml_dense_mma<SP>(av, sIn, lane, acc);
+// NB k-blocks (a whole tile, or half `half` of it) against the LDS tile sIn
+template <bool SP = false, int NB>
+__device__ __forceinline__ f32x16 ml_dense_mma(const f32x4 (&av)[NB], const float* __restrict__ sIn, int lane, int half, f32x16 acc) {
+  if constexpr (SP) return spk_tile_mma_sp<NB / 2, SP_AHEAD>(av, spk_tile_brow<ML_LD, 8>(sIn, lane, 64 * half), acc);
+  return spk_tile_mma(av, spk_tile_brow<ML_LD>(sIn, lane, 64 * half), acc);
 }
 
 // B operand of a Dense half-tile that is the SUM of two LDS tiles (the two teams' partial cfconv outputs)
@@ -465,13 +385,13 @@ __device__ __forceinline__ f32x16 ml_dense_mma8_sum(const f32x4 (&av)[8], const 
       p0[s] = *(const f32x4*)(sIn0 + o + 16 * s); p1[s] = *(const f32x4*)(sIn0 + o + 16 * s + 4);
       q0[s] = *(const f32x4*)(sIn1 + o + 16 * s); q1[s] = *(const f32x4*)(sIn1 + o + 16 * s + 4);
     }
-    ML_PIN();
+    SPK_PIN();
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
       if (s + SP_AHEAD < 4) {
         p0[s + SP_AHEAD] = *(const f32x4*)(sIn0 + o + 16 * (s + SP_AHEAD)); p1[s + SP_AHEAD] = *(const f32x4*)(sIn0 + o + 16 * (s + SP_AHEAD) + 4);
         q0[s + SP_AHEAD] = *(const f32x4*)(sIn1 + o + 16 * (s + SP_AHEAD)); q1[s + SP_AHEAD] = *(const f32x4*)(sIn1 + o + 16 * (s + SP_AHEAD) + 4);
-        ML_PIN();
+        SPK_PIN();
       }
       h16x4 h0, l0, h1, l1;
       sp_split4(p0[s] + q0[s], h0, l0);
@@ -485,14 +405,14 @@ __device__ __forceinline__ f32x16 ml_dense_mma8_sum(const f32x4 (&av)[8], const 
   f32x4 b0[8], b1[8];
 #pragma unroll
   for (int u = 0; u < 4; ++u) { b0[u] = *(const f32x4*)(sIn0 + off + 8 * u); b1[u] = *(const f32x4*)(sIn1 + off + 8 * u); }
-  ML_PIN();
+  SPK_PIN();
 #pragma unroll
   for (int u = 0; u < 8; ++u) {
-    acc = ML_MFMA(av[u].x, b0[u].x + b1[u].x, acc);
-    acc = ML_MFMA(av[u].y, b0[u].y + b1[u].y, acc);
-    acc = ML_MFMA(av[u].z, b0[u].z + b1[u].z, acc);
-    acc = ML_MFMA(av[u].w, b0[u].w + b1[u].w, acc);
-    if (u + 4 < 8) { b0[u + 4] = *(const f32x4*)(sIn0 + off + 8 * (u + 4)); b1[u + 4] = *(const f32x4*)(sIn1 + off + 8 * (u + 4)); ML_PIN(); }
+    acc = SPK_MFMA(av[u].x, b0[u].x + b1[u].x, acc);
+    acc = SPK_MFMA(av[u].y, b0[u].y + b1[u].y, acc);
+    acc = SPK_MFMA(av[u].z, b0[u].z + b1[u].z, acc);
+    acc = SPK_MFMA(av[u].w, b0[u].w + b1[u].w, acc);
+    if (u + 4 < 8) { b0[u + 4] = *(const f32x4*)(sIn0 + off + 8 * (u + 4)); b1[u + 4] = *(const f32x4*)(sIn1 + off + 8 * (u + 4)); SPK_PIN(); }
   }
   return acc;
 }
@@ -547,7 +467,7 @@ __global__ __launch_bounds__(512) void k_schnet_mol_fwd(MolFwdArgs a) {
       const int row = s >> 5, c4 = s & 31;
       f32x4 v = {0.f, 0.f, 0.f, 0.f};
       if (row < na) {
-        if (a.x0) v = ml_ld<f32x4>(a.x0 + (size_t)a0 * NF, (unsigned)(s * 16));
+        if (a.x0) v = spk_ld<f32x4>(a.x0 + (size_t)a0 * NF, (unsigned)(s * 16));
         else {
           const long long z = a.Z[a0 + row];
           if (z >= 0 && z < a.n_types) v = *(const f32x4*)(a.emb + (size_t)z * NF + 4 * c4);
@@ -601,15 +521,17 @@ __global__ __launch_bounds__(512) void k_schnet_mol_fwd(MolFwdArgs a) {
         if (in2f) {
           // ---- h[:, 32t : 32t+32] = x W_in^T  (kept in LDS for the modulation, saved for the backward)
           f32x16 acc;
+          f32x4 av[16];
 #pragma unroll
           for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-          acc = ml_dense_tile<false>(P.in2f_p, sX, t, lane, acc);     // (fp32 image: this tile runs beside the other team's first pair tile, off the
-                                                                        //  critical path, and its split form pushed the kernel 170 B/lane further into scratch)
+          ml_dense_load(av, P.in2f_p, t, lane);
+          acc = ml_dense_mma(av, sX, lane, 0, acc);     // (fp32 image: this tile runs beside the other team's first pair tile, off the
+                                                        //  critical path, and its split form pushed the kernel 170 B/lane further into scratch)
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
             const f32x4 hv = {acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]};
             *(f32x4*)(sH + el * ML_LD + 32 * t + 8 * q + 4 * hi) = hv;
-            if (el < na) ml_st<f32x4>(h_g + (size_t)a0 * NF + 32 * t, (unsigned)((el * NF + 8 * q + 4 * hi) * 4), hv);
+            if (el < na) spk_st<f32x4>(h_g + (size_t)a0 * NF + 32 * t, (unsigned)((el * NF + 8 * q + 4 * hi) * 4), hv);
           }
         } else if (active) {
           // ---- this wave's quarter of the hidden layer: z[pairs][32t : 32t+32] = ssp(W1 phi + b1)
@@ -617,7 +539,7 @@ __global__ __launch_bounds__(512) void k_schnet_mol_fwd(MolFwdArgs a) {
           const float d = SP ? sP[pfirst + el].d : sP[pfirst + (el < nvalid ? el : (nvalid - 1))].d;
           f32x16 zc;
 #pragma unroll
-          for (int r = 0; r < 16; ++r) zc[r] = sb1[32 * t + ml_row(r, hi)];
+          for (int r = 0; r < 16; ++r) zc[r] = sb1[32 * t + spk_acc_row(r, hi)];
           if constexpr (SP) {
             // split form: A = the (high, low) images of W1, B = this pair's basis values in the lane's k-slots; three f16 matrix
             // instructions per k-step, the cross terms in their own accumulator
@@ -656,10 +578,10 @@ __global__ __launch_bounds__(512) void k_schnet_mol_fwd(MolFwdArgs a) {
               float dp;
               ml_rbf(a.rb.kind, a.rb.n_rbf, sRb, sRb + 32, 8 * u + 4 * hi + v, d, ph[v], dp);
             }
-            zc = ML_MFMA(wq.x, ph[0], zc);
-            zc = ML_MFMA(wq.y, ph[1], zc);
-            zc = ML_MFMA(wq.z, ph[2], zc);
-            zc = ML_MFMA(wq.w, ph[3], zc);
+            zc = SPK_MFMA(wq.x, ph[0], zc);
+            zc = SPK_MFMA(wq.y, ph[1], zc);
+            zc = SPK_MFMA(wq.z, ph[2], zc);
+            zc = SPK_MFMA(wq.w, ph[3], zc);
           }
 #pragma unroll
           for (int q = 0; q < 4; ++q)
@@ -716,14 +638,14 @@ __global__ __launch_bounds__(512) void k_schnet_mol_fwd(MolFwdArgs a) {
             f32x4 wb[KB2], zb[KB2];
 #pragma unroll
             for (int ug = 0; ug < 3; ++ug) { wb[ug] = *(const f32x4*)(wbase + ug * 256); zb[ug] = *(const f32x4*)(zrow + 8 * ug); }
-            ML_PIN();
+            SPK_PIN();
 #pragma unroll
             for (int ug = 0; ug < KB2; ++ug) {
-              if (ug + 3 < KB2) { wb[ug + 3] = *(const f32x4*)(wbase + (ug + 3) * 256); zb[ug + 3] = *(const f32x4*)(zrow + 8 * (ug + 3)); ML_PIN(); }
-              g = ML_MFMA(zb[ug].x, wb[ug].x, g);
-              g = ML_MFMA(zb[ug].y, wb[ug].y, g);
-              g = ML_MFMA(zb[ug].z, wb[ug].z, g);
-              g = ML_MFMA(zb[ug].w, wb[ug].w, g);
+              if (ug + 3 < KB2) { wb[ug + 3] = *(const f32x4*)(wbase + (ug + 3) * 256); zb[ug + 3] = *(const f32x4*)(zrow + 8 * (ug + 3)); SPK_PIN(); }
+              g = SPK_MFMA(zb[ug].x, wb[ug].x, g);
+              g = SPK_MFMA(zb[ug].y, wb[ug].y, g);
+              g = SPK_MFMA(zb[ug].z, wb[ug].z, g);
+              g = SPK_MFMA(zb[ug].w, wb[ug].w, g);
             }
           }
           // raw filter outputs for the backward (row = position of the pair in the list, 128-byte row segments per half wave)
@@ -735,7 +657,7 @@ __global__ __launch_bounds__(512) void k_schnet_mol_fwd(MolFwdArgs a) {
             // Branch-free: a padding row carries the record of the tile's last pair with f_c = 0 (padded once per group, above).  The
             // hidden layer took that pair's distance for the padded lanes, so the row of g is that pair's row bit for bit and the store
             // below writes the same value to the same address again (tests/test_gpu_mol_fwd_operands.py); its weight is zero.
-            const MolPair* sQ = sP + pfirst + 4 * hi;    // forward-side records: ml_fwd_pair(); row ml_row(r, hi) = ml_row(r, 0) + 4 hi
+            const MolPair* sQ = sP + pfirst + 4 * hi;    // forward-side records: ml_fwd_pair(); row spk_acc_row(r, hi) = spk_acc_row(r, 0) + 4 hi
             const char* hcol = (const char*)(sH + c0);
             const int own = el * (ML_LD * 4);
 #pragma unroll
@@ -745,9 +667,9 @@ __global__ __launch_bounds__(512) void k_schnet_mol_fwd(MolFwdArgs a) {
 #pragma unroll
               for (int e = 0; e < 8; ++e) {
                 const int r = 8 * s2 + e;
-                const MolPair rec = sQ[ml_row(r, 0)];
+                const MolPair rec = sQ[spk_acc_row(r, 0)];
                 const int oi = rec.ij & 0xFFFF, oj = rec.ij >> 16;
-                ml_st<float>(gt, (unsigned)(__float_as_int(rec.dfc) + el * 4), g[r]);
+                spk_st<float>(gt, (unsigned)(__float_as_int(rec.dfc) + el * 4), g[r]);
                 const float W = g[r] * rec.fc;
                 tI[e] = W * *(const float*)(hcol + oj); tJ[e] = W * *(const float*)(hcol + oi);
                 ai[e] = oi == own ? (_Float16)1.0f : (_Float16)0.0f;
@@ -765,24 +687,24 @@ __global__ __launch_bounds__(512) void k_schnet_mol_fwd(MolFwdArgs a) {
           } else {
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
-            const int pr = ml_row(r, hi);
+            const int pr = spk_acc_row(r, hi);
             const bool ok = pr < nvalid;
             const MolPair rec = sP[pfirst + (ok ? pr : 0)];
             const int pi = rec.ij & 255, pj = (rec.ij >> 8) & 255;
-            if (ok) ml_st<float>(gt, (unsigned)(((rec.ij >> 16) * NF + el) * 4), g[r]);
+            if (ok) spk_st<float>(gt, (unsigned)(((rec.ij >> 16) * NF + el) * 4), g[r]);
             const float W = ok ? g[r] * rec.fc : 0.f;
             const float tI = W * sH[pj * ML_LD + c0], tJ = W * sH[pi * ML_LD + c0];
-            yacc = ML_MFMA(pi == el ? 1.0f : 0.0f, tI, yacc);
-            yacc = ML_MFMA(pj == el ? 1.0f : 0.0f, tJ, yacc);
+            yacc = SPK_MFMA(pi == el ? 1.0f : 0.0f, tI, yacc);
+            yacc = SPK_MFMA(pj == el ? 1.0f : 0.0f, tJ, yacc);
           }
           }
         }
         __syncthreads();     // every wave of the team is done with the hidden tile
       }
       ML_STAMP(2 + 5 * l);
-      // the two teams' partial sums: rows = atoms ml_row(r, hi), columns = channels 32 t + el
+      // the two teams' partial sums: rows = atoms spk_acc_row(r, hi), columns = channels 32 t + el
 #pragma unroll
-      for (int r = 0; r < 16; ++r) zbuf[ml_row(r, hi) * ML_LD + 32 * t + el] = yacc[r];
+      for (int r = 0; r < 16; ++r) zbuf[spk_acc_row(r, hi) * ML_LD + 32 * t + el] = yacc[r];
       __syncthreads();
       ML_STAMP(4 + 5 * l);
 
@@ -794,18 +716,18 @@ __global__ __launch_bounds__(512) void k_schnet_mol_fwd(MolFwdArgs a) {
                            // stores share one in-order counter, a load issued behind a store cannot be waited for without it
       if (team == 0) {
         f32x4 avA[8], avB[8];
-        ml_dense_load8(avA, P.o1_p, t, lane, 0);
-        ml_dense_load8(avB, P.o1_p, t, lane, 1);
+        ml_dense_load(avA, P.o1_p, t, lane, 0);
+        ml_dense_load(avB, P.o1_p, t, lane, 1);
         f32x16 acc;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = P.o1_b[32 * t + ml_row(r, hi)];
+        for (int r = 0; r < 16; ++r) acc[r] = P.o1_b[32 * t + spk_acc_row(r, hi)];
         acc = ml_dense_mma8_sum<SP>(avA, sY, sT, lane, 0, acc);
         acc = ml_dense_mma8_sum<SP>(avB, sY, sT, lane, 1, acc);
-        ml_dense_load8(avC, P.o2_p, t, lane, 0);
+        ml_dense_load(avC, P.o2_p, t, lane, 0);
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           const f32x4 pv = {acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]};
-          if (el < na) ml_st<f32x4>(pre3_g + (size_t)a0 * NF + 32 * t, (unsigned)((el * NF + 8 * q + 4 * hi) * 4), pv);
+          if (el < na) spk_st<f32x4>(pre3_g + (size_t)a0 * NF + 32 * t, (unsigned)((el * NF + 8 * q + 4 * hi) * 4), pv);
           const f32x4 hv = {spk_fast_ssp(pv.x), spk_fast_ssp(pv.y), spk_fast_ssp(pv.z), spk_fast_ssp(pv.w)};
           if constexpr (SP) ml_store_split4(sH, el, 32 * t + 8 * q + 4 * hi, hv);
           else *(f32x4*)(sH + el * ML_LD + 32 * t + 8 * q + 4 * hi) = hv;
@@ -823,7 +745,7 @@ __global__ __launch_bounds__(512) void k_schnet_mol_fwd(MolFwdArgs a) {
             ml_w2_image_load(v, a.L[l + 1].w2_img, t2);
             ml_stage_w1_load<KPB>(x0, x1, a.L[l + 1].w1, a.rb.n_rbf, t2);
             if (t2 < NF) { bv1 = a.L[l + 1].b1[t2]; bv2 = a.L[l + 1].b2[t2]; }
-            ML_PIN();
+            SPK_PIN();
             ml_w2_image_store(sW2, v, t2);
             ml_stage_w1_store<KPB>(sW1h, sW1l, x0, x1, t2);
             if (t2 < NF) { sb1[t2] = bv1; sb2[t2] = bv2; }
@@ -852,7 +774,7 @@ __global__ __launch_bounds__(512) void k_schnet_mol_fwd(MolFwdArgs a) {
             ml_head_w1_load(v, Hd.w1, Hd.H / 32, t2);
             if (t2 < Hd.H) { hb1 = Hd.b1[t2]; hw2 = Hd.w2[t2]; }
             if (t2 == 0 && Hd.b2) hb2 = Hd.b2[0];
-            ML_PIN();
+            SPK_PIN();
             ml_head_w1_store(sW2h, sW2l, v, Hd.H / 32, t2);
             if (t2 < Hd.H) { sb1[t2] = hb1; sb2[t2] = hw2; }
             if (t2 == 0) sW1[0] = hb2;
@@ -866,16 +788,16 @@ __global__ __launch_bounds__(512) void k_schnet_mol_fwd(MolFwdArgs a) {
       // ================= phase C2: x += hidden W4^T + b4
       if (team == 0) {
         f32x4 avB[8];
-        ml_dense_load8(avB, P.o2_p, t, lane, 1);
+        ml_dense_load(avB, P.o2_p, t, lane, 1);
         f32x16 acc;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = P.o2_b[32 * t + ml_row(r, hi)];
+        for (int r = 0; r < 16; ++r) acc[r] = P.o2_b[32 * t + spk_acc_row(r, hi)];
         if constexpr (SP) {
           acc = ml_dense_mma8_pre(avC, sH, lane, 0, acc);
           acc = ml_dense_mma8_pre(avB, sH, lane, 1, acc);
         } else {
-          acc = ml_dense_mma8(avC, sH, lane, 0, acc);
-          acc = ml_dense_mma8(avB, sH, lane, 1, acc);
+          acc = ml_dense_mma(avC, sH, lane, 0, acc);
+          acc = ml_dense_mma(avB, sH, lane, 1, acc);
         }
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
@@ -884,7 +806,7 @@ __global__ __launch_bounds__(512) void k_schnet_mol_fwd(MolFwdArgs a) {
           xv.x += acc[4 * q]; xv.y += acc[4 * q + 1]; xv.z += acc[4 * q + 2]; xv.w += acc[4 * q + 3];
           if (el >= na) xv = f32x4{0.f, 0.f, 0.f, 0.f};       // padding rows stay zero (in2f has no bias: h pads stay zero too)
           *(f32x4*)xp = xv;
-          if (l + 1 == a.n_layers && el < na) ml_st<f32x4>(a.x_out + (size_t)a0 * NF + 32 * t, (unsigned)((el * NF + 8 * q + 4 * hi) * 4), xv);
+          if (l + 1 == a.n_layers && el < na) spk_st<f32x4>(a.x_out + (size_t)a0 * NF + 32 * t, (unsigned)((el * NF + 8 * q + 4 * hi) * 4), xv);
           if constexpr (SP) {      // x_L once more as the split image, the B operand of the energy head (sY: last read by phase C1)
             if (l + 1 == a.n_layers) ml_store_split4(sY, el, 32 * t + 8 * q + 4 * hi, xv);
           }
@@ -927,13 +849,13 @@ __global__ __launch_bounds__(512) void k_schnet_mol_fwd(MolFwdArgs a) {
           }
           f32x16 acc;
 #pragma unroll
-          for (int r = 0; r < 16; ++r) acc[r] = sb1[32 * hw + ml_row(r, hi)];
+          for (int r = 0; r < 16; ++r) acc[r] = sb1[32 * hw + spk_acc_row(r, hi)];
           acc = ml_dense_mma_sp_pre<8>(av, (const char*)sY + el * (ML_LD * 4) + 16 * hi, acc);
           float part = 0.f;
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
             const f32x4 pv = {acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]};
-            if (el < na) ml_st<f32x4>(Hd.pre_h + (size_t)a0 * Hd.H + 32 * hw, (unsigned)((el * Hd.H + 8 * q + 4 * hi) * 4), pv);
+            if (el < na) spk_st<f32x4>(Hd.pre_h + (size_t)a0 * Hd.H + 32 * hw, (unsigned)((el * Hd.H + 8 * q + 4 * hi) * 4), pv);
             const f32x4 wv2 = *(const f32x4*)(sb2 + 32 * hw + 8 * q + 4 * hi);
             if (Hd.act == SPK_ACT_SILU)
               part += pv.x * spk_sigmoid(pv.x) * wv2.x + pv.y * spk_sigmoid(pv.y) * wv2.y + pv.z * spk_sigmoid(pv.z) * wv2.z + pv.w * spk_sigmoid(pv.w) * wv2.w;
@@ -947,16 +869,16 @@ __global__ __launch_bounds__(512) void k_schnet_mol_fwd(MolFwdArgs a) {
       if (hw < HT) {
         f32x4 av[16];                     // (requested after the barrier: register arrays that live across one get spilled)
 #pragma unroll
-        for (int u = 0; u < 16; ++u) av[u] = ml_ld<f32x4>(Hd.w1 + (size_t)(32 * hw) * NF, (unsigned)((el * NF + 8 * u + 4 * hi) * 4));
+        for (int u = 0; u < 16; ++u) av[u] = spk_ld<f32x4>(Hd.w1 + (size_t)(32 * hw) * NF, (unsigned)((el * NF + 8 * u + 4 * hi) * 4));
         f32x16 acc;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = Hd.b1[32 * hw + ml_row(r, hi)];
-        acc = ml_dense_mma(av, sX, lane, acc);
+        for (int r = 0; r < 16; ++r) acc[r] = Hd.b1[32 * hw + spk_acc_row(r, hi)];
+        acc = ml_dense_mma(av, sX, lane, 0, acc);
         float part = 0.f;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           const f32x4 pv = {acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]};
-          if (el < na) ml_st<f32x4>(Hd.pre_h + (size_t)a0 * Hd.H + 32 * hw, (unsigned)((el * Hd.H + 8 * q + 4 * hi) * 4), pv);
+          if (el < na) spk_st<f32x4>(Hd.pre_h + (size_t)a0 * Hd.H + 32 * hw, (unsigned)((el * Hd.H + 8 * q + 4 * hi) * 4), pv);
           const f32x4 wv2 = *(const f32x4*)(Hd.w2 + 32 * hw + 8 * q + 4 * hi);
           if (Hd.act == SPK_ACT_SILU)
             part += pv.x * spk_sigmoid(pv.x) * wv2.x + pv.y * spk_sigmoid(pv.y) * wv2.y + pv.z * spk_sigmoid(pv.z) * wv2.z + pv.w * spk_sigmoid(pv.w) * wv2.w;
@@ -1227,7 +1149,7 @@ __global__ __launch_bounds__(512) void k_schnet_mol_bwd(MolBwdArgs a) {
     for (int s = tid; s < 32 * 32; s += 512) {
       const int row = s >> 5, c4 = s & 31;
       f32x4 v = {0.f, 0.f, 0.f, 0.f};
-      if (row < na && a.gx_out) v = ml_ld<f32x4>(a.gx_out + (size_t)a0 * NF, (unsigned)(s * 16));
+      if (row < na && a.gx_out) v = spk_ld<f32x4>(a.gx_out + (size_t)a0 * NF, (unsigned)(s * 16));
       *(f32x4*)(sGx + row * ML_LD + 4 * c4) = v;
       *(f32x4*)(sH + row * ML_LD + 4 * c4) = f32x4{0.f, 0.f, 0.f, 0.f};
       if (!with_head) *(f32x4*)(sGh + row * ML_LD + 4 * c4) = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -1241,12 +1163,12 @@ __global__ __launch_bounds__(512) void k_schnet_mol_bwd(MolBwdArgs a) {
       ho_np = a.ho.np[grp];
       ho_np = ho_np < 0 ? 0 : (ho_np > np_list ? np_list : ho_np);      // (never beyond the group's span of the region)
       if (tid < np_list) {
-        ho_map = ml_ld<int>(a.ho.map + p0, (unsigned)tid * 4u);
-        pr3[0] = ml_ld<float>(a.ho.vec + 3 * (size_t)p0, (unsigned)tid * 12u);
-        pr3[1] = ml_ld<float>(a.ho.vec + 3 * (size_t)p0, (unsigned)tid * 12u + 4u);
-        pr3[2] = ml_ld<float>(a.ho.vec + 3 * (size_t)p0, (unsigned)tid * 12u + 8u);
+        ho_map = spk_ld<int>(a.ho.map + p0, (unsigned)tid * 4u);
+        pr3[0] = spk_ld<float>(a.ho.vec + 3 * (size_t)p0, (unsigned)tid * 12u);
+        pr3[1] = spk_ld<float>(a.ho.vec + 3 * (size_t)p0, (unsigned)tid * 12u + 4u);
+        pr3[2] = spk_ld<float>(a.ho.vec + 3 * (size_t)p0, (unsigned)tid * 12u + 8u);
       }
-      if (tid < ho_np) ho_pr = ml_ld<MolPair>(a.ho.rec + p0, (unsigned)tid * 16u);
+      if (tid < ho_np) ho_pr = spk_ld<MolPair>(a.ho.rec + p0, (unsigned)tid * 16u);
     }
     if (with_head) {
       // ---- dL/dx_L through the energy head, part 1: the hidden gradient gE[mol] w2 . act'(pre_h) -> sGh[:, :H]
@@ -1290,16 +1212,16 @@ __global__ __launch_bounds__(512) void k_schnet_mol_bwd(MolBwdArgs a) {
 #pragma unroll
           for (int u = 0; u < 8; ++u) {
             a8[u] = f32x4{0.f, 0.f, 0.f, 0.f};
-            if (c + u < KH) a8[u] = ml_ld<f32x4>(Hd.w1t + (size_t)(32 * t) * Hd.H, (unsigned)((el * Hd.H + 8 * (c + u) + 4 * hi) * 4));
+            if (c + u < KH) a8[u] = spk_ld<f32x4>(Hd.w1t + (size_t)(32 * t) * Hd.H, (unsigned)((el * Hd.H + 8 * (c + u) + 4 * hi) * 4));
           }
 #pragma unroll
           for (int u = 0; u < 8; ++u) {
             if (c + u < KH) {
               const f32x4 bv = *(const f32x4*)(brow + 8 * (c + u));
-              acc = ML_MFMA(a8[u].x, bv.x, acc);
-              acc = ML_MFMA(a8[u].y, bv.y, acc);
-              acc = ML_MFMA(a8[u].z, bv.z, acc);
-              acc = ML_MFMA(a8[u].w, bv.w, acc);
+              acc = SPK_MFMA(a8[u].x, bv.x, acc);
+              acc = SPK_MFMA(a8[u].y, bv.y, acc);
+              acc = SPK_MFMA(a8[u].z, bv.z, acc);
+              acc = SPK_MFMA(a8[u].w, bv.w, acc);
             }
           }
         }
@@ -1318,9 +1240,9 @@ __global__ __launch_bounds__(512) void k_schnet_mol_bwd(MolBwdArgs a) {
       const int t2 = tid - 256;
       const int row0 = np > 0 ? (sP[0].ij >> 16) : 0;
       for (int s = t2; s < ne; s += 256) {
-        const int pos = ml_ld<int>(a.edge_pair + e0, (unsigned)s * 4u) - p0;
+        const int pos = spk_ld<int>(a.edge_pair + e0, (unsigned)s * 4u) - p0;
         const int rec = sMap[pos];
-        const int nb = (int)(ml_ld<long long>(a.idx_j + e0, (unsigned)s * 8u) - a0);
+        const int nb = (int)(spk_ld<long long>(a.idx_j + e0, (unsigned)s * 8u) - a0);
         sEb[s] = rec >= 0 ? make_int2((pos << 8) | nb, __float_as_int(sP[rec].fc)) : make_int2((row0 << 8) | nb | (1 << 24), 0);
       }
       for (int s = t2; s < 2 * np; s += 256) sS[s] = 0.f;
@@ -1340,8 +1262,8 @@ __global__ __launch_bounds__(512) void k_schnet_mol_bwd(MolBwdArgs a) {
       if (wv < NT) {
         const int t = wv;
         f32x4 avA[8], avB[8];
-        ml_dense_load8(avA, P.o2_t, t, lane, 0);
-        ml_dense_load8(avB, P.o2_t, t, lane, 1);
+        ml_dense_load(avA, P.o2_t, t, lane, 0);
+        ml_dense_load(avB, P.o2_t, t, lane, 1);
         f32x16 acc;
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[r] = 0.f;
@@ -1349,10 +1271,10 @@ __global__ __launch_bounds__(512) void k_schnet_mol_bwd(MolBwdArgs a) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           pv[q] = f32x4{0.f, 0.f, 0.f, 0.f};
-          if (el < na) pv[q] = ml_ld<f32x4>(pre3_g + (size_t)a0 * NF + 32 * t, (unsigned)((el * NF + 8 * q + 4 * hi) * 4));
+          if (el < na) pv[q] = spk_ld<f32x4>(pre3_g + (size_t)a0 * NF + 32 * t, (unsigned)((el * NF + 8 * q + 4 * hi) * 4));
         }
-        acc = ml_dense_mma8<SP>(avA, sGx, lane, 0, acc);
-        acc = ml_dense_mma8<SP>(avB, sGx, lane, 1, acc);
+        acc = ml_dense_mma<SP>(avA, sGx, lane, 0, acc);
+        acc = ml_dense_mma<SP>(avB, sGx, lane, 1, acc);
 #pragma unroll
         for (int q = 0; q < 4; ++q)
           *(f32x4*)(sGh + el * ML_LD + 32 * t + 8 * q + 4 * hi) =
@@ -1370,13 +1292,13 @@ __global__ __launch_bounds__(512) void k_schnet_mol_bwd(MolBwdArgs a) {
       if (wv < NT) {
         const int t = wv;
         f32x4 avA[8], avB[8];
-        ml_dense_load8(avA, P.o1_t, t, lane, 0);
-        ml_dense_load8(avB, P.o1_t, t, lane, 1);
+        ml_dense_load(avA, P.o1_t, t, lane, 0);
+        ml_dense_load(avB, P.o1_t, t, lane, 1);
         f32x16 acc;
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-        acc = ml_dense_mma8<SP>(avA, sGh, lane, 0, acc);
-        acc = ml_dense_mma8<SP>(avB, sGh, lane, 1, acc);
+        acc = ml_dense_mma<SP>(avA, sGh, lane, 0, acc);
+        acc = ml_dense_mma<SP>(avB, sGh, lane, 1, acc);
 #pragma unroll
         for (int q = 0; q < 4; ++q)
           *(f32x4*)(sGy + el * ML_LD + 32 * t + 8 * q + 4 * hi) = f32x4{acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]};
@@ -1384,7 +1306,7 @@ __global__ __launch_bounds__(512) void k_schnet_mol_bwd(MolBwdArgs a) {
         const int t2 = tid - 256;
         for (int s = t2; s < na * 32; s += 256) {
           const int row = s >> 5, c4 = s & 31;
-          *(f32x4*)(sH + row * ML_LD + 4 * c4) = ml_ld<f32x4>(h_g + (size_t)a0 * NF, (unsigned)(s * 16));
+          *(f32x4*)(sH + row * ML_LD + 4 * c4) = spk_ld<f32x4>(h_g + (size_t)a0 * NF, (unsigned)(s * 16));
         }
         if constexpr (SP) ml_stage_w1_split<KPB>(sW1h, sW1l, P.w1, a.rb.n_rbf, t2);
         else ml_stage_packed<256, NF * KPB * 2>(sW1, P.w1, a.rb.n_rbf, KPB, t2);
@@ -1421,8 +1343,8 @@ __global__ __launch_bounds__(512) void k_schnet_mol_bwd(MolBwdArgs a) {
           // ---- G, channel tile t: gx[:, 32 t : 32 t + 32] += gh W_in (weights requested before the wait for the row sums)
           const int t = k - nder - nrow;
           f32x4 avA[8], avB[8];
-          ml_dense_load8(avA, P.in2f_t, t, lane, 0);
-          ml_dense_load8(avB, P.in2f_t, t, lane, 1);
+          ml_dense_load(avA, P.in2f_t, t, lane, 0);
+          ml_dense_load(avB, P.in2f_t, t, lane, 1);
           if (nrow > 0) {
             while (__hip_atomic_load(&sCnt[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < nrow) __builtin_amdgcn_s_sleep(2);
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
@@ -1430,8 +1352,8 @@ __global__ __launch_bounds__(512) void k_schnet_mol_bwd(MolBwdArgs a) {
           f32x16 acc;
 #pragma unroll
           for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-          acc = ml_dense_mma8<SP>(avA, sGh, lane, 0, acc);
-          acc = ml_dense_mma8<SP>(avB, sGh, lane, 1, acc);
+          acc = ml_dense_mma<SP>(avA, sGh, lane, 0, acc);
+          acc = ml_dense_mma<SP>(avB, sGh, lane, 1, acc);
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
             float* xp = sGx + el * ML_LD + 32 * t + 8 * q + 4 * hi;
@@ -1439,7 +1361,7 @@ __global__ __launch_bounds__(512) void k_schnet_mol_bwd(MolBwdArgs a) {
             xv.x += acc[4 * q]; xv.y += acc[4 * q + 1]; xv.z += acc[4 * q + 2]; xv.w += acc[4 * q + 3];
             if (el >= na) xv = f32x4{0.f, 0.f, 0.f, 0.f};
             *(f32x4*)xp = xv;
-            if (l == 0 && el < na) ml_st<f32x4>(a.gx0 + (size_t)a0 * NF + 32 * t, (unsigned)((el * NF + 8 * q + 4 * hi) * 4), xv);
+            if (l == 0 && el < na) spk_st<f32x4>(a.gx0 + (size_t)a0 * NF + 32 * t, (unsigned)((el * NF + 8 * q + 4 * hi) * 4), xv);
           }
           continue;
         }
@@ -1477,7 +1399,7 @@ __global__ __launch_bounds__(512) void k_schnet_mol_bwd(MolBwdArgs a) {
           for (int c = 0; c < NT; ++c) {
             f32x16 zc, zcx, zq, zqx;
 #pragma unroll
-            for (int r = 0; r < 16; ++r) { zc[r] = sb1[32 * c + ml_row(r, hi_o)]; zcx[r] = 0.f; zq[r] = 0.f; zqx[r] = 0.f; }
+            for (int r = 0; r < 16; ++r) { zc[r] = sb1[32 * c + spk_acc_row(r, hi_o)]; zcx[r] = 0.f; zq[r] = 0.f; zqx[r] = 0.f; }
 #pragma unroll
             for (int s = 0; s < (KPB > 2 ? 2 : 1); ++s) {
               h16x8 wh, wl;
@@ -1498,7 +1420,7 @@ __global__ __launch_bounds__(512) void k_schnet_mol_bwd(MolBwdArgs a) {
               sp_split8(v, zph[c][sp], zpl[c][sp]);
             }
           }
-          // ---- GEMM 2' per channel tile (rows = channels 32 t + ml_row(r, hi), columns = pairs): g' = W2 z'
+          // ---- GEMM 2' per channel tile (rows = channels 32 t + spk_acc_row(r, hi), columns = pairs): g' = W2 z'
           const float* gyi_p = sGy + pi * ML_LD + 4 * hi_o;
           const float* gyj_p = sGy + pj * ML_LD + 4 * hi_o;
           const float* hi_p = sH + pi * ML_LD + 4 * hi_o;
@@ -1511,7 +1433,7 @@ __global__ __launch_bounds__(512) void k_schnet_mol_bwd(MolBwdArgs a) {
 #pragma unroll
             for (int tt = 0; tt < 2; ++tt)
 #pragma unroll
-              for (int q = 0; q < 4; ++q) gl[tt][q] = ml_ld<f32x4>(g_g + 64 * tp, (unsigned)((grow * NF + 4 * hi + 32 * tt + 8 * q) * 4));
+              for (int q = 0; q < 4; ++q) gl[tt][q] = spk_ld<f32x4>(g_g + 64 * tp, (unsigned)((grow * NF + 4 * hi + 32 * tt + 8 * q) * 4));
             float s1 = 0.f, s2 = 0.f;
 #pragma unroll
             for (int tt = 0; tt < 2; ++tt) {
@@ -1565,15 +1487,15 @@ __global__ __launch_bounds__(512) void k_schnet_mol_bwd(MolBwdArgs a) {
           f32x4 wq = *(const f32x4*)(sW1 + lane * 4);
           f32x16 zc, zq;
 #pragma unroll
-          for (int r = 0; r < 16; ++r) { zc[r] = sb1[ml_row(r, hi)]; zq[r] = 0.f; }
+          for (int r = 0; r < 16; ++r) { zc[r] = sb1[spk_acc_row(r, hi)]; zq[r] = 0.f; }
 #pragma unroll
           for (int u = 0; u < KPB; ++u) {
             f32x4 wn = wq;
             if (u + 1 < NT * KPB) wn = *(const f32x4*)(sW1 + ((u + 1) * 64 + lane) * 4);
-            zc = ML_MFMA(wq.x, phi[u][0], zc); zq = ML_MFMA(wq.x, dphi[u][0], zq);
-            zc = ML_MFMA(wq.y, phi[u][1], zc); zq = ML_MFMA(wq.y, dphi[u][1], zq);
-            zc = ML_MFMA(wq.z, phi[u][2], zc); zq = ML_MFMA(wq.z, dphi[u][2], zq);
-            zc = ML_MFMA(wq.w, phi[u][3], zc); zq = ML_MFMA(wq.w, dphi[u][3], zq);
+            zc = SPK_MFMA(wq.x, phi[u][0], zc); zq = SPK_MFMA(wq.x, dphi[u][0], zq);
+            zc = SPK_MFMA(wq.y, phi[u][1], zc); zq = SPK_MFMA(wq.y, dphi[u][1], zq);
+            zc = SPK_MFMA(wq.z, phi[u][2], zc); zq = SPK_MFMA(wq.z, dphi[u][2], zq);
+            zc = SPK_MFMA(wq.w, phi[u][3], zc); zq = SPK_MFMA(wq.w, dphi[u][3], zq);
             wq = wn;
           }
 #pragma unroll
@@ -1581,7 +1503,7 @@ __global__ __launch_bounds__(512) void k_schnet_mol_bwd(MolBwdArgs a) {
             f32x16 zcn = zc, zqn = zq;
             if (c + 1 < NT) {
 #pragma unroll
-              for (int r = 0; r < 16; ++r) { zcn[r] = sb1[32 * (c + 1) + ml_row(r, hi)]; zqn[r] = 0.f; }
+              for (int r = 0; r < 16; ++r) { zcn[r] = sb1[32 * (c + 1) + spk_acc_row(r, hi)]; zqn[r] = 0.f; }
 #pragma unroll
               for (int u = 0; u < KPB; ++u) {
                 const int nxt = (c + 1) * KPB + u + 1;
@@ -1590,8 +1512,8 @@ __global__ __launch_bounds__(512) void k_schnet_mol_bwd(MolBwdArgs a) {
                 const float wv4[4] = {wq.x, wq.y, wq.z, wq.w};
 #pragma unroll
                 for (int v = 0; v < 4; ++v) {
-                  zcn = ML_MFMA(wv4[v], phi[u][v], zcn);
-                  zqn = ML_MFMA(wv4[v], dphi[u][v], zqn);
+                  zcn = SPK_MFMA(wv4[v], phi[u][v], zcn);
+                  zqn = SPK_MFMA(wv4[v], dphi[u][v], zqn);
                   const int st = 4 * u + v;
 #pragma unroll
                   for (int r = (16 * st) / NSTEP; r < (16 * (st + 1)) / NSTEP; ++r) {
@@ -1614,7 +1536,7 @@ __global__ __launch_bounds__(512) void k_schnet_mol_bwd(MolBwdArgs a) {
             zc = zcn; zq = zqn;
           }
         }
-        // ---- GEMM 2' per channel tile (rows = channels 32 t + ml_row(r, hi), columns = pairs): g' = W2 z'
+        // ---- GEMM 2' per channel tile (rows = channels 32 t + spk_acc_row(r, hi), columns = pairs): g' = W2 z'
         const float* gyi_p = sGy + pi * ML_LD + 4 * hi;
         const float* gyj_p = sGy + pj * ML_LD + 4 * hi;
         const float* hi_p = sH + pi * ML_LD + 4 * hi;
@@ -1627,7 +1549,7 @@ __global__ __launch_bounds__(512) void k_schnet_mol_bwd(MolBwdArgs a) {
 #pragma unroll
           for (int tt = 0; tt < 2; ++tt)
 #pragma unroll
-            for (int q = 0; q < 4; ++q) gl[tt][q] = ml_ld<f32x4>(g_g + 64 * tp, (unsigned)((grow * NF + 4 * hi + 32 * tt + 8 * q) * 4));
+            for (int q = 0; q < 4; ++q) gl[tt][q] = spk_ld<f32x4>(g_g + 64 * tp, (unsigned)((grow * NF + 4 * hi + 32 * tt + 8 * q) * 4));
           float s1 = 0.f, s2 = 0.f;
 #pragma unroll
           for (int tt = 0; tt < 2; ++tt) {
@@ -1642,15 +1564,15 @@ __global__ __launch_bounds__(512) void k_schnet_mol_bwd(MolBwdArgs a) {
               f32x4 wb[KB2];
 #pragma unroll
               for (int ug = 0; ug < 3; ++ug) wb[ug] = *(const f32x4*)(wbase + ug * 256);
-              ML_PIN();
+              SPK_PIN();
 #pragma unroll
               for (int ug = 0; ug < KB2; ++ug) {
                 const int c = ug >> 2, q = ug & 3;
-                if (ug + 3 < KB2) { wb[ug + 3] = *(const f32x4*)(wbase + (ug + 3) * 256); ML_PIN(); }
-                gp = ML_MFMA(wb[ug].x, zp[c][4 * q + 0], gp);
-                gp = ML_MFMA(wb[ug].y, zp[c][4 * q + 1], gp);
-                gp = ML_MFMA(wb[ug].z, zp[c][4 * q + 2], gp);
-                gp = ML_MFMA(wb[ug].w, zp[c][4 * q + 3], gp);
+                if (ug + 3 < KB2) { wb[ug + 3] = *(const f32x4*)(wbase + (ug + 3) * 256); SPK_PIN(); }
+                gp = SPK_MFMA(wb[ug].x, zp[c][4 * q + 0], gp);
+                gp = SPK_MFMA(wb[ug].y, zp[c][4 * q + 1], gp);
+                gp = SPK_MFMA(wb[ug].z, zp[c][4 * q + 2], gp);
+                gp = SPK_MFMA(wb[ug].w, zp[c][4 * q + 3], gp);
               }
             }
 #pragma unroll

@@ -55,7 +55,7 @@ __device__ __forceinline__ h16x8 sp_cat(const h16x4 a, const h16x4 b) { return h
 #define SP_FOLD(MAIN, CROSS) \
   do { _Pragma("unroll") for (int r_ = 0; r_ < 16; ++r_) (MAIN)[r_] = fmaf((CROSS)[r_], SP_DOWN, (MAIN)[r_]); } while (0)
 
-// Accumulator order of the contraction index: register r of lane half `hi` of a 32 x 32 accumulator holds row (r & 3) + 8 (r >> 2) + 4 hi.
+// Accumulator order of the contraction index: register r of lane half `hi` of a 32 x 32 accumulator holds row spk_acc_row(r, hi) = (r & 3) + 8 (r >> 2) + 4 hi (spk_mfma_tile.h).
 // When the 16 values a lane holds become the B (or A) operand of the NEXT product, k-step s' in {0, 1} takes its registers 8 s' .. 8 s' + 7
 // as they lie; the other operand must then be laid out so that slot (s', hi, e) of a 32-wide k block is index
 //        sp_acc_k(s', hi, e) = (e & 3) + 8 (2 s' + (e >> 2)) + 4 hi

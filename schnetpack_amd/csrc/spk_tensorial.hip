@@ -24,6 +24,7 @@
 //                    reference's 0 / 0 charge correction of such a molecule is never gathered by an atom).
 #include <math.h>
 #include "spk_common.h"
+#include "spk_mfma_tile.h"
 
 namespace {
 
@@ -71,18 +72,17 @@ __device__ __forceinline__ void gm_mm(const float* A, int lda, int plane, const 
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
       const f32x4 a = *(const f32x4*)(arow + c * plane + kb);
-      acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b.x, acc[c], 0, 0, 0);
-      acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b.y, acc[c], 0, 0, 0);
-      acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b.z, acc[c], 0, 0, 0);
-      acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b.w, acc[c], 0, 0, 0);
+      acc[c] = SPK_MFMA(a.x, b.x, acc[c]);
+      acc[c] = SPK_MFMA(a.y, b.y, acc[c]);
+      acc[c] = SPK_MFMA(a.z, b.z, acc[c]);
+      acc[c] = SPK_MFMA(a.w, b.w, acc[c]);
     }
   }
 }
 // |(x, y, z)| as ONE chain of explicit fused operations.  Written as x x + y y + z z the sixteen norms of an accumulator were contracted (and packed
 // by the SLP vectoriser) differently from register to register, so the last bit of an atom's result depended on its row in the tile.
 __device__ __forceinline__ float gm_norm3(float x, float y, float z) { return sqrtf(fmaf(z, z, fmaf(y, y, x * x))); }
-// row (atom of the tile) of accumulator register r in lane half hi; the column is lane & 31
-__device__ __forceinline__ int gm_row(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }
+// (spk_acc_row(r, hi): row = atom of the tile of accumulator register r in lane half hi; the column is lane & 31)
 
 template <int F, int ACT>
 __global__ __launch_bounds__(64 * kGmWaves) void k_gated_mlp(GmArgs a) {
@@ -125,12 +125,12 @@ __global__ __launch_bounds__(64 * kGmWaves) void k_gated_mlp(GmArgs a) {
     if (o0 < H) {
 #pragma unroll
       for (int r = 0; r < 16; ++r)
-        ctx[gm_row(r, hi) * L::LDC + F + o0 + col] = gm_norm3(acc[0][r], acc[1][r], acc[2][r]);
+        ctx[spk_acc_row(r, hi) * L::LDC + F + o0 + col] = gm_norm3(acc[0][r], acc[1][r], acc[2][r]);
     } else {
 #pragma unroll
       for (int c = 0; c < 3; ++c)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) wv[(c * kGmTile + gm_row(r, hi)) * L::LDW + o0 - H + col] = acc[c][r];
+        for (int r = 0; r < 16; ++r) wv[(c * kGmTile + spk_acc_row(r, hi)) * L::LDW + o0 - H + col] = acc[c][r];
     }
   }
   __syncthreads();      // (the v tile is dead from here: hid / s1 / h1 take its place)
@@ -144,7 +144,7 @@ __global__ __launch_bounds__(64 * kGmWaves) void k_gated_mlp(GmArgs a) {
     gm_mm<1, true>(ctx, L::LDC, 0, a.w10 + (size_t)o0 * (F + H), F + H, F + H, acc);
     const float b = a.b10[o0 + col];
 #pragma unroll
-    for (int r = 0; r < 16; ++r) hid[gm_row(r, hi) * L::LDV + o0 + col] = spk_act<ACT>(acc[0][r] + b);
+    for (int r = 0; r < 16; ++r) hid[spk_acc_row(r, hi) * L::LDV + o0 + col] = spk_act<ACT>(acc[0][r] + b);
   }
   __syncthreads();
 
@@ -158,13 +158,13 @@ __global__ __launch_bounds__(64 * kGmWaves) void k_gated_mlp(GmArgs a) {
     const float b = a.b20[o0 + col];
     if (o0 < H) {
 #pragma unroll
-      for (int r = 0; r < 16; ++r) s1[gm_row(r, hi) * L::LDW + o0 + col] = spk_act<ACT>(acc[0][r] + b);
+      for (int r = 0; r < 16; ++r) s1[spk_acc_row(r, hi) * L::LDW + o0 + col] = spk_act<ACT>(acc[0][r] + b);
     } else {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const float g = acc[0][r] + b;
 #pragma unroll
-        for (int c = 0; c < 3; ++c) wv[(c * kGmTile + gm_row(r, hi)) * L::LDW + o0 - H + col] *= g;
+        for (int c = 0; c < 3; ++c) wv[(c * kGmTile + spk_acc_row(r, hi)) * L::LDW + o0 - H + col] *= g;
       }
     }
   }
@@ -192,7 +192,7 @@ __global__ __launch_bounds__(64 * kGmWaves) void k_gated_mlp(GmArgs a) {
     const float b = a.b11[o0 + col], wn = a.w11[(size_t)(o0 + col) * (H + 1) + H];
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int at = gm_row(r, hi);
+      const int at = spk_acc_row(r, hi);
       const float v0 = vw[at], v1 = vw[2 * kGmTile + at], v2 = vw[4 * kGmTile + at];
       h1[at * L::LDW + o0 + col] = spk_act<ACT>(fmaf(wn, gm_norm3(v0, v1, v2), acc[0][r]) + b);
     }

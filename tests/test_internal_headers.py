@@ -52,6 +52,14 @@ def test_shared_definitions_occur_once():
     text = "".join(_read(p) for p in _sources("*.h", "*.hip", "*.cpp"))
     assert text.count("struct MolHeadDev") == 1
     assert text.count("define SPK_TRY") == 1
+    # the matrix-tile convention of the fused kernels lives in spk_mfma_tile.h alone
+    assert text.count("__builtin_amdgcn_mfma_f32_32x32x2f32") == 1
+    assert text.count("(r & 3) + 8 * (r >> 2)") == 1
+    assert text.count('"s_waitcnt lgkmcnt(0)\\n\\ts_barrier"') == 1
+    for name in ("ml_row", "pm_row", "ee_row", "gm_row", "pair_of", "ml_ld<", "pm_ld<", "ML_MFMA", "PM_MFMA", "PM_BARRIER"):
+        assert not re.search(r"\b" + re.escape(name) + (r"\b" if name[-1] != "<" else ""), text), name      # (whole names: ml_row_sums4 stays)
+    home = _read(os.path.join(CSRC, "spk_mfma_tile.h"))
+    assert "__builtin_amdgcn_mfma_f32_32x32x2f32" in home and "(r & 3) + 8 * (r >> 2)" in home and "s_barrier" in home
 
 
 def test_thread_local_state_only_in_the_error_buffer():

@@ -1,7 +1,7 @@
 """CPU model of the lane <-> element maps that the gfx950 MFMA kernels rely on.
 
 There is no GPU in the build container, so the index algebra of
-``schnetpack_amd/csrc/spk_dense.hip`` / ``spk_cfconv.hip`` ("T-GEMM" convention, packed LDS
+``schnetpack_amd/csrc/spk_mfma_tile.h`` / ``spk_cfconv.hip`` ("T-GEMM" convention, packed LDS
 weight image, chained GEMMs that re-use the accumulator as the next B operand, the per-wave
 transposition buffer and the segmented flush) is replayed here lane by lane with numpy, using
 the documented operand layout of ``v_mfma_f32_32x32x2_f32``
