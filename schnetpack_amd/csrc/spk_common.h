@@ -100,6 +100,12 @@ __device__ __forceinline__ float spk_fast_ssp(float x) {
   return fmaf(0.69314718055994531f, __builtin_amdgcn_logf(1.0f + t), fmaxf(x, 0.0f)) - SPK_LN2_F;
 }
 
+// sigmoid alone, select-free: rcp(1 + exp2(-log2(e) x)) -- one multiply, v_exp_f32, one add, v_rcp_f32.  For x << 0 the exponential
+// goes to +inf and v_rcp_f32 returns +0, the correctly flushed value; for x >> 0 it goes to 0 and the result is 1; NaN propagates.
+__device__ __forceinline__ float spk_fast_sigmoid(float x) {
+  return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * x));
+}
+
 template <int ACT>
 __device__ __forceinline__ float spk_act(float x) {
   if (ACT == SPK_ACT_SSP) return spk_ssp(x);

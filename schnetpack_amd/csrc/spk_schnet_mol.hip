@@ -510,12 +510,23 @@ __global__ __launch_bounds__(512) void k_schnet_mol_fwd(MolFwdArgs a) {
       f32x16 yacc;
 #pragma unroll
       for (int r = 0; r < 16; ++r) yacc[r] = 0.f;
-      const int n0 = (ntile + 1) / 2, n1 = 1 + ntile / 2;
-      const int n_iter = n0 > n1 ? n0 : n1;
-      for (int it = 0; it < n_iter; ++it) {
-        const int tile = team == 0 ? 2 * it : 2 * it - 1;
-        const bool in2f = (team == 1 && it == 0);
+      // The loop runs over HALF-STEPS -- one block and one barrier each -- with the teams half a round apart:
+      //     team 0:  hidden(0)  tile(0)    hidden(2)  tile(2)    ...
+      //     team 1:  in2f       hidden(1)  tile(1)    hidden(3)  tile(3)  ...
+      // Waves w and w + 4 share a SIMD: in every half-step it holds one wave in a hidden block (vector work: basis, softplus, split)
+      // and one in a tile block (the GEMM 2 chain), so the matrix chain of one runs beside the vector instructions of the other
+      // instead of both chains together and then both vector blocks, and team 1 does not wait out the tile block of a first round
+      // in which it has only in2f: an even tile count takes one block less than rounds did, an odd one as many
+      // (profiles/r14_mol_stagger.md: the blocks saved are the measured gain, the co-execution alone is none).  Each team visits
+      // its tiles in the order it always did; the count of half-steps is the larger of the two teams' and the same for every wave.
+      const int nh0 = 2 * ((ntile + 1) / 2), nh1 = 1 + 2 * (ntile / 2);
+      const int n_half = nh0 > nh1 ? nh0 : nh1;
+      for (int hs = 0; hs < n_half; ++hs) {
+        const int k = hs - team;                       // the team's own half-step; team 1: -1 = in2f
+        const bool in2f = k < 0;
+        const int tile = in2f ? 0 : 2 * (k >> 1) + team;
         const bool active = !in2f && tile < ntile;
+        const bool hidden = (k & 1) == 0;
         const int pfirst = 32 * tile;
         const int nvalid = active ? ((np - pfirst) < 32 ? (np - pfirst) : 32) : 0;
         if (in2f) {
@@ -533,7 +544,7 @@ __global__ __launch_bounds__(512) void k_schnet_mol_fwd(MolFwdArgs a) {
             *(f32x4*)(sH + el * ML_LD + 32 * t + 8 * q + 4 * hi) = hv;
             if (el < na) spk_st<f32x4>(h_g + (size_t)a0 * NF + 32 * t, (unsigned)((el * NF + 8 * q + 4 * hi) * 4), hv);
           }
-        } else if (active) {
+        } else if (active && hidden) {
           // ---- this wave's quarter of the hidden layer: z[pairs][32t : 32t+32] = ssp(W1 phi + b1)
           // lanes 32..63 mirror lanes 0..31; a padding lane takes the last pair's distance (split form: from the padded records)
           const float d = SP ? sP[pfirst + el].d : sP[pfirst + (el < nvalid ? el : (nvalid - 1))].d;
@@ -589,12 +600,11 @@ __global__ __launch_bounds__(512) void k_schnet_mol_fwd(MolFwdArgs a) {
                 f32x4{spk_fast_ssp(zc[4 * q]), spk_fast_ssp(zc[4 * q + 1]), spk_fast_ssp(zc[4 * q + 2]), spk_fast_ssp(zc[4 * q + 3])};
           }
         }
-        if (l == 0 && it == 0 && team == 0) {
+        if (l == 0 && hs == 0 && team == 0) {
           if constexpr (SP) { if (a.L[0].w2_img) ml_stage_w2_image<256>(sW2, a.L[0].w2_img, tid); else ml_stage_w2_split<256>(sW2h, sW2l, a.L[0].w2, tid); }
           else ml_stage_packed<256, NF * NF / 4>(sW2, a.L[0].w2, NF, KB2, tid);
         }
-        __syncthreads();     // the team's hidden tile (and, in the first round, h) is complete
-        if (active) {
+        if (active && !hidden) {      // (the barrier that ended the previous half-step completed the team's hidden tile -- and h, W2 before tile 0)
           // ---- GEMM 2, operands swapped (rows = pairs, columns = channels 32 t + el): g = W2 z + b2, A operand from LDS
           f32x16 g;
           const int c0 = 32 * t + el;
@@ -699,7 +709,7 @@ __global__ __launch_bounds__(512) void k_schnet_mol_fwd(MolFwdArgs a) {
           }
           }
         }
-        __syncthreads();     // every wave of the team is done with the hidden tile
+        __syncthreads();     // hidden block: the team's hidden tile is complete; tile block: every wave of the team is done with it
       }
       ML_STAMP(2 + 5 * l);
       // the two teams' partial sums: rows = atoms spk_acc_row(r, hi), columns = channels 32 t + el
@@ -858,9 +868,9 @@ __global__ __launch_bounds__(512) void k_schnet_mol_fwd(MolFwdArgs a) {
             if (el < na) spk_st<f32x4>(Hd.pre_h + (size_t)a0 * Hd.H + 32 * hw, (unsigned)((el * Hd.H + 8 * q + 4 * hi) * 4), pv);
             const f32x4 wv2 = *(const f32x4*)(sb2 + 32 * hw + 8 * q + 4 * hi);
             if (Hd.act == SPK_ACT_SILU)
-              part += pv.x * spk_sigmoid(pv.x) * wv2.x + pv.y * spk_sigmoid(pv.y) * wv2.y + pv.z * spk_sigmoid(pv.z) * wv2.z + pv.w * spk_sigmoid(pv.w) * wv2.w;
+              part += pv.x * spk_fast_sigmoid(pv.x) * wv2.x + pv.y * spk_fast_sigmoid(pv.y) * wv2.y + pv.z * spk_fast_sigmoid(pv.z) * wv2.z + pv.w * spk_fast_sigmoid(pv.w) * wv2.w;
             else
-              part += spk_ssp(pv.x) * wv2.x + spk_ssp(pv.y) * wv2.y + spk_ssp(pv.z) * wv2.z + spk_ssp(pv.w) * wv2.w;
+              part += spk_fast_ssp(pv.x) * wv2.x + spk_fast_ssp(pv.y) * wv2.y + spk_fast_ssp(pv.z) * wv2.z + spk_fast_ssp(pv.w) * wv2.w;
           }
           part += __shfl_xor(part, 32, 64);
           if (hi == 0) sH[hw * 32 + el] = part;          // (sH: the hidden tile of the last f2out is no longer needed)
@@ -881,9 +891,9 @@ __global__ __launch_bounds__(512) void k_schnet_mol_fwd(MolFwdArgs a) {
           if (el < na) spk_st<f32x4>(Hd.pre_h + (size_t)a0 * Hd.H + 32 * hw, (unsigned)((el * Hd.H + 8 * q + 4 * hi) * 4), pv);
           const f32x4 wv2 = *(const f32x4*)(Hd.w2 + 32 * hw + 8 * q + 4 * hi);
           if (Hd.act == SPK_ACT_SILU)
-            part += pv.x * spk_sigmoid(pv.x) * wv2.x + pv.y * spk_sigmoid(pv.y) * wv2.y + pv.z * spk_sigmoid(pv.z) * wv2.z + pv.w * spk_sigmoid(pv.w) * wv2.w;
+            part += pv.x * spk_fast_sigmoid(pv.x) * wv2.x + pv.y * spk_fast_sigmoid(pv.y) * wv2.y + pv.z * spk_fast_sigmoid(pv.z) * wv2.z + pv.w * spk_fast_sigmoid(pv.w) * wv2.w;
           else
-            part += spk_ssp(pv.x) * wv2.x + spk_ssp(pv.y) * wv2.y + spk_ssp(pv.z) * wv2.z + spk_ssp(pv.w) * wv2.w;
+            part += spk_fast_ssp(pv.x) * wv2.x + spk_fast_ssp(pv.y) * wv2.y + spk_fast_ssp(pv.z) * wv2.z + spk_fast_ssp(pv.w) * wv2.w;
         }
         part += __shfl_xor(part, 32, 64);
         if (hi == 0) sH[hw * 32 + el] = part;          // (sH: the hidden tile of the last f2out is no longer needed)
@@ -1179,7 +1189,7 @@ __global__ __launch_bounds__(512) void k_schnet_mol_bwd(MolBwdArgs a) {
         float v = 0.f;
         if (row < na) {
           const float pre = Hd.pre_h[(size_t)(a0 + row) * Hd.H + k];
-          const float sg = spk_sigmoid(pre);
+          const float sg = spk_fast_sigmoid(pre);
           const float da = Hd.act == SPK_ACT_SILU ? sg * (1.0f + pre * (1.0f - sg)) : sg;
           v = (Hd.gE ? Hd.gE[Hd.idx_m[a0 + row]] : 1.0f) * Hd.w2[k] * da;
         }
@@ -1278,7 +1288,7 @@ __global__ __launch_bounds__(512) void k_schnet_mol_bwd(MolBwdArgs a) {
 #pragma unroll
         for (int q = 0; q < 4; ++q)
           *(f32x4*)(sGh + el * ML_LD + 32 * t + 8 * q + 4 * hi) =
-              f32x4{acc[4 * q] * spk_sigmoid(pv[q].x), acc[4 * q + 1] * spk_sigmoid(pv[q].y), acc[4 * q + 2] * spk_sigmoid(pv[q].z), acc[4 * q + 3] * spk_sigmoid(pv[q].w)};
+              f32x4{acc[4 * q] * spk_fast_sigmoid(pv[q].x), acc[4 * q + 1] * spk_fast_sigmoid(pv[q].y), acc[4 * q + 2] * spk_fast_sigmoid(pv[q].z), acc[4 * q + 3] * spk_fast_sigmoid(pv[q].w)};
       } else {
         // (sW2 was last read by the derivative tasks of the interaction above: two barriers ago)
         if constexpr (SP) { if (P.w2_img) ml_stage_w2_image<256>(sW2, P.w2_img, tid - 256); else ml_stage_w2_split<256>(sW2h, sW2l, P.w2, tid - 256); }
@@ -1413,9 +1423,7 @@ __global__ __launch_bounds__(512) void k_schnet_mol_bwd(MolBwdArgs a) {
 #pragma unroll
               for (int e = 0; e < 8; ++e) {
                 const int r = 8 * sp + e;
-                float spv, sg;
-                spk_fast_softplus_sigmoid(fmaf(zcx[r], SP_DOWN, zc[r]), spv, sg);
-                v[e] = fmaf(zqx[r], SP_DOWN, zq[r]) * sg;
+                v[e] = fmaf(zqx[r], SP_DOWN, zq[r]) * spk_fast_sigmoid(fmaf(zcx[r], SP_DOWN, zc[r]));
               }
               sp_split8(v, zph[c][sp], zpl[c][sp]);
             }
@@ -1517,9 +1525,7 @@ __global__ __launch_bounds__(512) void k_schnet_mol_bwd(MolBwdArgs a) {
                   const int st = 4 * u + v;
 #pragma unroll
                   for (int r = (16 * st) / NSTEP; r < (16 * (st + 1)) / NSTEP; ++r) {
-                    float sp, sg;
-                    spk_fast_softplus_sigmoid(zc[r], sp, sg);
-                    zq[r] *= sg;
+                    zq[r] *= spk_fast_sigmoid(zc[r]);
                   }
                 }
                 wq = wn;
@@ -1527,9 +1533,7 @@ __global__ __launch_bounds__(512) void k_schnet_mol_bwd(MolBwdArgs a) {
             } else {
 #pragma unroll
               for (int r = 0; r < 16; ++r) {
-                float sp, sg;
-                spk_fast_softplus_sigmoid(zc[r], sp, sg);
-                zq[r] *= sg;
+                zq[r] *= spk_fast_sigmoid(zc[r]);
               }
             }
             zp[c] = zq;
