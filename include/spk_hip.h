@@ -769,6 +769,14 @@ void spk_schnet_mol_set_bwd_task_split(int split);
  * read; the forward still writes it), 2 = require the region: the backward entry points return SPK_ERR_ARG where `saved` has none.
  * Results do not depend on the mode, bit for bit.  Read at launch.  For tuning and tests. */
 void spk_schnet_mol_set_bwd_records(int mode);
+/* Launches of the force call of the standard potential (spk_schnet_potential_forces_f32 / _forces_gr_f32) on those kernels:
+ * 0 = automatic (default): ONE launch, k_schnet_mol_force -- forward and backward of every group in the same workgroup -- where the
+ * split-precision path is on, `saved` has a records region (spk_schnet_t::reserved) and the records mode above is not 1, and the
+ * per-launch profile (spk_profile_enable) is off; otherwise the two launches.  1 = one launch also with the profile on (tag
+ * schnet_mol_force); SPK_ERR_ARG where the call is not eligible.  2 = always two launches.  The environment variable
+ * SPK_MOL_FORCE_LAUNCHES (1 or 2) sets the initial value.  Energies do not depend on the mode, bit for bit; forces agree as two
+ * runs of one mode do.  Read at launch.  Every other entry point keeps its two launches. */
+void spk_schnet_mol_set_force_launches(int mode);
 /* The same for the molecule-resident PaiNN kernels (spk_painn_mol.hip; representation/painn.py:207-256 with q / mu / context rows
  * of a <= 32-atom block in LDS, all interactions in one launch): >= 256 int64; entry 0 = group start, 1 + 8 l .. 8 + 8 l = phase
  * boundaries of interaction l of the forward (thread 0 of workgroup 0); entries 64.. the backward, 128 + 16 w .. the message phase

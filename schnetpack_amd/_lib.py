@@ -226,6 +226,7 @@ _PROTOS = {
     "spk_schnet_mol_set_debug_buffer": (None, [c_f]),
     "spk_schnet_mol_set_bwd_task_split": (None, [ctypes.c_int]),
     "spk_schnet_mol_set_bwd_records": (None, [ctypes.c_int]),
+    "spk_schnet_mol_set_force_launches": (None, [ctypes.c_int]),
     "spk_painn_mol_set_debug_buffer": (None, [c_f]),
     "spk_schnet_saved_floats": (c_i64, [P(SchnetT), c_i64]),
     "spk_schnet_saved_floats_graph": (c_i64, [P(SchnetT), P(GraphT), P(RadialT)]),

@@ -12,6 +12,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 SOURCES = ["spk_util.hip", "spk_dense.hip", "spk_chain.hip", "spk_cfconv.hip", "spk_schnet.hip", "spk_schnet_mol.hip", "spk_painn.hip", "spk_painn_tile.hip", "spk_painn_blk.hip", "spk_painn_mol.hip", "spk_tabfilter.hip", "spk_nbl.hip", "spk_md.hip", "spk_md_thermo.hip", "spk_md_rp_thermo.hip", "spk_potential.hip", "spk_train.hip", "spk_fm.hip", "spk_virial.hip", "spk_zbl.hip", "spk_tensorial.hip", "spk_coulomb.hip", "spk_ewald.hip", "spk_so3.hip", "spk_eembed.hip"]
 HEADERS = ["spk_common.h", "spk_painn_msg.h", "spk_painn_mol.h", "spk_painn_blk.h", "spk_pack.h", "spk_dense.h", "spk_cfconv.h", "spk_schnet_mol.h", "spk_gemm_tn.h", "spk_fm_engine.h", "spk_fm_kernels.h", "spk_fm_chain.h", "spk_split.h", "spk_mfma_tile.h", "spk_filter_split.h", "spk_md_common.h", "spk_so3_tables.h",
+           "spk_schnet_mol_fwd_body.h", "spk_schnet_mol_bwd_body.h",   # the two kernel bodies of spk_schnet_mol.hip, included as text
            "spk_torch_train.h", "spk_torch_fm.h",   # parts of spk_torch.cpp; every header of this directory is listed (tests/test_internal_headers.py)
            os.path.join("..", "..", "include", "spk_hip.h")]
 LIB = os.path.join(HERE, "libspk_hip.so")

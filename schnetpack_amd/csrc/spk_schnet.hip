@@ -255,7 +255,9 @@ extern "C" int spk_schnet_backward_f32(const spk_schnet_t* m, const spk_graph_t*
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// The standard potential  PairwiseDistances -> SchNet -> Atomwise(sum) -> Forces  on batches of small molecules: TWO launches
+// The standard potential  PairwiseDistances -> SchNet -> Atomwise(sum) -> Forces  on batches of small molecules: TWO launches, forward
+// and backward -- and ONE for the force call (energies and forces, dL/dE = 1: schnet_potential_forces below), which runs the two
+// back to back in one kernel
 // (atomistic/distances.py:14-26, representation/schnet.py:147-173, atomistic/atomwise.py:69-88, atomistic/response.py:59-76).
 static bool potential_ok(const spk_schnet_t* m, const spk_head_t* head, const spk_graph_t* g, const spk_radial_t* rb) {
   if (!m || !head || !g || !rb || !m->layers || m->n_interactions <= 0 || !(m->reserved & 1)) return false;
@@ -304,7 +306,7 @@ extern "C" int spk_schnet_potential_backward_f32(const spk_schnet_t* m, const sp
                                     spk_cfconv_gsave_floats(g, rb, m->n_filters), nullptr, gR, gx0, stream);
 }
 
-// Energies and FORCES of the standard potential in the two launches, nothing else: x0 may be NULL (the rows of the nuclear
+// Energies and FORCES of the standard potential in one launch (or the two launches: see below), nothing else: x0 may be NULL (the rows of the nuclear
 // embedding table `emb` [n_types, F] are looked up by Z inside the forward launch), dL/dE is 1 (forces of the summed energy), the
 // backward writes -dE/dR.  all_inside != 0: the caller guarantees that every molecule's atoms lie inside ONE group of the plan and
 // that every molecule has an atom -- the energies are then stored, not accumulated, and E needs no clearing launch.
@@ -325,6 +327,14 @@ static int schnet_potential_forces(const spk_schnet_t* m, const spk_head_t* head
   h.idx_m = idx_m; h.E = E; h.pre_h = pre_h; h.gE = nullptr; h.direct_store = all_inside ? 1 : 0; h.negate = 1;
   const SpkPackTable ptab = schnet_pack_table(m);
   const int64_t gsz = spk_cfconv_gsave_floats(g, rb, m->n_filters);
+  // One launch (k_schnet_mol_force) where the call is eligible -- split path, records region in `saved`, records mode not 1 -- and the
+  // per-launch profile is off; with the profile on the two launches stay, so that its tags schnet_mol_fwd / schnet_mol_bwd keep
+  // telling which half ran and what to book to it.  spk_schnet_mol_set_force_launches(): 1 = one launch regardless, 2 = two.
+  const int launches = spk_schnet_mol_force_launches();
+  const bool can_fuse = spk_schnet_mol_force_eligible(m, g, rb, gsz);
+  SPK_CHECK_ARG(launches != 1 || can_fuse, "%s: force launches = 1, but this call is not eligible for one launch (split path off, no records region, or records mode 1)", who);
+  if (can_fuse && (launches == 1 || (launches == 0 && !spk_prof_enabled())))
+    return spk_schnet_mol_force_ex(m, g, rb, ptab, x0, R, offsets, &h, x_out, saved, gsz, gr, F, stream, x0 ? nullptr : emb, Z, n_types);
   SPK_TRY(spk_schnet_mol_forward_ex(m, g, rb, ptab, x0, nullptr, R, offsets, &h, x_out, saved, gsz, stream, x0 ? nullptr : emb, Z, n_types));
   return spk_schnet_mol_backward_ex(m, g, rb, ptab, nullptr, nullptr, R, offsets, &h, saved, gsz, gr, F, nullptr, stream);
 }

@@ -42,3 +42,9 @@ int spk_schnet_mol_forward_ex(const spk_schnet_t* m, const spk_graph_t* g, const
 int spk_schnet_mol_backward_ex(const spk_schnet_t* m, const spk_graph_t* g, const spk_radial_t* rb, const SpkPackTable& ptab,
                                const float* gx_out, const float* r_ij, const float* R, const float* offsets, const MolHeadDev* head,
                                const float* saved, int64_t gsz, float* gr, float* gR, float* gx0, hipStream_t stream);
+// The force call of the standard potential (forward, then backward with dL/dE = 1) in ONE launch: k_schnet_mol_force.
+int spk_schnet_mol_force_launches();        // spk_schnet_mol_set_force_launches(): 0 = automatic, 1 = one launch, 2 = two launches
+bool spk_schnet_mol_force_eligible(const spk_schnet_t* m, const spk_graph_t* g, const spk_radial_t* rb, int64_t gsz);
+int spk_schnet_mol_force_ex(const spk_schnet_t* m, const spk_graph_t* g, const spk_radial_t* rb, const SpkPackTable& ptab, const float* x0,
+                            const float* R, const float* offsets, const MolHeadDev* head, float* x_out, float* saved, int64_t gsz, float* gr,
+                            float* gR, hipStream_t stream, const float* emb = nullptr, const int64_t* Z = nullptr, int n_types = 0);

@@ -25,6 +25,11 @@
 // Matrix products run on the split-precision path (spk_split.h: fp32
 // operands as two fp16 images on v_mfma_f32_32x32x16_f16; 1e-5 parity with the reference rules out plain bf16 / fp16), or, with
 // spk_set_split(0), on v_mfma_f32_32x32x2_f32 (the <KPB, false> instances).
+//
+// Kernels: k_schnet_mol_fwd<KPB, SP> and k_schnet_mol_bwd<KPB, SP, HO> (further down), one launch each -- and k_schnet_mol_force<KPB>,
+// the FORCE CALL of the standard potential in one launch: the same two bodies back to back in one kernel, a group's backward in the
+// workgroup that ran its forward (spk_schnet_mol_force_ex; which calls take it: schnet_potential_forces in spk_schnet.hip).  The bodies
+// live in spk_schnet_mol_fwd_body.h / spk_schnet_mol_bwd_body.h and are included as text into the kernels that run them.
 #include "spk_common.h"
 #include "spk_pack.h"
 #include "spk_schnet_mol.h"
@@ -427,510 +432,7 @@ __device__ __forceinline__ f32x16 ml_dense_mma8_sum(const f32x4 (&av)[8], const 
 // No atomics, no re-read of the filters, no scatter pass; team 1 runs in2f while team 0 starts the first tile.
 template <int KPB, bool SP>
 __global__ __launch_bounds__(512) void k_schnet_mol_fwd(MolFwdArgs a) {
-  constexpr int NF = 128, KB2 = 16;
-  constexpr int W1F = SP ? 2 * MlW1Image<KPB>::BYTES / 4 : NF * KPB * 8;     // floats of the W1 image(s)
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  float* sW2 = smem;                                  // NF*NF  (SP: high image | low image, 32 KB each)
-  float* sW1 = sW2 + NF * NF;                         // NF*KPB*8  (SP: high image | low image)
-  float* sb1 = sW1 + W1F;                             // NF
-  h16x8* const sW2h = (h16x8*)sW2;
-  h16x8* const sW2l = sW2h + 2048;
-  char* const sW1h = (char*)sW1;
-  char* const sW1l = sW1h + MlW1Image<KPB>::BYTES;
-  float* sb2 = sb1 + NF;                              // NF
-  float* sX = sb2 + NF;                               // [32][ML_LD] atom features x_l
-  float* sH = sX + 32 * ML_LD;                        // h = in2f(x); later the hidden layer of f2out
-  float* sY = sH + 32 * ML_LD;                        // team 0: hidden activations of its pair tile, then its partial y
-  float* sT = sY + 32 * ML_LD;                        // team 1: the same
-  MolPair* sP = (MolPair*)(sT + 32 * ML_LD);          // per pair: local atoms, d, f_c, f_c'
-  float* sRb = (float*)(sP + ML_MAXPAIRS);            // [2][32] radial basis parameters
-  int* sScan = (int*)(sRb + 64);                      // [8] per-wave counts of the pair compaction
-
-  const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);   // wv: SGPR
-  const int hi = lane >> 5, el = lane & 31;
-  const int team = wv >> 2, t = wv & 3;
-  if constexpr (SP) ml_basis_table(sRb, a.rb, tid);          // (offset, exponent coefficient) per slot: ml_basis_split_lin()
-  else if (tid < 64) {
-    const int k = tid & 31;
-    const float* src = (tid < 32) ? a.rb.p0 : a.rb.p1;
-    sRb[tid] = (src && k < a.rb.n_rbf) ? src[k] : 1.0f;
-  }
-
-  for (int grp = blockIdx.x; grp < a.n_groups; grp += gridDim.x) {
-    const int a0 = a.grp_atom0[grp], na = a.grp_atom0[grp + 1] - a0;
-    const int p0 = a.grp_pair0[grp], np_list = a.grp_pair0[grp + 1] - p0;
-    __syncthreads();   // the previous group is done with every LDS buffer
-    ML_STAMP(0);
-
-    // ---- group set-up: features, pair geometry (shared by all interactions), first filter weights
-    for (int s = tid; s < 32 * 32; s += 512) {
-      const int row = s >> 5, c4 = s & 31;
-      f32x4 v = {0.f, 0.f, 0.f, 0.f};
-      if (row < na) {
-        if (a.x0) v = spk_ld<f32x4>(a.x0 + (size_t)a0 * NF, (unsigned)(s * 16));
-        else {
-          const long long z = a.Z[a0 + row];
-          if (z >= 0 && z < a.n_types) v = *(const f32x4*)(a.emb + (size_t)z * NF + 4 * c4);
-          else { const float qn = __builtin_nanf(""); v = f32x4{qn, qn, qn, qn}; }     // no such row (nn.Embedding raises): NaN, never out of bounds
-        }
-      }
-      *(f32x4*)(sX + row * ML_LD + 4 * c4) = v;
-    }
-    // (the records go to `saved` from the registers that hold them, before ml_fwd_pair() below rewrites sP in place)
-    const int np = ml_pair_records(sP, nullptr, sScan, a.half, a.rij, a.R, a.offsets, a.idx_i, a.idx_j, p0, np_list, a0, a.rb.cutoff, a.compact != 0, tid,
-                                   nullptr, a.ho.rec ? &a.ho : nullptr, grp);
-    const int ntile = (np + 31) / 32;
-    if constexpr (SP) {      // (each thread its own record; the barrier at the top of the first interaction publishes them)
-      // The last tile is PADDED here, once per group: entries [np, 32 ntile) are the last pair's record with f_c = 0, so the tile
-      // blocks below read sP at constant offsets and need neither a row count nor a select.  A padding entry and record np - 1 lie
-      // in the same aligned block of 32 -- the same wave, whose LDS reads complete in order before its writes.
-      static_assert(ML_MAXPAIRS % 32 == 0, "the padded last tile must fit sP");
-      if (tid < 32 * ntile) {
-        MolPair q = ml_fwd_pair(sP[tid < np ? tid : np - 1]);
-        if (tid >= np) q.fc = 0.f;
-        sP[tid] = q;
-      }
-    }
-    // (W2 of the first interaction -- first read by GEMM 2 of the first tile -- is staged by team 0 behind its first hidden tile,
-    // while team 1 is still busy with in2f)
-    if constexpr (SP) ml_stage_w1_split<KPB>(sW1h, sW1l, a.L[0].w1, a.rb.n_rbf, tid);
-    else ml_stage_packed<512, NF * KPB * 2>(sW1, a.L[0].w1, a.rb.n_rbf, KPB, tid);
-    if (tid < NF) { sb1[tid] = a.L[0].b1[tid]; sb2[tid] = a.L[0].b2[tid]; }
-
-    for (int l = 0; l < a.n_layers; ++l) {
-      const MolLayerDev& P = a.L[l];
-      float* h_g = a.saved + (int64_t)l * a.N * (2 * NF);
-      float* pre3_g = h_g + a.N * (int64_t)NF;
-      float* g_g = a.gbase + (int64_t)l * a.gsz + (int64_t)p0 * NF;
-      __syncthreads();
-      ML_STAMP(1 + 5 * l);
-
-      // ================= phase A: pair tiles, team 0 takes tiles 0, 2, 4, ..., team 1 in2f and then tiles 1, 3, ...
-      float* zbuf = team ? sT : sY;
-      f32x16 yacc;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) yacc[r] = 0.f;
-      // The loop runs over HALF-STEPS -- one block and one barrier each -- with the teams half a round apart:
-      //     team 0:  hidden(0)  tile(0)    hidden(2)  tile(2)    ...
-      //     team 1:  in2f       hidden(1)  tile(1)    hidden(3)  tile(3)  ...
-      // Waves w and w + 4 share a SIMD: in every half-step it holds one wave in a hidden block (vector work: basis, softplus, split)
-      // and one in a tile block (the GEMM 2 chain), so the matrix chain of one runs beside the vector instructions of the other
-      // instead of both chains together and then both vector blocks, and team 1 does not wait out the tile block of a first round
-      // in which it has only in2f: an even tile count takes one block less than rounds did, an odd one as many
-      // (profiles/r14_mol_stagger.md: the blocks saved are the measured gain, the co-execution alone is none).  Each team visits
-      // its tiles in the order it always did; the count of half-steps is the larger of the two teams' and the same for every wave.
-      const int nh0 = 2 * ((ntile + 1) / 2), nh1 = 1 + 2 * (ntile / 2);
-      const int n_half = nh0 > nh1 ? nh0 : nh1;
-      for (int hs = 0; hs < n_half; ++hs) {
-        const int k = hs - team;                       // the team's own half-step; team 1: -1 = in2f
-        const bool in2f = k < 0;
-        const int tile = in2f ? 0 : 2 * (k >> 1) + team;
-        const bool active = !in2f && tile < ntile;
-        const bool hidden = (k & 1) == 0;
-        const int pfirst = 32 * tile;
-        const int nvalid = active ? ((np - pfirst) < 32 ? (np - pfirst) : 32) : 0;
-        if (in2f) {
-          // ---- h[:, 32t : 32t+32] = x W_in^T  (kept in LDS for the modulation, saved for the backward)
-          f32x16 acc;
-          f32x4 av[16];
-#pragma unroll
-          for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-          ml_dense_load(av, P.in2f_p, t, lane);
-          acc = ml_dense_mma(av, sX, lane, 0, acc);     // (fp32 image: this tile runs beside the other team's first pair tile, off the
-                                                        //  critical path, and its split form pushed the kernel 170 B/lane further into scratch)
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const f32x4 hv = {acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]};
-            *(f32x4*)(sH + el * ML_LD + 32 * t + 8 * q + 4 * hi) = hv;
-            if (el < na) spk_st<f32x4>(h_g + (size_t)a0 * NF + 32 * t, (unsigned)((el * NF + 8 * q + 4 * hi) * 4), hv);
-          }
-        } else if (active && hidden) {
-          // ---- this wave's quarter of the hidden layer: z[pairs][32t : 32t+32] = ssp(W1 phi + b1)
-          // lanes 32..63 mirror lanes 0..31; a padding lane takes the last pair's distance (split form: from the padded records)
-          const float d = SP ? sP[pfirst + el].d : sP[pfirst + (el < nvalid ? el : (nvalid - 1))].d;
-          f32x16 zc;
-#pragma unroll
-          for (int r = 0; r < 16; ++r) zc[r] = sb1[32 * t + spk_acc_row(r, hi)];
-          if constexpr (SP) {
-            // split form: A = the (high, low) images of W1, B = this pair's basis values in the lane's k-slots; three f16 matrix
-            // instructions per k-step, the cross terms in their own accumulator
-            h16x8 ph[2], pl[2], dh_[2], dl_[2];
-            ml_basis_split_lin<KPB, false>(a.rb.kind, sRb, hi, d, ph, pl, dh_, dl_);
-            f32x16 zx;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) zx[r] = 0.f;
-#pragma unroll
-            for (int s = 0; s < (KPB > 2 ? 2 : 1); ++s) {
-              h16x8 wh, wl;
-              ml_w1_operand<KPB>(sW1h, sW1l, s, t * 64 + lane, wh, wl);
-              SP_STEP(wh, wl, ph[s], pl[s], zc, zx);
-            }
-            SP_FOLD(zc, zx);
-            // the hidden tile in LDS as the split A operand of GEMM 2: row = pair, [high: 128 halves | low: 128 halves], contraction
-            // index in accumulator order -- the lane's registers 8 s' .. 8 s' + 7 are slot (2 t + s', hi) as they lie
-            char* zr = (char*)zbuf + el * (ML_LD * 4) + 16 * hi;
-#pragma unroll
-            for (int sp = 0; sp < 2; ++sp) {
-              float v[8];
-#pragma unroll
-              for (int e = 0; e < 8; ++e) v[e] = spk_fast_ssp(zc[8 * sp + e]);
-              h16x8 h, l2;
-              sp_split8(v, h, l2);
-              *(h16x8*)(zr + 32 * (2 * t + sp)) = h;
-              *(h16x8*)(zr + 256 + 32 * (2 * t + sp)) = l2;
-            }
-          } else {
-#pragma unroll
-          for (int u = 0; u < KPB; ++u) {
-            const f32x4 wq = *(const f32x4*)(sW1 + ((t * KPB + u) * 64 + lane) * 4);
-            float ph[4];
-#pragma unroll
-            for (int v = 0; v < 4; ++v) {
-              float dp;
-              ml_rbf(a.rb.kind, a.rb.n_rbf, sRb, sRb + 32, 8 * u + 4 * hi + v, d, ph[v], dp);
-            }
-            zc = SPK_MFMA(wq.x, ph[0], zc);
-            zc = SPK_MFMA(wq.y, ph[1], zc);
-            zc = SPK_MFMA(wq.z, ph[2], zc);
-            zc = SPK_MFMA(wq.w, ph[3], zc);
-          }
-#pragma unroll
-          for (int q = 0; q < 4; ++q)
-            *(f32x4*)(zbuf + el * ML_LD + 32 * t + 8 * q + 4 * hi) =
-                f32x4{spk_fast_ssp(zc[4 * q]), spk_fast_ssp(zc[4 * q + 1]), spk_fast_ssp(zc[4 * q + 2]), spk_fast_ssp(zc[4 * q + 3])};
-          }
-        }
-        if (l == 0 && hs == 0 && team == 0) {
-          if constexpr (SP) { if (a.L[0].w2_img) ml_stage_w2_image<256>(sW2, a.L[0].w2_img, tid); else ml_stage_w2_split<256>(sW2h, sW2l, a.L[0].w2, tid); }
-          else ml_stage_packed<256, NF * NF / 4>(sW2, a.L[0].w2, NF, KB2, tid);
-        }
-        if (active && !hidden) {      // (the barrier that ended the previous half-step completed the team's hidden tile -- and h, W2 before tile 0)
-          // ---- GEMM 2, operands swapped (rows = pairs, columns = channels 32 t + el): g = W2 z + b2, A operand from LDS
-          f32x16 g;
-          const int c0 = 32 * t + el;
-          const float bias2 = sb2[c0];
-#pragma unroll
-          for (int r = 0; r < 16; ++r) g[r] = bias2;
-          if constexpr (SP) {
-            // A = hidden tile (rows = pairs) from LDS, B = W2 image (columns = channels): both split, requested ONE k-step ahead and
-            // fenced there -- the four reads of step s + 1 fly under the three matrix instructions of step s.  (Two and three steps
-            // ahead keep 16 / 32 registers more in flight and gained half as much / nothing: profiles/r12_mol_matrix_overlap.md)
-            constexpr int AHEAD = 1;
-            f32x16 gx;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) gx[r] = 0.f;
-            const h16x8* wbh = sW2h + (t * 8) * 64 + lane;
-            const h16x8* wbl = sW2l + (t * 8) * 64 + lane;
-            const char* zr = (const char*)zbuf + el * (ML_LD * 4) + 16 * hi;
-            h16x8 zh[8], zl[8], wh[8], wl[8];
-#pragma unroll
-            for (int s = 0; s < AHEAD; ++s) {
-              zh[s] = *(const h16x8*)(zr + 32 * s); zl[s] = *(const h16x8*)(zr + 256 + 32 * s);
-              wh[s] = wbh[s * 64]; wl[s] = wbl[s * 64];
-            }
-            ML_FENCE();
-#pragma unroll
-            for (int s = 0; s < 8; ++s) {
-              if (s + AHEAD < 8) {
-                zh[s + AHEAD] = *(const h16x8*)(zr + 32 * (s + AHEAD)); zl[s + AHEAD] = *(const h16x8*)(zr + 256 + 32 * (s + AHEAD));
-                wh[s + AHEAD] = wbh[(s + AHEAD) * 64]; wl[s + AHEAD] = wbl[(s + AHEAD) * 64];
-                ML_FENCE();
-              }
-              SP_STEP(zh[s], zl[s], wh[s], wl[s], g, gx);
-            }
-            SP_FOLD(g, gx);
-          } else {
-            const float* wbase = sW2 + ((int64_t)t * KB2 * 64 + lane) * 4;
-            const float* zrow = zbuf + el * ML_LD + 4 * hi;
-            // both operands come from LDS: requested THREE k-blocks ahead and pinned there (the one-ahead form written here
-            // before was collapsed by the compiler to "two ds_reads, wait for both, four MFMAs": the LDS round trip of every
-            // k-block sat in the MFMA chain)
-            f32x4 wb[KB2], zb[KB2];
-#pragma unroll
-            for (int ug = 0; ug < 3; ++ug) { wb[ug] = *(const f32x4*)(wbase + ug * 256); zb[ug] = *(const f32x4*)(zrow + 8 * ug); }
-            SPK_PIN();
-#pragma unroll
-            for (int ug = 0; ug < KB2; ++ug) {
-              if (ug + 3 < KB2) { wb[ug + 3] = *(const f32x4*)(wbase + (ug + 3) * 256); zb[ug + 3] = *(const f32x4*)(zrow + 8 * (ug + 3)); SPK_PIN(); }
-              g = SPK_MFMA(zb[ug].x, wb[ug].x, g);
-              g = SPK_MFMA(zb[ug].y, wb[ug].y, g);
-              g = SPK_MFMA(zb[ug].z, wb[ug].z, g);
-              g = SPK_MFMA(zb[ug].w, wb[ug].w, g);
-            }
-          }
-          // raw filter outputs for the backward (row = position of the pair in the list, 128-byte row segments per half wave)
-          // ---- and modulation + accumulation on the matrix core: y[atom][c0] += [i = atom] W h[j][c0] + [j = atom] W h[i][c0]
-          float* gt = g_g + 32 * t;
-          if constexpr (SP) {
-            // incidence product on the f16 matrix instruction: A (0 / 1, exact) carries the weight 2^-11 of the low parts itself, so
-            // the accumulator that lives across the tiles stays ONE
-            // Branch-free: a padding row carries the record of the tile's last pair with f_c = 0 (padded once per group, above).  The
-            // hidden layer took that pair's distance for the padded lanes, so the row of g is that pair's row bit for bit and the store
-            // below writes the same value to the same address again (tests/test_gpu_mol_fwd_operands.py); its weight is zero.
-            const MolPair* sQ = sP + pfirst + 4 * hi;    // forward-side records: ml_fwd_pair(); row spk_acc_row(r, hi) = spk_acc_row(r, 0) + 4 hi
-            const char* hcol = (const char*)(sH + c0);
-            const int own = el * (ML_LD * 4);
-#pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2) {
-              float tI[8], tJ[8];
-              h16x8 ai, aj;
-#pragma unroll
-              for (int e = 0; e < 8; ++e) {
-                const int r = 8 * s2 + e;
-                const MolPair rec = sQ[spk_acc_row(r, 0)];
-                const int oi = rec.ij & 0xFFFF, oj = rec.ij >> 16;
-                spk_st<float>(gt, (unsigned)(__float_as_int(rec.dfc) + el * 4), g[r]);
-                const float W = g[r] * rec.fc;
-                tI[e] = W * *(const float*)(hcol + oj); tJ[e] = W * *(const float*)(hcol + oi);
-                ai[e] = oi == own ? (_Float16)1.0f : (_Float16)0.0f;
-                aj[e] = oj == own ? (_Float16)1.0f : (_Float16)0.0f;
-              }
-              h16x8 ih, il, jh, jl;
-              sp_split8(tI, ih, il);
-              sp_split8(tJ, jh, jl);
-              const h16x8 ais = ai * (_Float16)SP_DOWN, ajs = aj * (_Float16)SP_DOWN;
-              yacc = SP_MFMA(ai, ih, yacc);
-              yacc = SP_MFMA(ais, il, yacc);
-              yacc = SP_MFMA(aj, jh, yacc);
-              yacc = SP_MFMA(ajs, jl, yacc);
-            }
-          } else {
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int pr = spk_acc_row(r, hi);
-            const bool ok = pr < nvalid;
-            const MolPair rec = sP[pfirst + (ok ? pr : 0)];
-            const int pi = rec.ij & 255, pj = (rec.ij >> 8) & 255;
-            if (ok) spk_st<float>(gt, (unsigned)(((rec.ij >> 16) * NF + el) * 4), g[r]);
-            const float W = ok ? g[r] * rec.fc : 0.f;
-            const float tI = W * sH[pj * ML_LD + c0], tJ = W * sH[pi * ML_LD + c0];
-            yacc = SPK_MFMA(pi == el ? 1.0f : 0.0f, tI, yacc);
-            yacc = SPK_MFMA(pj == el ? 1.0f : 0.0f, tJ, yacc);
-          }
-          }
-        }
-        __syncthreads();     // hidden block: the team's hidden tile is complete; tile block: every wave of the team is done with it
-      }
-      ML_STAMP(2 + 5 * l);
-      // the two teams' partial sums: rows = atoms spk_acc_row(r, hi), columns = channels 32 t + el
-#pragma unroll
-      for (int r = 0; r < 16; ++r) zbuf[spk_acc_row(r, hi) * ML_LD + 32 * t + el] = yacc[r];
-      __syncthreads();
-      ML_STAMP(4 + 5 * l);
-
-      // ================= phase C1: pre3 = (y0 + y1) W3^T + b3 (saved), hidden = ssp(pre3) -> sH; the other team stages weights
-      // (split instances: the wave that computes the hidden layer writes it to sH as the SPLIT IMAGE, phase C2 reads it with
-      //  ml_dense_mma8_pre -- activations are split once, by whoever writes them.  The input of C1 stays on the on-the-fly form:
-      //  forming and splitting y0 + y1 once costs a pass of the workgroup and a barrier, and did not shorten the phase)
-      f32x4 avC[8];        // team 0: first half of the weight tile of phase C2, requested BEFORE the stores of pre3 -- loads and
-                           // stores share one in-order counter, a load issued behind a store cannot be waited for without it
-      if (team == 0) {
-        f32x4 avA[8], avB[8];
-        ml_dense_load(avA, P.o1_p, t, lane, 0);
-        ml_dense_load(avB, P.o1_p, t, lane, 1);
-        f32x16 acc;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = P.o1_b[32 * t + spk_acc_row(r, hi)];
-        acc = ml_dense_mma8_sum<SP>(avA, sY, sT, lane, 0, acc);
-        acc = ml_dense_mma8_sum<SP>(avB, sY, sT, lane, 1, acc);
-        ml_dense_load(avC, P.o2_p, t, lane, 0);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const f32x4 pv = {acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]};
-          if (el < na) spk_st<f32x4>(pre3_g + (size_t)a0 * NF + 32 * t, (unsigned)((el * NF + 8 * q + 4 * hi) * 4), pv);
-          const f32x4 hv = {spk_fast_ssp(pv.x), spk_fast_ssp(pv.y), spk_fast_ssp(pv.z), spk_fast_ssp(pv.w)};
-          if constexpr (SP) ml_store_split4(sH, el, 32 * t + 8 * q + 4 * hi, hv);
-          else *(f32x4*)(sH + el * ML_LD + 32 * t + 8 * q + 4 * hi) = hv;
-        }
-      } else if (l + 1 < a.n_layers) {     // the filter GEMMs of this interaction are done: their LDS images can be replaced
-        const int t2 = tid - 256;
-        bool staged = false;                // the split instances' one-round-trip form below has written the biases too
-        if constexpr (SP) {
-          if (a.L[l + 1].w2_img) {
-            // every staging load of this thread is requested before the first one is used: ONE round trip to L2.  In turn -- two
-            // batches of the W2 image, W1, the biases: four round trips -- this team reached the barrier 2 ... 3 k cycles behind the
-            // GEMM waves, and the phase was as long as the staging (ML_WSTAMP below; profiles/r09_mol_dense_operands.md)
-            f32x4 v[16];
-            float x0[8], x1[8], bv1 = 0.f, bv2 = 0.f;
-            ml_w2_image_load(v, a.L[l + 1].w2_img, t2);
-            ml_stage_w1_load<KPB>(x0, x1, a.L[l + 1].w1, a.rb.n_rbf, t2);
-            if (t2 < NF) { bv1 = a.L[l + 1].b1[t2]; bv2 = a.L[l + 1].b2[t2]; }
-            SPK_PIN();
-            ml_w2_image_store(sW2, v, t2);
-            ml_stage_w1_store<KPB>(sW1h, sW1l, x0, x1, t2);
-            if (t2 < NF) { sb1[t2] = bv1; sb2[t2] = bv2; }
-            staged = true;
-          } else {
-            ml_stage_w2_split<256>(sW2h, sW2l, a.L[l + 1].w2, t2);
-            ml_stage_w1_split<KPB>(sW1h, sW1l, a.L[l + 1].w1, a.rb.n_rbf, t2);
-          }
-        } else {
-          ml_stage_packed<256, NF * NF / 4>(sW2, a.L[l + 1].w2, NF, KB2, t2);
-          ml_stage_packed<256, NF * KPB * 2>(sW1, a.L[l + 1].w1, a.rb.n_rbf, KPB, t2);
-        }
-        if (!staged && t2 < NF) { sb1[t2] = a.L[l + 1].b1[t2]; sb2[t2] = a.L[l + 1].b2[t2]; }
-      } else {
-        if constexpr (SP) {
-          if (a.head.w1) {
-            // last interaction: this team stages the energy head into the images of the filter network, which nobody reads after the
-            // last phase A -- outnet.0.weight as split A operand -> sW2, its bias -> sb1, outnet.1.weight -> sb2, its bias -> sW1[0];
-            // one round trip, so that the head below starts from LDS (the next group's set-up overwrites all of it behind the
-            // barrier at the top of the group loop)
-            const MolHeadDev& Hd = a.head;
-            int t2 = tid - 256;
-            asm volatile("" : "+v"(t2));      // opaque: the slot addresses are formed here, not ahead of the interaction loop
-            f32x4 v[16];
-            float hb1 = 0.f, hw2 = 0.f, hb2 = 0.f;
-            ml_head_w1_load(v, Hd.w1, Hd.H / 32, t2);
-            if (t2 < Hd.H) { hb1 = Hd.b1[t2]; hw2 = Hd.w2[t2]; }
-            if (t2 == 0 && Hd.b2) hb2 = Hd.b2[0];
-            SPK_PIN();
-            ml_head_w1_store(sW2h, sW2l, v, Hd.H / 32, t2);
-            if (t2 < Hd.H) { sb1[t2] = hb1; sb2[t2] = hw2; }
-            if (t2 == 0) sW1[0] = hb2;
-          }
-        }
-      }
-      if constexpr (SP) { if (l == 1) ML_WSTAMP(64); if (l == 2) ML_WSTAMP(80); }
-      __syncthreads();
-      ML_STAMP(5 + 5 * l);
-
-      // ================= phase C2: x += hidden W4^T + b4
-      if (team == 0) {
-        f32x4 avB[8];
-        ml_dense_load(avB, P.o2_p, t, lane, 1);
-        f32x16 acc;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = P.o2_b[32 * t + spk_acc_row(r, hi)];
-        if constexpr (SP) {
-          acc = ml_dense_mma8_pre(avC, sH, lane, 0, acc);
-          acc = ml_dense_mma8_pre(avB, sH, lane, 1, acc);
-        } else {
-          acc = ml_dense_mma(avC, sH, lane, 0, acc);
-          acc = ml_dense_mma(avB, sH, lane, 1, acc);
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          float* xp = sX + el * ML_LD + 32 * t + 8 * q + 4 * hi;
-          f32x4 xv = *(const f32x4*)xp;
-          xv.x += acc[4 * q]; xv.y += acc[4 * q + 1]; xv.z += acc[4 * q + 2]; xv.w += acc[4 * q + 3];
-          if (el >= na) xv = f32x4{0.f, 0.f, 0.f, 0.f};       // padding rows stay zero (in2f has no bias: h pads stay zero too)
-          *(f32x4*)xp = xv;
-          if (l + 1 == a.n_layers && el < na) spk_st<f32x4>(a.x_out + (size_t)a0 * NF + 32 * t, (unsigned)((el * NF + 8 * q + 4 * hi) * 4), xv);
-          if constexpr (SP) {      // x_L once more as the split image, the B operand of the energy head (sY: last read by phase C1)
-            if (l + 1 == a.n_layers) ml_store_split4(sY, el, 32 * t + 8 * q + 4 * hi, xv);
-          }
-        }
-      }
-      if constexpr (SP) {
-        if (l == 1) ML_WSTAMP(72);
-        // (the interaction counter re-derived through an opaque asm, like the lane in the backward's derivative task -- DESIGN.md
-        //  section 4.3a.  Found by elimination, not in the listing: the per-wave stamp above alone took k_schnet_mol_fwd<3, true> from
-        //  136 to 92 B per lane of scratch and the group set-up from 10.4 k to 8.6 k cycles, and of what the stamp consists of only
-        //  this -- a counter the compiler cannot follow through the loop -- does the same without it; a scheduling barrier, a memory
-        //  clobber or a wait in its place do not.  Presumably the per-interaction addresses are otherwise formed ahead of the loop and
-        //  parked in scratch by the prologue.  profiles/r09_mol_dense_operands.md, section 2)
-        asm volatile("" : "+s"(l));
-      }
-      // (the barrier at the top of the next interaction / group closes this phase)
-    }
-    if (a.head.w1) {
-      // ================= energy head on the atom tile that is still in LDS: y = w2 . act(W1 x + b1) + b2, E[mol] += sum_atoms y
-      const MolHeadDev& Hd = a.head;
-      const int HT = Hd.H / 32;
-      ML_STAMP(101);
-      long long my_mol = -1;
-      if (wv == 1 && lane < 32) my_mol = lane < na ? Hd.idx_m[a0 + lane] : -2;      // wave 1: molecule id of atom `lane`
-      __syncthreads();                    // x_L is complete
-      const int hw = wv;
-      if constexpr (SP) {
-        // split instances: everything the head reads is in LDS -- its weights as staged by team 1 during phase C1 of the last
-        // interaction, x_L as the split image the C2 epilogue wrote to sY.  8 k-steps of three f16 matrix instructions per row tile
-        // in place of 64 dependent fp32 ones behind a round trip for the weights and another for outnet.1.weight.
-        if (hw < HT) {
-          int ln = lane;
-          asm volatile("" : "+v"(ln));      // opaque, as above: nothing of the head is prepared ahead of the group loop
-          const int hi = ln >> 5, el = ln & 31;
-          f32x4 av[16];
-#pragma unroll
-          for (int s = 0; s < 8; ++s) {
-            av[2 * s] = __builtin_bit_cast(f32x4, sW2h[(hw * 8 + s) * 64 + ln]);
-            av[2 * s + 1] = __builtin_bit_cast(f32x4, sW2l[(hw * 8 + s) * 64 + ln]);
-          }
-          f32x16 acc;
-#pragma unroll
-          for (int r = 0; r < 16; ++r) acc[r] = sb1[32 * hw + spk_acc_row(r, hi)];
-          acc = ml_dense_mma_sp_pre<8>(av, (const char*)sY + el * (ML_LD * 4) + 16 * hi, acc);
-          float part = 0.f;
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const f32x4 pv = {acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]};
-            if (el < na) spk_st<f32x4>(Hd.pre_h + (size_t)a0 * Hd.H + 32 * hw, (unsigned)((el * Hd.H + 8 * q + 4 * hi) * 4), pv);
-            const f32x4 wv2 = *(const f32x4*)(sb2 + 32 * hw + 8 * q + 4 * hi);
-            if (Hd.act == SPK_ACT_SILU)
-              part += pv.x * spk_fast_sigmoid(pv.x) * wv2.x + pv.y * spk_fast_sigmoid(pv.y) * wv2.y + pv.z * spk_fast_sigmoid(pv.z) * wv2.z + pv.w * spk_fast_sigmoid(pv.w) * wv2.w;
-            else
-              part += spk_fast_ssp(pv.x) * wv2.x + spk_fast_ssp(pv.y) * wv2.y + spk_fast_ssp(pv.z) * wv2.z + spk_fast_ssp(pv.w) * wv2.w;
-          }
-          part += __shfl_xor(part, 32, 64);
-          if (hi == 0) sH[hw * 32 + el] = part;          // (sH: the hidden tile of the last f2out is no longer needed)
-        }
-      } else
-      if (hw < HT) {
-        f32x4 av[16];                     // (requested after the barrier: register arrays that live across one get spilled)
-#pragma unroll
-        for (int u = 0; u < 16; ++u) av[u] = spk_ld<f32x4>(Hd.w1 + (size_t)(32 * hw) * NF, (unsigned)((el * NF + 8 * u + 4 * hi) * 4));
-        f32x16 acc;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = Hd.b1[32 * hw + spk_acc_row(r, hi)];
-        acc = ml_dense_mma(av, sX, lane, 0, acc);
-        float part = 0.f;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const f32x4 pv = {acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]};
-          if (el < na) spk_st<f32x4>(Hd.pre_h + (size_t)a0 * Hd.H + 32 * hw, (unsigned)((el * Hd.H + 8 * q + 4 * hi) * 4), pv);
-          const f32x4 wv2 = *(const f32x4*)(Hd.w2 + 32 * hw + 8 * q + 4 * hi);
-          if (Hd.act == SPK_ACT_SILU)
-            part += pv.x * spk_fast_sigmoid(pv.x) * wv2.x + pv.y * spk_fast_sigmoid(pv.y) * wv2.y + pv.z * spk_fast_sigmoid(pv.z) * wv2.z + pv.w * spk_fast_sigmoid(pv.w) * wv2.w;
-          else
-            part += spk_fast_ssp(pv.x) * wv2.x + spk_fast_ssp(pv.y) * wv2.y + spk_fast_ssp(pv.z) * wv2.z + spk_fast_ssp(pv.w) * wv2.w;
-        }
-        part += __shfl_xor(part, 32, 64);
-        if (hi == 0) sH[hw * 32 + el] = part;          // (sH: the hidden tile of the last f2out is no longer needed)
-      }
-      ML_STAMP(102);
-      __syncthreads();
-      // wave 1 holds the molecule id of atom (lane) in my_mol: segment heads add their run, one atomic per (group, molecule)
-      if (wv == 1) {
-        float y = 0.f;
-        if (lane < 32) {
-          if constexpr (SP) y = sW1[0];                 // outnet.1.bias as staged with the head's weights (0 when there is none)
-          else y = Hd.b2 ? Hd.b2[0] : 0.f;
-          for (int w = 0; w < HT; ++w) y += sH[w * 32 + lane];
-          if (lane >= na) y = 0.f;
-        }
-        const long long first_mol = __shfl(my_mol, 0, 64);
-        if (__all(lane >= na || my_mol == first_mol)) {
-          // the whole group is one molecule (the usual case): a butterfly over the 32 atom lanes (y is 0 beyond na)
-          float sum = y;
-#pragma unroll
-          for (int m = 16; m >= 1; m >>= 1) sum += __shfl_xor(sum, m, 64);
-          if (lane == 0 && na > 0) { if (Hd.direct_store) Hd.E[my_mol] = sum; else unsafeAtomicAdd(Hd.E + my_mol, sum); }
-        } else {
-          const long long prev = __shfl_up(my_mol, 1, 64);
-          const bool head_of_run = lane < na && (lane == 0 || prev != my_mol);
-          float sum = 0.f;
-          for (int b = 0; b < 32; ++b) {               // runs are contiguous: every head walks forward while the id matches
-            const float yb = spk_readlane_f(y, b);
-            const long long mb = __shfl(my_mol, b, 64);
-            if (head_of_run && b >= lane && b < na && mb == my_mol) sum += yb;
-          }
-          if (head_of_run) { if (Hd.direct_store) Hd.E[my_mol] = sum; else unsafeAtomicAdd(Hd.E + my_mol, sum); }
-        }
-      }
-    }
-    ML_STAMP(31);
-  }
+#include "spk_schnet_mol_fwd_body.h"
 }
 
 // ------------------------------------------------------------------------------------------ host side
@@ -1014,6 +516,9 @@ static int launch_mol_fwd_sp(const MolFwdArgs& a, hipStream_t stream) {
 // pair kernels would compact) the space of the per-call pair list, which these launches leave alone, then -- model word bit 1, lists
 // the molecule-resident backward covers -- the records region: per record of a group its MolPair, per list position the pair vector
 // and the record index, per group the number of records (MolHandoff; spk_schnet_mol_records_region()).
+static int mol_fwd_args(MolFwdArgs& a, const spk_schnet_t* m, const spk_graph_t* g, const spk_radial_t* rb, const SpkPackTable& ptab,
+                        const float* x0, const float* r_ij, const float* R, const float* offsets, const MolHeadDev* head, float* x_out,
+                        float* saved, int64_t gsz, const float* emb, const int64_t* Z, int n_types);
 int spk_schnet_mol_forward(const spk_schnet_t* m, const spk_graph_t* g, const spk_radial_t* rb, const SpkPackTable& ptab,
                            const float* x0, const float* r_ij, float* x_out, float* saved, int64_t gsz, hipStream_t stream) {
   return spk_schnet_mol_forward_ex(m, g, rb, ptab, x0, r_ij, nullptr, nullptr, nullptr, x_out, saved, gsz, stream);
@@ -1022,6 +527,20 @@ int spk_schnet_mol_forward_ex(const spk_schnet_t* m, const spk_graph_t* g, const
                               const float* x0, const float* r_ij, const float* R, const float* offsets, const MolHeadDev* head, float* x_out,
                               float* saved, int64_t gsz, hipStream_t stream, const float* emb, const int64_t* Z, int n_types) {
   MolFwdArgs a;
+  SPK_TRY(mol_fwd_args(a, m, g, rb, ptab, x0, r_ij, R, offsets, head, x_out, saved, gsz, emb, Z, n_types));
+  switch ((rb->n_rbf + 7) / 8) {
+    case 1: return launch_mol_fwd<1>(a, stream);
+    case 2: return launch_mol_fwd<2>(a, stream);
+    case 3: return launch_mol_fwd<3>(a, stream);
+    case 4: return launch_mol_fwd<4>(a, stream);
+  }
+  spk_set_error("spk_schnet_mol_forward: n_rbf = %d unsupported", rb->n_rbf);
+  return SPK_ERR_ARG;
+}
+// the argument block of a forward launch (shared with the one-launch force call)
+static int mol_fwd_args(MolFwdArgs& a, const spk_schnet_t* m, const spk_graph_t* g, const spk_radial_t* rb, const SpkPackTable& ptab,
+                        const float* x0, const float* r_ij, const float* R, const float* offsets, const MolHeadDev* head, float* x_out,
+                        float* saved, int64_t gsz, const float* emb, const int64_t* Z, int n_types) {
   a.R = R; a.offsets = offsets;
   a.emb = emb; a.Z = Z; a.n_types = n_types;
   if (head) a.head = *head; else a.head.w1 = nullptr;
@@ -1045,14 +564,7 @@ int spk_schnet_mol_forward_ex(const spk_schnet_t* m, const spk_graph_t* g, const
   a.compact = spk_schnet_mol_bwd_eligible(m, g, rb) ? 1 : 0;     // only when the molecule-resident backward (which compacts too) will consume `saved`
   a.ho = mol_handoff(m, g, rb, gsz, saved);
   a.dbg = g_mol_dbg;
-  switch ((rb->n_rbf + 7) / 8) {
-    case 1: return launch_mol_fwd<1>(a, stream);
-    case 2: return launch_mol_fwd<2>(a, stream);
-    case 3: return launch_mol_fwd<3>(a, stream);
-    case 4: return launch_mol_fwd<4>(a, stream);
-  }
-  spk_set_error("spk_schnet_mol_forward: n_rbf = %d unsupported", rb->n_rbf);
-  return SPK_ERR_ARG;
+  return SPK_OK;
 }
 
 // ==========================================================================================================
@@ -1106,556 +618,7 @@ struct MolBwdArgs {
 // set-up alone (both in one kernel cost the split instances 48 B per lane of scratch: profiles/r11_mol_bwd_setup.md)
 template <int KPB, bool SP, bool HO>
 __global__ __launch_bounds__(512) void k_schnet_mol_bwd(MolBwdArgs a) {
-  constexpr int NF = 128, NT = 4, KB2 = 16;
-  constexpr int W1F = SP ? 2 * MlW1Image<KPB>::BYTES / 4 : NF * KPB * 8;     // floats of the W1 image(s)
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  float* sW2 = smem;                                  // NF*NF  (SP: high image | low image, 32 KB each)
-  float* sW1 = sW2 + NF * NF;                         // NF*KPB*8  (SP: high image | low image)
-  float* sb1 = sW1 + W1F;                             // NF (+ NF unused: same footprint as the forward)
-  h16x8* const sW2h = (h16x8*)sW2;
-  h16x8* const sW2l = sW2h + 2048;
-  char* const sW1h = (char*)sW1;
-  char* const sW1l = sW1h + MlW1Image<KPB>::BYTES;
-  float* sGx = sb1 + 2 * NF;                          // [32][ML_LD] dL/dx of the current level
-  float* sH = sGx + 32 * ML_LD;                       // h_l (saved by the forward)
-  float* sGy = sH + 32 * ML_LD;                       // dL/dy_l
-  float* sGh = sGy + 32 * ML_LD;                      // dL/dh_l; before that the hidden gradient of f2out
-  MolPair* sP = (MolPair*)(sGh + 32 * ML_LD);         // per pair: local atoms, d, f_c, f_c'
-  int2* sEb = (int2*)(sP + ML_MAXPAIRS);              // per directed edge: ((local pair << 8) | local neighbour, f_c)
-  int* sRow = (int*)(sEb + ML_MAXEDGES);              // [33]
-  int* sCnt = sRow + 36;                              // [4]
-  float* sRb = (float*)(sCnt + 4);                    // [2][32] radial basis parameters
-  float* sS = sRb + 64;                               // [ML_MAXPAIRS][2] per-pair geometry sums, all interactions
-  short* sMap = (short*)(sS + 2 * ML_MAXPAIRS);       // [ML_MAXPAIRS] position in the pair list -> record (-1: beyond the cutoff)
-  int* sScan = (int*)(sMap + ML_MAXPAIRS);            // [8]
-
-  const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);   // wv: SGPR
-  const int hi = lane >> 5, el = lane & 31;
-  if constexpr (SP) ml_basis_table(sRb, a.rb, tid);          // as in the forward: ml_basis_split_lin()
-  else if (tid < 64) {
-    const int k = tid & 31;
-    const float* src = (tid < 32) ? a.rb.p0 : a.rb.p1;
-    sRb[tid] = (src && k < a.rb.n_rbf) ? src[k] : 1.0f;
-  }
-
-  if (a.dbg && tid == 0) { a.dbg[128 + 4 * blockIdx.x] = (long long)__builtin_amdgcn_s_memrealtime(); a.dbg[130 + 4 * blockIdx.x] = (long long)__builtin_readcyclecounter(); }
-  for (int grp = blockIdx.x; grp < a.n_groups; grp += gridDim.x) {
-    const int a0 = a.grp_atom0[grp], na = a.grp_atom0[grp + 1] - a0;
-    const int p0 = a.grp_pair0[grp], np_list = a.grp_pair0[grp + 1] - p0;
-    const int e0 = a.rowptr[a0], ne = a.rowptr[a0 + na] - e0;
-    const int Ltop = a.n_layers - 1;
-    __syncthreads();
-
-    // ---- group set-up.  Everything here is short and latency-bound, so the independent pieces share their round trips and
-    //      barriers: the head's hidden gradient is filled while the pair records are loaded (the first barrier inside
-    //      ml_pair_records() publishes both), the head GEMM (waves 0-3) runs beside the per-edge records (waves 4-7), and the
-    //      filter weights of the top interaction are staged by the idle half of the two Dense phases below -- the derivative tasks
-    //      of phase E are their first reader.
-    const bool with_head = a.head.w1t != nullptr;
-    constexpr bool handoff = HO;
-    MolPair ho_pr = {0, 0.f, 0.f, 0.f};
-    int ho_map = -1, ho_np = 0;
-    float pr3[3] = {0.f, 0.f, 0.f};      // this thread's pair vector: used again at the very end (dL/dr, dL/dR) without going back to memory
-    for (int s = tid; s < 32 * 32; s += 512) {
-      const int row = s >> 5, c4 = s & 31;
-      f32x4 v = {0.f, 0.f, 0.f, 0.f};
-      if (row < na && a.gx_out) v = spk_ld<f32x4>(a.gx_out + (size_t)a0 * NF, (unsigned)(s * 16));
-      *(f32x4*)(sGx + row * ML_LD + 4 * c4) = v;
-      *(f32x4*)(sH + row * ML_LD + 4 * c4) = f32x4{0.f, 0.f, 0.f, 0.f};
-      if (!with_head) *(f32x4*)(sGh + row * ML_LD + 4 * c4) = f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-    ML_STAMP(120);
-    // With the records region of `saved` (written by the forward of this call: ml_pair_records() there) a thread requests its
-    // record, its map entry and its pair vector here, in one round of independent loads in front of those of the head: no chain
-    // half -> idx_i, idx_j -> R, no distance, no cutoff function, no ballot / prefix -- and one barrier, not two.  (Requested at the
-    // top of the group instead, in front of the feature gradient, the set-up is as long: profiles/r11_mol_bwd_setup.md)
-    if constexpr (handoff) {
-      ho_np = a.ho.np[grp];
-      ho_np = ho_np < 0 ? 0 : (ho_np > np_list ? np_list : ho_np);      // (never beyond the group's span of the region)
-      if (tid < np_list) {
-        ho_map = spk_ld<int>(a.ho.map + p0, (unsigned)tid * 4u);
-        pr3[0] = spk_ld<float>(a.ho.vec + 3 * (size_t)p0, (unsigned)tid * 12u);
-        pr3[1] = spk_ld<float>(a.ho.vec + 3 * (size_t)p0, (unsigned)tid * 12u + 4u);
-        pr3[2] = spk_ld<float>(a.ho.vec + 3 * (size_t)p0, (unsigned)tid * 12u + 8u);
-      }
-      if (tid < ho_np) ho_pr = spk_ld<MolPair>(a.ho.rec + p0, (unsigned)tid * 16u);
-    }
-    if (with_head) {
-      // ---- dL/dx_L through the energy head, part 1: the hidden gradient gE[mol] w2 . act'(pre_h) -> sGh[:, :H]
-      //      (the columns beyond H are not read by part 2, and the first Dense phase rewrites sGh in full)
-      const MolHeadDev& Hd = a.head;
-      for (int s = tid; s < 32 * Hd.H; s += 512) {
-        const int row = s / Hd.H, k = s - row * Hd.H;
-        float v = 0.f;
-        if (row < na) {
-          const float pre = Hd.pre_h[(size_t)(a0 + row) * Hd.H + k];
-          const float sg = spk_fast_sigmoid(pre);
-          const float da = Hd.act == SPK_ACT_SILU ? sg * (1.0f + pre * (1.0f - sg)) : sg;
-          v = (Hd.gE ? Hd.gE[Hd.idx_m[a0 + row]] : 1.0f) * Hd.w2[k] * da;
-        }
-        sGh[row * ML_LD + k] = v;
-      }
-    }
-    int np;
-    if constexpr (handoff) {
-      if (tid < np_list) sMap[tid] = (short)ho_map;
-      if (tid < ho_np) sP[tid] = ho_pr;
-      __syncthreads();        // publishes the records and the head's hidden gradient
-      np = ho_np;
-    } else {
-      np = ml_pair_records(sP, sMap, sScan, a.half, a.rij, a.R, a.offsets, a.idx_i, a.idx_j, p0, np_list, a0, a.rb.cutoff, a.compact != 0, tid, pr3);
-    }
-    const int ntile = (np + 31) / 32;
-    ML_STAMP(123);
-    if (wv < NT) {
-      if (with_head) {
-        // ---- part 2: gx += hidden gradient x W1
-        const MolHeadDev& Hd = a.head;
-        const int KH = Hd.H / 8;
-        const int t = wv;
-        f32x16 acc;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-        const float* brow = sGh + el * ML_LD + 4 * hi;
-        for (int c = 0; c < KH; c += 8) {            // H is a multiple of 32 (KH of 4): chunks of eight k-blocks, masked (A = rows of W1^T)
-          f32x4 a8[8];
-#pragma unroll
-          for (int u = 0; u < 8; ++u) {
-            a8[u] = f32x4{0.f, 0.f, 0.f, 0.f};
-            if (c + u < KH) a8[u] = spk_ld<f32x4>(Hd.w1t + (size_t)(32 * t) * Hd.H, (unsigned)((el * Hd.H + 8 * (c + u) + 4 * hi) * 4));
-          }
-#pragma unroll
-          for (int u = 0; u < 8; ++u) {
-            if (c + u < KH) {
-              const f32x4 bv = *(const f32x4*)(brow + 8 * (c + u));
-              acc = SPK_MFMA(a8[u].x, bv.x, acc);
-              acc = SPK_MFMA(a8[u].y, bv.y, acc);
-              acc = SPK_MFMA(a8[u].z, bv.z, acc);
-              acc = SPK_MFMA(a8[u].w, bv.w, acc);
-            }
-          }
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          float* xp = sGx + el * ML_LD + 32 * t + 8 * q + 4 * hi;
-          f32x4 xv = *(const f32x4*)xp;
-          xv.x += acc[4 * q]; xv.y += acc[4 * q + 1]; xv.z += acc[4 * q + 2]; xv.w += acc[4 * q + 3];
-          if (el >= na) xv = f32x4{0.f, 0.f, 0.f, 0.f};
-          *(f32x4*)xp = xv;
-        }
-      }
-    } else {
-      // per directed edge: (row of the saved filter tensor << 8 | local neighbour, f_c); edges of dropped pairs point at the
-      // first record's row with weight 0 (their own row was never written)
-      const int t2 = tid - 256;
-      const int row0 = np > 0 ? (sP[0].ij >> 16) : 0;
-      for (int s = t2; s < ne; s += 256) {
-        const int pos = spk_ld<int>(a.edge_pair + e0, (unsigned)s * 4u) - p0;
-        const int rec = sMap[pos];
-        const int nb = (int)(spk_ld<long long>(a.idx_j + e0, (unsigned)s * 8u) - a0);
-        sEb[s] = rec >= 0 ? make_int2((pos << 8) | nb, __float_as_int(sP[rec].fc)) : make_int2((row0 << 8) | nb | (1 << 24), 0);
-      }
-      for (int s = t2; s < 2 * np; s += 256) sS[s] = 0.f;
-      if (t2 <= na) sRow[t2] = a.rowptr[a0 + t2] - e0;
-    }
-    __syncthreads();
-    ML_STAMP(32);
-
-    for (int l = Ltop; l >= 0; --l) {
-      const MolBwdLayerDev& P = a.L[l];
-      const float* h_g = a.saved + (int64_t)l * a.N * (2 * NF);
-      const float* pre3_g = h_g + a.N * (int64_t)NF;
-      const float* g_g = a.gbase + (int64_t)l * a.gsz + (int64_t)p0 * NF;
-      const bool last = (l == 0) && !a.gx0;     // nothing below consumes dL/dh_0: no row sums, no in2f transpose
-
-      // ================= D1: gt = (gx W4) * ssp'(pre3);  the other half stages W2 of this interaction's filter network
-      if (wv < NT) {
-        const int t = wv;
-        f32x4 avA[8], avB[8];
-        ml_dense_load(avA, P.o2_t, t, lane, 0);
-        ml_dense_load(avB, P.o2_t, t, lane, 1);
-        f32x16 acc;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-        f32x4 pv[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          pv[q] = f32x4{0.f, 0.f, 0.f, 0.f};
-          if (el < na) pv[q] = spk_ld<f32x4>(pre3_g + (size_t)a0 * NF + 32 * t, (unsigned)((el * NF + 8 * q + 4 * hi) * 4));
-        }
-        acc = ml_dense_mma<SP>(avA, sGx, lane, 0, acc);
-        acc = ml_dense_mma<SP>(avB, sGx, lane, 1, acc);
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-          *(f32x4*)(sGh + el * ML_LD + 32 * t + 8 * q + 4 * hi) =
-              f32x4{acc[4 * q] * spk_fast_sigmoid(pv[q].x), acc[4 * q + 1] * spk_fast_sigmoid(pv[q].y), acc[4 * q + 2] * spk_fast_sigmoid(pv[q].z), acc[4 * q + 3] * spk_fast_sigmoid(pv[q].w)};
-      } else {
-        // (sW2 was last read by the derivative tasks of the interaction above: two barriers ago)
-        if constexpr (SP) { if (P.w2_img) ml_stage_w2_image<256>(sW2, P.w2_img, tid - 256); else ml_stage_w2_split<256>(sW2h, sW2l, P.w2, tid - 256); }
-        else ml_stage_packed<256, NF * NF / 4>(sW2, P.w2, NF, KB2, tid - 256);
-      }
-      if (tid == 0) { sCnt[0] = 0; sCnt[1] = 0; }
-      __syncthreads();
-      ML_STAMP(33 + 6 * (Ltop - l));
-
-      // ================= D2: gy = gt W3;  the other half loads h_l and stages W1, b1
-      if (wv < NT) {
-        const int t = wv;
-        f32x4 avA[8], avB[8];
-        ml_dense_load(avA, P.o1_t, t, lane, 0);
-        ml_dense_load(avB, P.o1_t, t, lane, 1);
-        f32x16 acc;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-        acc = ml_dense_mma<SP>(avA, sGh, lane, 0, acc);
-        acc = ml_dense_mma<SP>(avB, sGh, lane, 1, acc);
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-          *(f32x4*)(sGy + el * ML_LD + 32 * t + 8 * q + 4 * hi) = f32x4{acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]};
-      } else {
-        const int t2 = tid - 256;
-        for (int s = t2; s < na * 32; s += 256) {
-          const int row = s >> 5, c4 = s & 31;
-          *(f32x4*)(sH + row * ML_LD + 4 * c4) = spk_ld<f32x4>(h_g + (size_t)a0 * NF, (unsigned)(s * 16));
-        }
-        if constexpr (SP) ml_stage_w1_split<KPB>(sW1h, sW1l, P.w1, a.rb.n_rbf, t2);
-        else ml_stage_packed<256, NF * KPB * 2>(sW1, P.w1, a.rb.n_rbf, KPB, t2);
-        if (t2 < NF) sb1[t2] = P.b1[t2];
-      }
-      __syncthreads();
-      ML_STAMP(34 + 6 * (Ltop - l));
-
-      // ================= E: derivative tasks (pair tile, pair of channel tiles) + row-sum tasks (one atom, all channels)
-      // The queue hands out the derivative tasks first, then the row sums, then -- unless nothing below consumes dL/dx -- the four
-      // channel tiles of G (gx += gh W_in): G only waits for the row sums (a counter in LDS), not for the derivative tasks, so it
-      // runs on the waves that the derivative tasks leave idle instead of being a phase of its own.
-      // A derivative task covers pair tile `tile` and the channel-tile pairs [tp0, tp1): the hidden layer of the filter network does
-      // not depend on the channel tile, so a task computes it once and loops over its channel-tile pairs behind it.  `split` tasks
-      // per tile (uniform over the group): 1 = one task does both pairs (hidden layer once per tile), 2 = one pair each (twice).
-      // Automatic = 1 for every group.  The candidate exception -- two tasks per tile while they fit one round, 2 ntile <= 8 -- lost
-      // where it would apply (profiles/r07_mol_bwd_task_split.md; backward launch, 1 against 2 tasks per tile): 256 ethanol frames,
-      // groups of 2 ... 4 tiles, 61.7 against 65.9 us; 16-atom blobs, 8 tiles, 76.5 against 92.1 us; aspirin, 5 tiles, 63.6 against
-      // 73.0 us -- spread of the call times 0.2 ... 0.4 us.
-      const int split = a.task_split ? a.task_split : 1;
-      const int nder = split * ntile;
-      const int nrow = (last || np == 0) ? 0 : na;
-      const int ng = last ? 0 : NT;
-      if (np == 0 && !last) {    // no pair inside the cutoff: dL/dh = 0 (the buffer still holds the hidden gradient of f2out)
-        for (int s = tid; s < 32 * 32; s += 512) *(f32x4*)(sGh + (s >> 5) * ML_LD + 4 * (s & 31)) = f32x4{0.f, 0.f, 0.f, 0.f};
-        __syncthreads();         // (uniform over the workgroup)
-      }
-      while (true) {
-        int k = 0;
-        if (lane == 0) k = atomicAdd(&sCnt[0], 1);
-        k = __builtin_amdgcn_readfirstlane(k);
-        if (k >= nder + nrow + ng) break;
-        if (k >= nder + nrow) {
-          // ---- G, channel tile t: gx[:, 32 t : 32 t + 32] += gh W_in (weights requested before the wait for the row sums)
-          const int t = k - nder - nrow;
-          f32x4 avA[8], avB[8];
-          ml_dense_load(avA, P.in2f_t, t, lane, 0);
-          ml_dense_load(avB, P.in2f_t, t, lane, 1);
-          if (nrow > 0) {
-            while (__hip_atomic_load(&sCnt[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < nrow) __builtin_amdgcn_s_sleep(2);
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-          }
-          f32x16 acc;
-#pragma unroll
-          for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-          acc = ml_dense_mma<SP>(avA, sGh, lane, 0, acc);
-          acc = ml_dense_mma<SP>(avB, sGh, lane, 1, acc);
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            float* xp = sGx + el * ML_LD + 32 * t + 8 * q + 4 * hi;
-            f32x4 xv = *(const f32x4*)xp;
-            xv.x += acc[4 * q]; xv.y += acc[4 * q + 1]; xv.z += acc[4 * q + 2]; xv.w += acc[4 * q + 3];
-            if (el >= na) xv = f32x4{0.f, 0.f, 0.f, 0.f};
-            *(f32x4*)xp = xv;
-            if (l == 0 && el < na) spk_st<f32x4>(a.gx0 + (size_t)a0 * NF + 32 * t, (unsigned)((el * NF + 8 * q + 4 * hi) * 4), xv);
-          }
-          continue;
-        }
-        if (k >= nder) {
-          // ---- gh[a][c] = sum over the row of a of gy[b][c] g[pair][c] f_c
-          ml_row_sums4<10>(sGh, sGy, g_g, sEb, sRow, k - nder, lane);
-          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-          if (lane == 0) atomicAdd(&sCnt[1], 1);
-          continue;
-        }
-        const int tile = split == 2 ? k >> 1 : k;
-        const int tp0 = split == 2 ? (k & 1) : 0, tp1 = split == 2 ? tp0 + 1 : 2;
-        const int pfirst = 32 * tile;
-        const int nvalid = (np - pfirst) < 32 ? (np - pfirst) : 32;
-        const bool valid = el < nvalid;
-        const int pl = pfirst + (valid ? el : (nvalid - 1));
-        const MolPair pr = sP[pl];
-        const float fc = valid ? pr.fc : 0.f, dfc = valid ? pr.dfc : 0.f;
-        const int pi = pr.ij & 255, pj = (pr.ij >> 8) & 255;
-        const int grow = pr.ij >> 16;                       // row of this pair in the saved filter tensor
-        float* const sums = sS + 2 * pl;                    // this pair's (s1, s2)
-        if constexpr (SP) {
-          // ---- split form (spk_split.h).  GEMM 1, value and derivative, for the four hidden tiles: A = the W1 images, B = this pair's
-          // basis values / slopes in the lane's k-slots; z' = sigmoid(a) a' goes from the accumulator registers into the B operand
-          // of GEMM 2' as it lies (W2 is staged with its contraction index in accumulator order).
-          // (lane re-derived through an opaque asm: the LDS offsets below are then formed here and not hoisted out of the task loop
-          //  into the prologue of the kernel, where the allocator parks them in scratch -- section 4.3a of DESIGN.md)
-          int lane_o = lane;
-          asm volatile("" : "+v"(lane_o));
-          const int hi_o = lane_o >> 5;
-          h16x8 ph[2], pl[2], dh[2], dl[2];
-          ml_basis_split_lin<KPB, true>(a.rb.kind, sRb, hi_o, pr.d, ph, pl, dh, dl);
-          h16x8 zph[NT][2], zpl[NT][2];
-#pragma unroll
-          for (int c = 0; c < NT; ++c) {
-            f32x16 zc, zcx, zq, zqx;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) { zc[r] = sb1[32 * c + spk_acc_row(r, hi_o)]; zcx[r] = 0.f; zq[r] = 0.f; zqx[r] = 0.f; }
-#pragma unroll
-            for (int s = 0; s < (KPB > 2 ? 2 : 1); ++s) {
-              h16x8 wh, wl;
-              ml_w1_operand<KPB>(sW1h, sW1l, s, c * 64 + lane_o, wh, wl);
-              SP_STEP(wh, wl, ph[s], pl[s], zc, zcx);
-              SP_STEP(wh, wl, dh[s], dl[s], zq, zqx);
-            }
-#pragma unroll
-            for (int sp = 0; sp < 2; ++sp) {
-              float v[8];
-#pragma unroll
-              for (int e = 0; e < 8; ++e) {
-                const int r = 8 * sp + e;
-                v[e] = fmaf(zqx[r], SP_DOWN, zq[r]) * spk_fast_sigmoid(fmaf(zcx[r], SP_DOWN, zc[r]));
-              }
-              sp_split8(v, zph[c][sp], zpl[c][sp]);
-            }
-          }
-          // ---- GEMM 2' per channel tile (rows = channels 32 t + spk_acc_row(r, hi), columns = pairs): g' = W2 z'
-          const float* gyi_p = sGy + pi * ML_LD + 4 * hi_o;
-          const float* gyj_p = sGy + pj * ML_LD + 4 * hi_o;
-          const float* hi_p = sH + pi * ML_LD + 4 * hi_o;
-          const float* hj_p = sH + pj * ML_LD + 4 * hi_o;
-#pragma unroll 1
-          for (int tp = tp0; tp < tp1; ++tp) {
-            // the saved raw filter outputs of this lane's pair for both channel tiles of the pair: requested in front of the
-            // matrix instructions of this iteration, used behind them
-            f32x4 gl[2][4];
-#pragma unroll
-            for (int tt = 0; tt < 2; ++tt)
-#pragma unroll
-              for (int q = 0; q < 4; ++q) gl[tt][q] = spk_ld<f32x4>(g_g + 64 * tp, (unsigned)((grow * NF + 4 * hi + 32 * tt + 8 * q) * 4));
-            float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-            for (int tt = 0; tt < 2; ++tt) {
-              const int t = 2 * tp + tt;
-              f32x16 gp, gpx;
-#pragma unroll
-              for (int r = 0; r < 16; ++r) { gp[r] = 0.f; gpx[r] = 0.f; }
-              const h16x8* wbh = sW2h + (t * 8) * 64 + lane_o;
-              const h16x8* wbl = sW2l + (t * 8) * 64 + lane_o;
-              h16x8 wh[8], wl[8];
-#pragma unroll
-              for (int s = 0; s < 2; ++s) { wh[s] = wbh[s * 64]; wl[s] = wbl[s * 64]; }
-              ML_FENCE();      // (fenced: with the pin alone every k-step waited for reads issued directly in front of it)
-#pragma unroll
-              for (int s = 0; s < 8; ++s) {
-                if (s + 2 < 8) { wh[s + 2] = wbh[(s + 2) * 64]; wl[s + 2] = wbl[(s + 2) * 64]; ML_FENCE(); }
-                SP_STEP(wh[s], wl[s], zph[s >> 1][s & 1], zpl[s >> 1][s & 1], gp, gpx);
-              }
-              SP_FOLD(gp, gpx);
-#pragma unroll
-              for (int q = 0; q < 4; ++q) {
-                const int col = 32 * t + 8 * q;
-                const f32x4 gyi = *(const f32x4*)(gyi_p + col), gyj = *(const f32x4*)(gyj_p + col);
-                const f32x4 hvi = *(const f32x4*)(hi_p + col), hvj = *(const f32x4*)(hj_p + col);
-                const f32x4 gq = gl[tt][q];
-                const float D0 = gp[4 * q] * fc + gq.x * dfc, D1 = gp[4 * q + 1] * fc + gq.y * dfc;
-                const float D2 = gp[4 * q + 2] * fc + gq.z * dfc, D3 = gp[4 * q + 3] * fc + gq.w * dfc;
-                s1 += gyi.x * hvj.x * D0 + gyi.y * hvj.y * D1 + gyi.z * hvj.z * D2 + gyi.w * hvj.w * D3;
-                s2 += gyj.x * hvi.x * D0 + gyj.y * hvi.y * D1 + gyj.z * hvi.z * D2 + gyj.w * hvi.w * D3;
-              }
-            }
-            // one partial per channel-tile pair, added in the order tp = 0, 1 (the LDS operations of a wave stay in order): with one
-            // task per tile the sum of a pair is built by one wave in one order
-            s1 += __shfl_xor(s1, 32, 64);
-            s2 += __shfl_xor(s2, 32, 64);
-            if (hi == 0 && valid) { atomicAdd(sums, s1); atomicAdd(sums + 1, s2); }
-          }
-        } else {
-        float phi[KPB][4], dphi[KPB][4];
-#pragma unroll
-        for (int u = 0; u < KPB; ++u)
-#pragma unroll
-          for (int v = 0; v < 4; ++v) ml_rbf(a.rb.kind, a.rb.n_rbf, sRb, sRb + 32, 8 * u + 4 * hi + v, pr.d, phi[u][v], dphi[u][v]);
-        // ---- GEMM 1, value and derivative (rows = hidden channels, columns = pairs): z' = sigmoid(W1 phi + b1) * (W1 phi')
-        // Software-pipelined by hand: a wave issues in order, so an activation block placed between two MFMA groups leaves the
-        // matrix pipe idle for its whole length.  The MFMAs of hidden tile c + 1 are therefore interleaved with the activations
-        // of tile c (one or two of its 16 accumulator rows per MFMA pair): the VALU work runs in the shadow of the MFMAs.
-        f32x16 zp[NT];
-        {
-          constexpr int NSTEP = 4 * KPB;
-          f32x4 wq = *(const f32x4*)(sW1 + lane * 4);
-          f32x16 zc, zq;
-#pragma unroll
-          for (int r = 0; r < 16; ++r) { zc[r] = sb1[spk_acc_row(r, hi)]; zq[r] = 0.f; }
-#pragma unroll
-          for (int u = 0; u < KPB; ++u) {
-            f32x4 wn = wq;
-            if (u + 1 < NT * KPB) wn = *(const f32x4*)(sW1 + ((u + 1) * 64 + lane) * 4);
-            zc = SPK_MFMA(wq.x, phi[u][0], zc); zq = SPK_MFMA(wq.x, dphi[u][0], zq);
-            zc = SPK_MFMA(wq.y, phi[u][1], zc); zq = SPK_MFMA(wq.y, dphi[u][1], zq);
-            zc = SPK_MFMA(wq.z, phi[u][2], zc); zq = SPK_MFMA(wq.z, dphi[u][2], zq);
-            zc = SPK_MFMA(wq.w, phi[u][3], zc); zq = SPK_MFMA(wq.w, dphi[u][3], zq);
-            wq = wn;
-          }
-#pragma unroll
-          for (int c = 0; c < NT; ++c) {
-            f32x16 zcn = zc, zqn = zq;
-            if (c + 1 < NT) {
-#pragma unroll
-              for (int r = 0; r < 16; ++r) { zcn[r] = sb1[32 * (c + 1) + spk_acc_row(r, hi)]; zqn[r] = 0.f; }
-#pragma unroll
-              for (int u = 0; u < KPB; ++u) {
-                const int nxt = (c + 1) * KPB + u + 1;
-                f32x4 wn = wq;
-                if (nxt < NT * KPB) wn = *(const f32x4*)(sW1 + (nxt * 64 + lane) * 4);
-                const float wv4[4] = {wq.x, wq.y, wq.z, wq.w};
-#pragma unroll
-                for (int v = 0; v < 4; ++v) {
-                  zcn = SPK_MFMA(wv4[v], phi[u][v], zcn);
-                  zqn = SPK_MFMA(wv4[v], dphi[u][v], zqn);
-                  const int st = 4 * u + v;
-#pragma unroll
-                  for (int r = (16 * st) / NSTEP; r < (16 * (st + 1)) / NSTEP; ++r) {
-                    zq[r] *= spk_fast_sigmoid(zc[r]);
-                  }
-                }
-                wq = wn;
-              }
-            } else {
-#pragma unroll
-              for (int r = 0; r < 16; ++r) {
-                zq[r] *= spk_fast_sigmoid(zc[r]);
-              }
-            }
-            zp[c] = zq;
-            zc = zcn; zq = zqn;
-          }
-        }
-        // ---- GEMM 2' per channel tile (rows = channels 32 t + spk_acc_row(r, hi), columns = pairs): g' = W2 z'
-        const float* gyi_p = sGy + pi * ML_LD + 4 * hi;
-        const float* gyj_p = sGy + pj * ML_LD + 4 * hi;
-        const float* hi_p = sH + pi * ML_LD + 4 * hi;
-        const float* hj_p = sH + pj * ML_LD + 4 * hi;
-#pragma unroll 1
-        for (int tp = tp0; tp < tp1; ++tp) {
-          // the saved raw filter outputs of this lane's pair for both channel tiles of the pair: requested in front of the
-          // matrix instructions of this iteration, used behind them
-          f32x4 gl[2][4];
-#pragma unroll
-          for (int tt = 0; tt < 2; ++tt)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) gl[tt][q] = spk_ld<f32x4>(g_g + 64 * tp, (unsigned)((grow * NF + 4 * hi + 32 * tt + 8 * q) * 4));
-          float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-          for (int tt = 0; tt < 2; ++tt) {
-            const int t = 2 * tp + tt;
-            f32x16 gp;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) gp[r] = 0.f;
-            {
-              // weights from LDS, requested three k-blocks ahead and pinned there (the one-ahead form was collapsed by the compiler
-              // to "ds_read, wait, four MFMAs": a derivative task alone on its SIMD then waits out the LDS round trip of every k-block)
-              const float* wbase = sW2 + ((int64_t)t * KB2 * 64 + lane) * 4;
-              f32x4 wb[KB2];
-#pragma unroll
-              for (int ug = 0; ug < 3; ++ug) wb[ug] = *(const f32x4*)(wbase + ug * 256);
-              SPK_PIN();
-#pragma unroll
-              for (int ug = 0; ug < KB2; ++ug) {
-                const int c = ug >> 2, q = ug & 3;
-                if (ug + 3 < KB2) { wb[ug + 3] = *(const f32x4*)(wbase + (ug + 3) * 256); SPK_PIN(); }
-                gp = SPK_MFMA(wb[ug].x, zp[c][4 * q + 0], gp);
-                gp = SPK_MFMA(wb[ug].y, zp[c][4 * q + 1], gp);
-                gp = SPK_MFMA(wb[ug].z, zp[c][4 * q + 2], gp);
-                gp = SPK_MFMA(wb[ug].w, zp[c][4 * q + 3], gp);
-              }
-            }
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-              const int col = 32 * t + 8 * q;
-              const f32x4 gyi = *(const f32x4*)(gyi_p + col), gyj = *(const f32x4*)(gyj_p + col);
-              const f32x4 hvi = *(const f32x4*)(hi_p + col), hvj = *(const f32x4*)(hj_p + col);
-              const f32x4 gq = gl[tt][q];
-              const float D0 = gp[4 * q] * fc + gq.x * dfc, D1 = gp[4 * q + 1] * fc + gq.y * dfc;
-              const float D2 = gp[4 * q + 2] * fc + gq.z * dfc, D3 = gp[4 * q + 3] * fc + gq.w * dfc;
-              s1 += gyi.x * hvj.x * D0 + gyi.y * hvj.y * D1 + gyi.z * hvj.z * D2 + gyi.w * hvj.w * D3;
-              s2 += gyj.x * hvi.x * D0 + gyj.y * hvi.y * D1 + gyj.z * hvi.z * D2 + gyj.w * hvi.w * D3;
-            }
-          }
-          // one partial per channel-tile pair, added in the order tp = 0, 1 (the LDS operations of a wave stay in order): with one
-          // task per tile the sum of a pair is built by one wave in one order
-          s1 += __shfl_xor(s1, 32, 64);
-          s2 += __shfl_xor(s2, 32, 64);
-          if (hi == 0 && valid) { atomicAdd(sums, s1); atomicAdd(sums + 1, s2); }
-        }
-        }
-      }
-      ML_STAMP(35 + 6 * (Ltop - l));
-      __syncthreads();
-      ML_STAMP(36 + 6 * (Ltop - l));
-      if (last) break;
-
-    }
-
-    // ---- dL/dr of both directions of every pair, once for all interactions (pairs beyond the cutoff: zero); with gR the pair's
-    //      contribution (s1 + s2) r / d is parked in LDS for the per-atom pass below (sGh is free by now)
-    float* sV = sGh;                                    // [ML_MAXPAIRS][3]
-    if (a.gR) __syncthreads();
-    if (tid < np_list) {                                // one pair per thread (np_list <= ML_MAXPAIRS < 512), its vector still in registers
-      const int s = tid;
-      const int rec = sMap[s];
-      float s1 = 0.f, s2 = 0.f;
-      if (rec >= 0) {
-        const float d = sP[rec].d;
-        const float inv = d > 0.f ? 1.0f / d : 0.f;
-        s1 = sS[2 * rec] * inv; s2 = sS[2 * rec + 1] * inv;
-      }
-      const float rx = pr3[0], ry = pr3[1], rz = pr3[2];
-      if (a.gr) {
-        const int64_t e = a.half[p0 + s];
-        const int64_t e2 = a.rev[e];
-        a.gr[3 * e] = s1 * rx; a.gr[3 * e + 1] = s1 * ry; a.gr[3 * e + 2] = s1 * rz;
-        a.gr[3 * e2] = -s2 * rx; a.gr[3 * e2 + 1] = -s2 * ry; a.gr[3 * e2 + 2] = -s2 * rz;
-      }
-      if (a.gR && rec >= 0) {
-        const float w = s1 + s2;
-        sV[3 * rec] = w * rx; sV[3 * rec + 1] = w * ry; sV[3 * rec + 2] = w * rz;
-      }
-    }
-    // ---- dL/dR: the transpose of r_ij = R_j - R_i + offsets, per atom over its row (each pair of the atom appears once
-    //      there): the pair (i, j) with canonical vector r gives -(s1 + s2) r / d to i and +(s1 + s2) r / d to j.  Fixed order.
-    if (a.gR) {
-      __syncthreads();
-      // eight lanes per (atom, component): they walk the row's edges with stride 8 and meet by shuffles (fixed order)
-      const int slot = tid & 7, q = tid >> 3;          // q < 64 >= 3 * na / ... : na <= 21 atoms fill 63 of the 64 groups; larger groups loop
-      for (int s = q; s < 3 * na; s += 64) {
-        const int at = s / 3, comp = s - 3 * at;
-        float acc = 0.f;
-        for (int e = sRow[at] + slot; e < sRow[at + 1]; e += 8) {
-          const int x = sEb[e].x;
-          if (x & (1 << 24)) continue;
-          const int rec = sMap[(x >> 8) & 0xFFFF];
-          const float v = sV[3 * rec + comp];
-          acc += ((sP[rec].ij & 255) == at) ? -v : v;
-        }
-        acc += __shfl_xor(acc, 1, 64);
-        acc += __shfl_xor(acc, 2, 64);
-        acc += __shfl_xor(acc, 4, 64);
-        if (slot == 0) a.gR[3 * (size_t)(a0 + at) + comp] = a.head.negate ? -acc : acc;
-      }
-    }
-    ML_STAMP(63);
-  }
-  if (a.dbg && tid == 0) { a.dbg[129 + 4 * blockIdx.x] = (long long)__builtin_amdgcn_s_memrealtime(); a.dbg[131 + 4 * blockIdx.x] = (long long)__builtin_readcyclecounter(); }
+#include "spk_schnet_mol_bwd_body.h"
 }
 
 static size_t mol_bwd_lds(int kpb, bool sp) {
@@ -1689,11 +652,68 @@ static int launch_mol_bwd_sp(const MolBwdArgs& a, hipStream_t stream) {
   return SPK_OK;
 }
 
+// ==========================================================================================================
+// The force call in ONE launch: forward and backward of the standard potential (spk_schnet.hip: schnet_potential_forces) back to
+// back in one kernel -- the two bodies above as they are, split path and records hand-over on.  Both launches use the same grid and
+// the same loop over the groups, so a group's backward runs in the workgroup that ran its forward, and it reads nothing another
+// workgroup wrote: dL/dE is 1 on this route, the energies are outputs only.  What goes away is a launch boundary per call.
+// The argument block is the two launches' blocks side by side (about 1.6 KB of the 4 KB kernarg segment): both bodies index their
+// table of interactions with a run-time counter, which needs the table in memory as the kernarg segment has it, and the existing
+// kernels keep their layouts -- the geometry pointers the two have in common are what is stored twice.
+// ==========================================================================================================
+struct MolForceArgs { MolFwdArgs f; MolBwdArgs b; };
+static_assert(sizeof(MolForceArgs) <= 2048, "the kernarg segment of k_schnet_mol_force stays well under 4 KB");
+
+template <int KPB>
+__global__ __launch_bounds__(512) void k_schnet_mol_force(MolForceArgs fa) {
+  constexpr bool SP = true, HO = true;
+  {
+    const MolFwdArgs& a = fa.f;
+#include "spk_schnet_mol_fwd_body.h"
+  }
+  // Between the halves: the forward wrote h, pre3, the raw filter rows g, the records region and pre_h with global stores, and OTHER
+  // threads of this workgroup read them below.  Release / barrier / acquire at WORKGROUP scope suffices: the eight waves of a
+  // workgroup sit on one compute unit and share its vector L1, which writes through -- a wave's release waits for its stores, and a
+  // load issued behind the barrier by any wave of the same unit sees them.  No line of these buffers can be stale in that L1 either:
+  // the workgroup reads none of them before it has written its groups' part.  (Nothing of another workgroup is read, so nothing
+  // wider than the workgroup is needed; the compiler, which sees the stores, keeps the loads below off the scalar cache.)
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __syncthreads();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+  {
+    const MolBwdArgs& a = fa.b;
+#include "spk_schnet_mol_bwd_body.h"
+  }
+}
+
+template <int KPB>
+static int launch_mol_force(const MolForceArgs& a, hipStream_t stream) {
+  const size_t lf = mol_fwd_lds(KPB, true), lb = mol_bwd_lds(KPB, true);
+  const size_t lds = lf > lb ? lf : lb;
+  auto kern = k_schnet_mol_force<KPB>;
+  static SpkPerDevice attr_set;
+  int attr_dev;
+  if (attr_set.pending(&attr_dev)) {
+    SPK_HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    attr_set.mark(attr_dev);
+  }
+  int grid = a.f.n_groups;
+  const int maxg = spk_num_cus();
+  if (grid > maxg) grid = maxg;
+  SpkProfScope prof("schnet_mol_force", stream);
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, stream, a);
+  SPK_LAUNCH_CHECK();
+  return SPK_OK;
+}
+
 // n_rbf up to 24 (3 k-blocks): the LDS budget of the backward (per-pair sums) ends there; wider bases take the general driver
 bool spk_schnet_mol_bwd_eligible(const spk_schnet_t* m, const spk_graph_t* g, const spk_radial_t* rb) {
   return spk_schnet_mol_eligible(m, g, rb) && (rb->n_rbf + 7) / 8 <= 3 && !getenv("SPK_NO_MOL_BWD");
 }
 
+static int mol_bwd_args(MolBwdArgs& a, const spk_schnet_t* m, const spk_graph_t* g, const spk_radial_t* rb, const SpkPackTable& ptab,
+                        const float* gx_out, const float* r_ij, const float* R, const float* offsets, const MolHeadDev* head,
+                        const float* saved, int64_t gsz, float* gr, float* gR, float* gx0);
 int spk_schnet_mol_backward(const spk_schnet_t* m, const spk_graph_t* g, const spk_radial_t* rb, const SpkPackTable& ptab,
                             const float* gx_out, const float* r_ij, const float* saved, int64_t gsz, float* gr, float* gx0,
                             hipStream_t stream) {
@@ -1703,6 +723,19 @@ int spk_schnet_mol_backward_ex(const spk_schnet_t* m, const spk_graph_t* g, cons
                                const float* gx_out, const float* r_ij, const float* R, const float* offsets, const MolHeadDev* head,
                                const float* saved, int64_t gsz, float* gr, float* gR, float* gx0, hipStream_t stream) {
   MolBwdArgs a;
+  SPK_TRY(mol_bwd_args(a, m, g, rb, ptab, gx_out, r_ij, R, offsets, head, saved, gsz, gr, gR, gx0));
+  switch ((rb->n_rbf + 7) / 8) {
+    case 1: return launch_mol_bwd<1>(a, stream);
+    case 2: return launch_mol_bwd<2>(a, stream);
+    case 3: return launch_mol_bwd<3>(a, stream);
+  }
+  spk_set_error("spk_schnet_mol_backward: n_rbf = %d unsupported", rb->n_rbf);
+  return SPK_ERR_ARG;
+}
+// the argument block of a backward launch (shared with the one-launch force call)
+static int mol_bwd_args(MolBwdArgs& a, const spk_schnet_t* m, const spk_graph_t* g, const spk_radial_t* rb, const SpkPackTable& ptab,
+                        const float* gx_out, const float* r_ij, const float* R, const float* offsets, const MolHeadDev* head,
+                        const float* saved, int64_t gsz, float* gr, float* gR, float* gx0) {
   a.R = R; a.offsets = offsets; a.gR = gR;
   if (head) a.head = *head; else { a.head.w1 = nullptr; a.head.w1t = nullptr; a.head.negate = 0; }
   const bool split = spk_get_split() != 0;
@@ -1728,11 +761,36 @@ int spk_schnet_mol_backward_ex(const spk_schnet_t* m, const spk_graph_t* g, cons
   a.ho = mol_handoff(m, g, rb, gsz, saved);
   SPK_CHECK_ARG(g_mol_bwd_records != 2 || a.ho.rec, "spk_schnet_mol_backward: records mode 2, but `saved` of this model / list has no records region");
   if (g_mol_bwd_records == 1) a.ho.rec = nullptr;
+  return SPK_OK;
+}
+
+// ---- the force call: one launch or two.  0 = automatic (one launch where the call is eligible and the per-launch profile is off:
+// the profile's unit is the launch, and its tags schnet_mol_fwd / schnet_mol_bwd are how the two halves are told apart and booked),
+// 1 = one launch even with the profile on (tag schnet_mol_force; an error where the call is not eligible), 2 = always two launches.
+// SPK_MOL_FORCE_LAUNCHES in the environment sets the initial value: one build runs both ways under an unmodified caller.
+static int g_mol_force_launches = [] { const char* e = getenv("SPK_MOL_FORCE_LAUNCHES"); return (e && (e[0] == '1' || e[0] == '2') && !e[1]) ? e[0] - '0' : 0; }();
+extern "C" void spk_schnet_mol_set_force_launches(int mode) { g_mol_force_launches = (mode == 1 || mode == 2) ? mode : 0; }
+int spk_schnet_mol_force_launches() { return g_mol_force_launches; }
+// eligible: the split path is on, `saved` has a records region and the backward is not told to ignore it
+bool spk_schnet_mol_force_eligible(const spk_schnet_t* m, const spk_graph_t* g, const spk_radial_t* rb, int64_t gsz) {
+  int64_t off = 0, floats = 0;
+  return spk_get_split() != 0 && g_mol_bwd_records != 1 && gsz > 0 && spk_schnet_mol_bwd_eligible(m, g, rb) &&
+         spk_schnet_mol_records_region(m, g, rb, &off, &floats);
+}
+int spk_schnet_mol_force_ex(const spk_schnet_t* m, const spk_graph_t* g, const spk_radial_t* rb, const SpkPackTable& ptab, const float* x0,
+                            const float* R, const float* offsets, const MolHeadDev* head, float* x_out, float* saved, int64_t gsz, float* gr,
+                            float* gR, hipStream_t stream, const float* emb, const int64_t* Z, int n_types) {
+  SPK_CHECK_ARG(head && head->w1 && head->w1t && !head->gE, "spk_schnet_mol_force: the one-launch call is the forces route (energy head, dL/dE = 1)");
+  SPK_CHECK_ARG(spk_schnet_mol_force_eligible(m, g, rb, gsz), "spk_schnet_mol_force: call not eligible for one launch (split path off, or no records region in `saved`, or records mode 1)");
+  MolForceArgs a;
+  SPK_TRY(mol_fwd_args(a.f, m, g, rb, ptab, x0, nullptr, R, offsets, head, x_out, saved, gsz, emb, Z, n_types));
+  SPK_TRY(mol_bwd_args(a.b, m, g, rb, ptab, nullptr, nullptr, R, offsets, head, saved, gsz, gr, gR, nullptr));
+  SPK_CHECK_ARG(a.f.ho.rec && a.b.ho.rec, "spk_schnet_mol_force: no records region");
   switch ((rb->n_rbf + 7) / 8) {
-    case 1: return launch_mol_bwd<1>(a, stream);
-    case 2: return launch_mol_bwd<2>(a, stream);
-    case 3: return launch_mol_bwd<3>(a, stream);
+    case 1: return launch_mol_force<1>(a, stream);
+    case 2: return launch_mol_force<2>(a, stream);
+    case 3: return launch_mol_force<3>(a, stream);
   }
-  spk_set_error("spk_schnet_mol_backward: n_rbf = %d unsupported", rb->n_rbf);
+  spk_set_error("spk_schnet_mol_force: n_rbf = %d unsupported", rb->n_rbf);
   return SPK_ERR_ARG;
 }

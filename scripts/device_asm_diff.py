@@ -4,12 +4,14 @@
 
 For every file of build.SOURCES the parent revision (default HEAD) and the working tree are compiled with
 `hipcc <flags_for(src)> --offload-device-only -S`; the two assembly texts are compared after the lines that contain
-`__hip_cuid_` are dropped (a hash of the compilation unit, which changes with any edit).  One line per file; exit
+`__hip_cuid_` are dropped (a hash of the compilation unit, which changes with any edit).  One line per file, and for a file
+that differs one line per function (identical / CHANGED / new / gone: a file that gained a kernel differs as a whole); exit
 status 1 if any file differs.
 """
 import argparse
 import difflib
 import os
+import re
 import subprocess
 import sys
 import tarfile
@@ -31,6 +33,21 @@ def device_asm(tree, src, out):
                           stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
     with open(out) as f:
         return [ln for ln in f if "__hip_cuid_" not in ln]
+
+
+def functions(lines):
+    """{symbol: its lines} of an assembly text: from the label of a mangled function to its .Lfunc_end."""
+    out, cur = {}, None
+    for ln in lines:
+        if cur is None:
+            m = re.match(r"^(_Z\w+):", ln)
+            if m:
+                cur = out.setdefault(m.group(1), [])
+        elif ln.startswith(".Lfunc_end"):
+            cur = None
+        else:
+            cur.append(ln)
+    return out
 
 
 def main():
@@ -61,7 +78,13 @@ def main():
                 else:
                     d = [ln for ln in difflib.unified_diff(a, b, "parent", "branch", n=0) if ln[0] in "+-" and ln[:3] not in ("+++", "---")]
                     print("%-24s DIFFERENT  %6d / %d lines, %d changed" % (s, len(a), len(b), len(d)))
-                    sys.stdout.writelines("    " + ln for ln in d[:40])
+                    # per function: a file that gained a kernel differs as a whole, its other kernels need not
+                    fa, fb = functions(a), functions(b)
+                    for name in sorted(set(fa) | set(fb)):
+                        state = "new" if name not in fa else "gone" if name not in fb else "identical" if fa[name] == fb[name] else "CHANGED"
+                        print("    %-9s %6d lines  %s" % (state, len(fb.get(name, fa.get(name))), name))
+                    if any(n in fa and n in fb and fa[n] != fb[n] for n in fa):
+                        sys.stdout.writelines("    " + ln for ln in d[:40])
                     differ += 1
     return 1 if differ else 0
 
